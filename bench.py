@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — CpG-sites/sec segmented on synthetic hg19-shaped betas (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--samples 32] [--sites 28217448]
+    python bench.py [--gpus N --steps K --warmup W] [--samples 32] [--sites 28217448] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one whole `segment` job over the resident beta bytes: scan/validate pass, window extents, block scoring,
@@ -80,7 +80,38 @@ def parse():
     ap.add_argument('--e2e', type=int, default=1, help='also time the CLI end to end on page-cached files (1 GPU only; 0: skip)')
     ap.add_argument('--oversubscribe', action='store_true',
                     help='dry runs of the N > 1 forms on fewer GPUs than shares / ranks (several shares per device): without this flag such a launch is refused')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the border lists the last timed step returned as DIR/<name>.npy (see dump_outputs)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BYTES_MAX = 64 << 20        # --dump-outputs: at most this many bytes of .npy data in all
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: what a caller of the timed path receives from one step, the absolute border list of every region, as float64
+    .npy files (border sites < 2^53: exact).  borders.npy holds the lists one after the other, region_offsets.npy where each region's
+    list starts in it (n_regions + 1 entries).  Should the borders exceed the byte budget, borders.npy holds a fixed seeded sample of
+    them, in order, and border_index.npy their positions in the whole.  -> {name: shape} of the files written."""
+    lists = [np.asarray(r, dtype=np.int64) for r in res]
+    off = np.zeros(len(lists) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([r.size for r in lists])
+    flat = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+    arrays = {'region_offsets': off.astype(np.float64)}
+    cap = (DUMP_BYTES_MAX - arrays['region_offsets'].nbytes) // 8
+    if flat.size <= cap:
+        arrays['borders'] = flat.astype(np.float64)
+    else:
+        idx = np.sort(np.random.default_rng(SEED).choice(flat.size, size=cap // 2, replace=False))
+        arrays['borders'] = flat[idx].astype(np.float64)
+        arrays['border_index'] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(op.join(d, name + '.npy'), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -657,6 +688,9 @@ def main():
     if multi:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:           # before anything else reuses the buffer the lists are views into
+        dumped = {'dir': args.dump_outputs, 'files': dump_outputs(args.dump_outputs, res)}
 
     # what ran where: one (host, device) per share / rank, so that the line can only state the devices it really used
     import socket
@@ -1033,6 +1067,8 @@ def main():
                 rows.append({'samples': 32, 'islands': True, 'failed': repr(e)})
             out['matrix'] = {'what': 'the same whole-genome step at the other sample counts of the metric (inputs resident, 1 warm-up, timed with '
                                      'synchronize + perf_counter around the steps like the main run)', 'rows': rows}
+        if dumped is not None:
+            out['dump_outputs'] = dumped
         print(json.dumps(out), flush=True)
     if seg is not None:
         seg.close()

@@ -167,6 +167,35 @@ def offset_chunks(spec):
 CHR21 = dict(n=400000, a=0, samples=list(range(8)), pcount=15.0, max_cpg=1000, max_bp=2000, chunk=60000)
 
 
+def random_world(seed):
+    """A random world for the restatement against the reference binary (tests/test_oracle_golden.py, tests/golden/random_world_cases.json):
+    dense runs, equal positions, long gaps; zero, saturated and meth == cov counts; a random sample count, a pseudo count nobody chose
+    (any float in 2^-12 .. 2^12, besides 0 and the usual ones), random window limits, and three random chunks (start0, len) of it.
+    -> (slices, loci, pcount, max_cpg, max_bp, chunks)"""
+    rng = np.random.default_rng(31000 + seed)
+    n = int(rng.integers(300, 2500))
+    n_samples = int(rng.choice([1, 2, 3, 5, 9]))
+    kind = rng.integers(0, 4, n)
+    gap = np.where(kind == 0, 0, np.where(kind == 1, rng.integers(1, 12, n), np.where(kind == 2, rng.integers(2, 300, n), rng.integers(300, 9000, n))))
+    loci = (np.cumsum(gap) + 1000).astype(np.uint32)
+    slices = []
+    for _ in range(n_samples):
+        cov = rng.integers(0, 256, n)
+        mode = rng.integers(0, 6, n)
+        cov = np.where(mode == 0, 0, np.where(mode == 1, 255, cov))
+        meth = np.minimum(cov, np.where(mode == 2, cov, np.where(mode == 3, 0, rng.integers(0, 256, n))))
+        slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
+    pcount = float(np.float32(rng.choice([0.0, 0.5, 1.0, 15.0, float(np.exp2(rng.uniform(-12, 12))), float(np.exp2(rng.uniform(-12, 12)))])))
+    max_cpg = int(rng.choice([2, 7, 60, 61, 129, 500, 1000]))
+    max_bp = int(rng.choice([1, 40, 700, 2000, 100000]))
+    chunks = []
+    for _ in range(3):
+        ln = int(rng.integers(1, n + 1))
+        st = int(rng.integers(0, n - ln + 1))
+        chunks.append((st, ln))
+    return slices, loci, pcount, max_cpg, max_bp, chunks
+
+
 def lbeta_twin(data):
     """uint16 [n, 2] twin of a uint8 beta array for the .lbeta-input cases: (meth, cov) of site i times k(i) = 1 + (i * 2654435761 mod 997)
     (<= 54 * 997 < 65536; keeps meth <= cov)."""

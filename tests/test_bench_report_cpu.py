@@ -1,6 +1,7 @@
 """bench.py's N > 1 line states the devices it really used (missing 2): `n_gpus` counts DISTINCT physical devices, the
 number of shares / ranks and the number asked for are separate fields.  Pure formatter: no GPU, no torch."""
 import importlib.util
+import os
 import os.path as op
 
 ROOT = op.dirname(op.dirname(op.abspath(__file__)))
@@ -84,3 +85,32 @@ def test_synthetic_pat_text_and_bgzf_writer(tmp_path):
     assert gzip.open(gz, 'rb').read() == text
     assert b''.join(pat2beta.bgzf_pieces(gz)) == text
     assert b''.join(pat2beta.pat_chunks(gz)) == text
+
+
+def test_dump_outputs_writes_the_border_lists_as_float64(tmp_path):
+    import numpy as np
+    res = [np.array([1, 4, 9, 12], dtype=np.int32), np.array([12, 13], dtype=np.int32), np.array([13, 28217449], dtype=np.int32)]
+    files = bench.dump_outputs(str(tmp_path / 'out'), res)
+    assert files == {'region_offsets': [4], 'borders': [8]}
+    off = np.load(tmp_path / 'out' / 'region_offsets.npy')
+    flat = np.load(tmp_path / 'out' / 'borders.npy')
+    assert off.dtype == flat.dtype == np.float64
+    assert [flat[int(off[r]):int(off[r + 1])].astype(np.int64).tolist() for r in range(len(res))] == [r.tolist() for r in res]
+
+
+def test_dump_outputs_samples_a_larger_output_the_same_way_every_time(tmp_path, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, 'DUMP_BYTES_MAX', 4096)
+    res = [np.arange(1, 3001, dtype=np.int32), np.arange(3000, 5001, dtype=np.int32)]
+    got = []
+    for k in range(2):
+        d = tmp_path / ('out%d' % k)
+        files = bench.dump_outputs(str(d), res)
+        assert sum(os.path.getsize(d / (n + '.npy')) - 128 for n in files) <= 4096
+        got.append({n: np.load(d / (n + '.npy')) for n in files})
+    flat = np.concatenate(res)
+    idx = got[0]['border_index'].astype(np.int64)
+    assert (np.diff(idx) > 0).all() and np.array_equal(got[0]['borders'], flat[idx].astype(np.float64))
+    assert got[0]['region_offsets'].tolist() == [0, 3000, 5001]
+    for n in got[0]:
+        assert np.array_equal(got[0][n], got[1][n])

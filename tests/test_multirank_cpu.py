@@ -16,7 +16,11 @@ WORKER = textwrap.dedent('''
     import os, sys, json
     import numpy as np
     sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
+    import torch
     import torch.distributed as dist
+    # CPU-only ranks: every barrier asks for the machine's accelerator, and that question alone wakes the HIP runtime, which then
+    # holds the GPU open in each rank on a GPU box; the answer the gloo ranks act on is the CPU either way
+    torch._C._get_accelerator = lambda *a, **k: torch.device('cpu')
     from wgbs_tools_amd import synth, parallel, segment as S, _lib
     from test_driver_cpu import OracleEngine, FickleEngine, _tree_merge
     rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
@@ -224,7 +228,11 @@ WORKER8 = textwrap.dedent('''
     import os, sys
     import numpy as np
     sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
+    import torch
     import torch.distributed as dist
+    # CPU-only ranks: every barrier asks for the machine's accelerator, and that question alone wakes the HIP runtime, which then
+    # holds the GPU open in each rank on a GPU box; the answer the gloo ranks act on is the CPU either way
+    torch._C._get_accelerator = lambda *a, **k: torch.device('cpu')
     from wgbs_tools_amd import synth, parallel
     from test_driver_cpu import FickleEngine, _tree_merge
     rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
