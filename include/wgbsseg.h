@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 220            /* 0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 230            /* 0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -413,6 +413,31 @@ int wgbsseg_patbeta_finish(wgbsseg_patbeta* pb, int32_t lbeta, void* out, char* 
 void wgbsseg_patbeta_destroy(wgbsseg_patbeta* pb);
 /* device time (ms, HIP events) of the counting-kernel launches of all chunks fed so far; waits for them.  < 0: error */
 double wgbsseg_patbeta_kernel_ms(wgbsseg_patbeta* pb);
+
+/*
+ * pat -> per-block U / X / M read counts (`wgbstools homog`: homog.py:61-131 pipes `gunzip -c x.pat.gz` into the reference's
+ * homog binary, src/homog/homog.cpp:154-260).  create(): the blocks [start_cpg[j], end_cpg[j]) already sorted by
+ * (startCpG, endCpG) (refused otherwise; startCpG >= 1, endCpG > startCpG, endCpG < 2^31), the bin edges range[0 .. n_bins]
+ * (ascending float32, 1 <= n_bins <= 8), min_cpgs (the reference's -l) and inclusive (--inclusive).  feed(): a chunk of pat
+ * TEXT made of whole lines, as for wgbsseg_patbeta_feed (asynchronous, the text is copied).  A read `chr, s, pattern, count`
+ * covering [s, s + len) adds `count` to one bin of every block it overlaps, as long as s < endCpG of the LAST block: the
+ * pattern clipped to the overlap (inclusive: the whole pattern) must be at least min_cpgs long and hold at least min_cpgs
+ * C / H / T; meth = (float)#C,H / (float)#C,H,T picks bin b with range[b] <= meth < range[b + 1] (meth == 1: the last bin).
+ * finish(): counts[n_blocks * n_bins] (int32, row-major, sorted block order).  finish() returns WGBSSEG_E_ARG naming the byte
+ * offset of the first malformed line (fewer than four fields, a site / count that is not a number), or else of the first read
+ * that starts before the read before it (the reference's output then depends on the reads' order).
+ * wgbsseg_homog_kernel_ms: device time (HIP events) of the counting kernel over all chunks fed so far; waits for them.
+ * wgbsseg_debug_homog_bins (test hook, device 0): out[t (t + 1) / 2 + nrC] = the device's bin for every (nrC, nrT) with
+ * t = nrC + nrT <= max_total (-1: below range[0]).
+ */
+typedef struct wgbsseg_homog wgbsseg_homog;
+int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, const float* range, int32_t n_bins,
+                         int32_t min_cpgs, int32_t inclusive, wgbsseg_homog** out, char* err, size_t errlen);
+int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char* err, size_t errlen);
+int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t errlen);
+void wgbsseg_homog_destroy(wgbsseg_homog* h);
+double wgbsseg_homog_kernel_ms(wgbsseg_homog* h);
+int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_total, int8_t* out);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

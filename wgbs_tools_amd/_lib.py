@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 220          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 230          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -36,7 +36,9 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_patbeta_destroy', 'wgbsseg_patbeta_kernel_ms', 'wgbsseg_group_load_host_async', 'wgbsseg_group_load_wait',
            'wgbsseg_marker_stats', 'wgbsseg_blocks_parse', 'wgbsseg_blocks_write_table', 'wgbsseg_blocks_write_bedgraph',
            'wgbsseg_format_fixed', 'wgbsseg_bed_parse', 'wgbsseg_bed_write_annotated', 'wgbsseg_debug_canonical_float',
-           'wgbsseg_first_batch_items', 'wgbsseg_plan_shares_weighted']
+           'wgbsseg_first_batch_items', 'wgbsseg_plan_shares_weighted',
+           'wgbsseg_homog_create', 'wgbsseg_homog_feed', 'wgbsseg_homog_finish', 'wgbsseg_homog_destroy', 'wgbsseg_homog_kernel_ms',
+           'wgbsseg_debug_homog_bins']
 
 
 class NativeLibraryError(RuntimeError):
@@ -209,6 +211,18 @@ def load():
     L.wgbsseg_patbeta_destroy.argtypes = [vp]
     L.wgbsseg_patbeta_kernel_ms.restype = C.c_double
     L.wgbsseg_patbeta_kernel_ms.argtypes = [vp]
+    L.wgbsseg_homog_create.restype = i32
+    L.wgbsseg_homog_create.argtypes = [i32, vp, vp, i64, vp, i32, i32, i32, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.wgbsseg_homog_feed.restype = i32
+    L.wgbsseg_homog_feed.argtypes = [vp, C.c_char_p, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_homog_finish.restype = i32
+    L.wgbsseg_homog_finish.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_homog_destroy.restype = None
+    L.wgbsseg_homog_destroy.argtypes = [vp]
+    L.wgbsseg_homog_kernel_ms.restype = C.c_double
+    L.wgbsseg_homog_kernel_ms.argtypes = [vp]
+    L.wgbsseg_debug_homog_bins.restype = i32
+    L.wgbsseg_debug_homog_bins.argtypes = [vp, i32, i32, vp]
     L.wgbsseg_marker_stats.restype = i32
     L.wgbsseg_marker_stats.argtypes = [vp, vp, i32, vp, i32, i64, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_add_loci.restype = i32
@@ -512,6 +526,58 @@ class PatBeta:
 
     def __exit__(self, *a):
         self.close()
+
+
+class Homog:
+    """wgbsseg_homog: pat text -> int32 counts[n_blocks][n_bins] of the blocks [starts, ends) (sorted by (start, end)) on one GPU."""
+
+    def __init__(self, starts, ends, edges, min_cpgs, inclusive=False, device=0):
+        self._L = load()
+        self._h = C.c_void_p()
+        self._err = C.create_string_buffer(ERRLEN)
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(ends, dtype=np.int64)
+        r = np.ascontiguousarray(edges, dtype=np.float32)
+        if s.shape != e.shape or s.ndim != 1 or r.ndim != 1 or r.size < 2:
+            raise ValueError('starts / ends: one value per block; edges: n_bins + 1 values')
+        self.n_blocks, self.n_bins = int(s.size), int(r.size) - 1
+        _check(self._L.wgbsseg_homog_create(int(device), s.ctypes.data, e.ctypes.data, s.size, r.ctypes.data, self.n_bins, int(min_cpgs),
+                                            1 if inclusive else 0, C.byref(self._h), self._err, ERRLEN), self._err)
+
+    def feed(self, text):
+        """text: bytes made of whole lines (must end with a newline)"""
+        _check(self._L.wgbsseg_homog_feed(self._h, text, len(text), self._err, ERRLEN), self._err)
+
+    def kernel_ms(self):
+        """device time of the counting kernel over every chunk fed so far (waits for them)"""
+        return float(self._L.wgbsseg_homog_kernel_ms(self._h))
+
+    def finish(self):
+        out = np.empty((self.n_blocks, self.n_bins), dtype=np.int32)
+        _check(self._L.wgbsseg_homog_finish(self._h, out.ctypes.data, self._err, ERRLEN), self._err)
+        return out
+
+    def close(self):
+        if self._h:
+            self._L.wgbsseg_homog_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def debug_homog_bins(edges, max_total):
+    """wgbsseg_debug_homog_bins: int8 bins of every (nrC, nrT) with t = nrC + nrT <= max_total, at t (t + 1) / 2 + nrC"""
+    L = load()
+    r = np.ascontiguousarray(edges, dtype=np.float32)
+    out = np.empty((max_total + 1) * (max_total + 2) // 2, dtype=np.int8)
+    rc = L.wgbsseg_debug_homog_bins(r.ctypes.data, r.size - 1, int(max_total), out.ctypes.data)
+    if rc != OK:
+        raise SegmentorError(rc, 'debug_homog_bins failed')
+    return out
 
 
 def _stats_dict(stats):

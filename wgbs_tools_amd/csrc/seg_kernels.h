@@ -2764,16 +2764,14 @@ __device__ __forceinline__ bool wg_parse_int(const PatText& t, int64_t& i, int64
     return true;
 }
 
-__global__ __launch_bounds__(WG_BLOCK) void k_pat_count(const char* __restrict__ text, int64_t n, int64_t start, int64_t end,
-                                                        int32_t* __restrict__ meth, int32_t* __restrict__ cov, unsigned long long* bad,
-                                                        unsigned long long chunk_off)
+// The staging and line finding of a tile (k_pat_count, k_homog_count): tx[16 + WG_PAT_TILE + WG_PAT_OVER] (16-byte aligned) receives the
+// bytes, lstart[WG_PAT_TILE / 2 + 1] the tile-relative first bytes of the lines that begin in the tile; returns their number.  Every
+// thread of the workgroup calls it (it synchronises).
+__device__ __forceinline__ uint32_t wg_pat_tile_lines(const char* __restrict__ text, int64_t n, int64_t base, char* tx, uint16_t* lstart,
+                                                      uint32_t* wtot)
 {
     static_assert(WG_PAT_TILE == 16 * WG_BLOCK && WG_PAT_OVER % 16 == 0 && WG_PAT_OVER / 16 <= WG_BLOCK, "16 bytes per thread");
-    __shared__ __attribute__((aligned(16))) char tx[16 + WG_PAT_TILE + WG_PAT_OVER];     // tx[15] = the byte before the tile; the tile from tx[16]
-    __shared__ uint16_t lstart[WG_PAT_TILE / 2 + 1];         // tile-relative first bytes of the lines that begin in the tile (at most every other byte)
-    __shared__ uint32_t wtot[WG_BLOCK / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t base = (int64_t)blockIdx.x * WG_PAT_TILE;
     // ---- stage: 16 bytes per thread (the chunk's buffer is 16-byte aligned and so is base), bytes at or past n as '\n'
     auto stage16 = [&](int64_t off) {                        // off: tile-relative, multiple of 16
         const int64_t a = base + off;
@@ -2817,36 +2815,57 @@ __global__ __launch_bounds__(WG_BLOCK) void k_pat_count(const char* __restrict__
         lstart[before++] = (uint16_t)(tid * 16 + j);
     }
     __syncthreads();
+    return total;
+}
+
+// The four fields of the pat line that begins at byte p: site, the pattern's first byte ps and length plen, count; false when the line
+// has fewer than four fields or its site / count is not a number (what makes the reference's std::stoi throw).
+__device__ __forceinline__ bool wg_pat_parse_line(const PatText& T, int64_t p, int64_t n, int64_t& site, int64_t& ps, int64_t& plen, int64_t& count)
+{
+    int64_t i = p;
+    char ch = 0;
+    bool ok = true;
+    while (i < n && (ch = T.at(i)) != '\t' && ch != '\n') i++;   // field 1: chromosome
+    ok = i < n && ch == '\t';
+    if (ok) {
+        i++;
+        ok = wg_parse_int(T, i, n, site);                           // field 2: index of the read's first CpG
+    }
+    if (ok) {
+        while (i < n && (ch = T.at(i)) != '\t' && ch != '\n') i++;
+        ok = i < n && ch == '\t';
+    }
+    if (ok) {
+        i++;
+        ps = i;                                                     // field 3: the pattern
+        while (i < n && (ch = T.at(i)) != '\t' && ch != '\n') i++;
+        ok = i < n && ch == '\t';
+        plen = i - ps;
+    }
+    if (ok) {
+        i++;
+        ok = i < n && T.at(i) != '\n' && wg_parse_int(T, i, n, count);   // field 4: how many reads (an empty one: stoi throws)
+    }
+    return ok;
+}
+
+__global__ __launch_bounds__(WG_BLOCK) void k_pat_count(const char* __restrict__ text, int64_t n, int64_t start, int64_t end,
+                                                        int32_t* __restrict__ meth, int32_t* __restrict__ cov, unsigned long long* bad,
+                                                        unsigned long long chunk_off)
+{
+    __shared__ __attribute__((aligned(16))) char tx[16 + WG_PAT_TILE + WG_PAT_OVER];     // tx[15] = the byte before the tile; the tile from tx[16]
+    __shared__ uint16_t lstart[WG_PAT_TILE / 2 + 1];         // tile-relative first bytes of the lines that begin in the tile (at most every other byte)
+    __shared__ uint32_t wtot[WG_BLOCK / 64];
+    const int tid = threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * WG_PAT_TILE;
+    const uint32_t total = wg_pat_tile_lines(text, n, base, tx, lstart, wtot);
     // ---- one line per thread
     const PatText T = {tx + 16, text, base, n};
     const int64_t nr = end - start;
     for (uint32_t l = (uint32_t)tid; l < total; l += WG_BLOCK) {
         const int64_t p = base + lstart[l];
-        int64_t i = p;
-        char ch = 0;
-        bool ok = true;
-        while (i < n && (ch = T.at(i)) != '\t' && ch != '\n') i++;   // field 1: chromosome
-        ok = i < n && ch == '\t';
         int64_t site = 0, count = 0, ps = 0, plen = 0;
-        if (ok) {
-            i++;
-            ok = wg_parse_int(T, i, n, site);                           // field 2: index of the read's first CpG
-        }
-        if (ok) {
-            while (i < n && (ch = T.at(i)) != '\t' && ch != '\n') i++;
-            ok = i < n && ch == '\t';
-        }
-        if (ok) {
-            i++;
-            ps = i;                                                     // field 3: the pattern
-            while (i < n && (ch = T.at(i)) != '\t' && ch != '\n') i++;
-            ok = i < n && ch == '\t';
-            plen = i - ps;
-        }
-        if (ok) {
-            i++;
-            ok = i < n && T.at(i) != '\n' && wg_parse_int(T, i, n, count);   // field 4: how many reads (an empty one: stoi throws)
-        }
+        const bool ok = wg_pat_parse_line(T, p, n, site, ps, plen, count);
         if (!ok) { atomicMin(bad, chunk_off + (unsigned long long)p); continue; }
         if (site + plen - 1 < start || site >= end) continue;           // stdin2beta.cpp:75-78
         for (int64_t k = 0; k < plen; k++) {

@@ -28,6 +28,7 @@
 
 #include "../../include/wgbsseg.h"
 #include "seg_kernels.h"
+#include "homog_kernels.h"
 #include "plain_dp.h"
 #include "stitch.h"
 #include "add_loci.h"
@@ -2831,6 +2832,186 @@ double wgbsseg_patbeta_kernel_ms(wgbsseg_patbeta* p)
     if (hipSetDevice(p->device) != hipSuccess || hipStreamSynchronize(p->st) != hipSuccess) return -1.0;
     p->collect(0); p->collect(1);
     return p->kernel_ms;
+}
+
+}  // extern "C"
+
+// `wgbstools homog` accumulator: (block, bin) read counts on one device; text chunks through two page-locked staging buffers as
+// for wgbsseg_patbeta (the caller inflates chunk k+1 while chunk k is copied and counted).
+struct wgbsseg_homog {
+    int device = 0;
+    hipStream_t st = nullptr;
+    int64_t n_blocks = 0, last_end = 0;
+    int n_bins = 0, min_cpgs = 0, inclusive = 0;
+    DevBuf bstart, bend, bpmax, range, counts, text[2], bad, desc, prev;
+    PinnedBuf stage[2];
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool busy[2] = {false, false};
+    int k = 0;
+    unsigned long long fed = 0, chunks = 0;
+    double kernel_ms = 0.0;
+    hipEvent_t k0[2] = {nullptr, nullptr}, k1[2] = {nullptr, nullptr};
+    bool timed[2] = {false, false};
+    void collect(int k)
+    {
+        float ms = 0.f;
+        if (timed[k] && hipEventElapsedTime(&ms, k0[k], k1[k]) == hipSuccess) kernel_ms += (double)ms;
+        timed[k] = false;
+    }
+};
+
+extern "C" {
+
+void wgbsseg_homog_destroy(wgbsseg_homog* h);
+
+int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, const float* range, int32_t n_bins,
+                         int32_t min_cpgs, int32_t inclusive, wgbsseg_homog** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    if (n_blocks < 1 || !start_cpg || !end_cpg) { set_err(err, errlen, "homog: no blocks"); return WGBSSEG_E_ARG; }
+    if (!range || n_bins < 1 || n_bins > WG_HOMOG_MAX_BINS) { set_err(err, errlen, "homog: %d bins (1..%d)", (int)n_bins, WG_HOMOG_MAX_BINS); return WGBSSEG_E_ARG; }
+    for (int b = 0; b < n_bins; b++)
+        if (!(range[b] < range[b + 1])) { set_err(err, errlen, "homog: the range is not ascending"); return WGBSSEG_E_ARG; }
+    if (min_cpgs < 1) { set_err(err, errlen, "homog: min_cpgs %d < 1", (int)min_cpgs); return WGBSSEG_E_ARG; }
+    std::vector<int32_t> s32((size_t)n_blocks), e32((size_t)n_blocks), pm((size_t)n_blocks);
+    int32_t run = 0;
+    for (int64_t j = 0; j < n_blocks; j++) {
+        const int64_t a = start_cpg[j], b = end_cpg[j];
+        if (a < 1) { set_err(err, errlen, "homog: block %lld (in sorted order) has startCpG %lld < 1", (long long)j, (long long)a); return WGBSSEG_E_ARG; }
+        if (b <= a || b > 0x7fffffffLL) { set_err(err, errlen, "homog: block %lld (in sorted order) has endCpG %lld (startCpG %lld)", (long long)j, (long long)b, (long long)a); return WGBSSEG_E_ARG; }
+        if (j && (a < start_cpg[j - 1] || (a == start_cpg[j - 1] && b < end_cpg[j - 1]))) {
+            set_err(err, errlen, "homog: blocks must be given sorted by (startCpG, endCpG) (block %lld)", (long long)j); return WGBSSEG_E_ARG;
+        }
+        s32[(size_t)j] = (int32_t)a; e32[(size_t)j] = (int32_t)b;
+        run = std::max(run, (int32_t)b);
+        pm[(size_t)j] = run;
+    }
+    wgbsseg_ctx* probe = nullptr;                                 // device checks (gfx950, index) as for a segment context
+    int rc = wgbsseg_create(device, &probe, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    wgbsseg_destroy(probe);
+    struct Free { void operator()(wgbsseg_homog* q) const { wgbsseg_homog_destroy(q); } };
+    std::unique_ptr<wgbsseg_homog, Free> h(new (std::nothrow) wgbsseg_homog());
+    if (!h) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    h->device = device; h->n_blocks = n_blocks; h->last_end = end_cpg[n_blocks - 1];
+    h->n_bins = n_bins; h->min_cpgs = min_cpgs; h->inclusive = inclusive ? 1 : 0;
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
+    for (auto& e : h->ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (int q = 0; q < 2; q++) { HIP_TRY(hipEventCreate(&h->k0[q])); HIP_TRY(hipEventCreate(&h->k1[q])); }
+    const size_t nb4 = (size_t)n_blocks * 4, cb = (size_t)n_blocks * (size_t)n_bins * 4;
+    HIP_TRY(h->bstart.ensure(nb4)); HIP_TRY(h->bend.ensure(nb4)); HIP_TRY(h->bpmax.ensure(nb4));
+    HIP_TRY(h->range.ensure(sizeof(float) * (size_t)(n_bins + 1))); HIP_TRY(h->counts.ensure(cb));
+    HIP_TRY(h->bad.ensure(8)); HIP_TRY(h->desc.ensure(8)); HIP_TRY(h->prev.ensure(16));
+    HIP_TRY(hipMemcpy(h->bstart.p, s32.data(), nb4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->bend.p, e32.data(), nb4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->bpmax.p, pm.data(), nb4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->range.p, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice));
+    const long long none[2] = {WG_HOMOG_NO_SITE, WG_HOMOG_NO_SITE};
+    HIP_TRY(hipMemcpy(h->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(h->counts.p, 0, cb, h->st));
+    HIP_TRY(hipMemsetAsync(h->bad.p, 0xff, 8, h->st));
+    HIP_TRY(hipMemsetAsync(h->desc.p, 0xff, 8, h->st));
+    *out = h.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_homog_destroy(wgbsseg_homog* h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->st) { (void)hipStreamSynchronize(h->st); }
+    for (DevBuf* b : {&h->bstart, &h->bend, &h->bpmax, &h->range, &h->counts, &h->text[0], &h->text[1], &h->bad, &h->desc, &h->prev}) b->release();
+    for (auto& s : h->stage) s.release();
+    for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
+    for (int q = 0; q < 2; q++) { if (h->k0[q]) (void)hipEventDestroy(h->k0[q]); if (h->k1[q]) (void)hipEventDestroy(h->k1[q]); }
+    if (h->st) (void)hipStreamDestroy(h->st);
+    delete h;
+}
+
+int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    if (!h || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to homog_feed"); return WGBSSEG_E_ARG; }
+    if (n_bytes == 0) return WGBSSEG_OK;
+    if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "homog_feed: a chunk must end with a complete line"); return WGBSSEG_E_ARG; }
+    const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;     // one workgroup per tile of text
+    if (gx > 0x7fffffff) { set_err(err, errlen, "homog_feed: chunk too large"); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(h->device));
+    const int k = h->k;
+    if (h->busy[k]) { HIP_TRY(hipEventSynchronize(h->ev[k])); h->collect(k); }      // its previous chunk has been consumed
+    if (!h->stage[k].ensure((size_t)n_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    HIP_TRY(h->text[k].ensure((size_t)n_bytes));
+    memcpy(h->stage[k].p, text, (size_t)n_bytes);
+    HIP_TRY(hipMemcpyAsync(h->text[k].p, h->stage[k].p, (size_t)n_bytes, hipMemcpyHostToDevice, h->st));
+    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
+    long long* prev = h->prev.as<long long>();
+    const int out_slot = (int)(h->chunks & 1), in_slot = out_slot ^ 1;
+    HIP_TRY(hipMemcpyAsync(prev + out_slot, prev + in_slot, 8, hipMemcpyDeviceToDevice, h->st));
+    HIP_TRY(hipEventRecord(h->k0[k], h->st));
+    hipLaunchKernelGGL(k_homog_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, h->st, h->text[k].as<char>(), n_bytes,
+                       h->bstart.as<int32_t>(), h->bend.as<int32_t>(), h->bpmax.as<int32_t>(), h->n_blocks, h->last_end,
+                       h->range.as<float>(), h->n_bins, h->min_cpgs, h->inclusive, h->counts.as<int32_t>(),
+                       h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), prev + in_slot, prev + out_slot, h->fed);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(h->k1[k], h->st));
+    h->timed[k] = true;
+    HIP_TRY(hipEventRecord(h->ev[k], h->st));
+    h->busy[k] = true;
+    h->k ^= 1;
+    h->fed += (unsigned long long)n_bytes;
+    h->chunks += 1;
+    return WGBSSEG_OK;
+}
+
+int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t errlen)
+{
+    if (!h || !counts) { set_err(err, errlen, "bad arguments to homog_finish"); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(h->device));
+    unsigned long long bad = 0, desc = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipMemcpyAsync(&desc, h->desc.p, 8, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+    if (bad != ~0ULL) {
+        set_err(err, errlen, "failed calculating homog: invalid line at byte offset %llu of the input (too few columns, or a site / count that is not a number)", bad);
+        return WGBSSEG_E_ARG;
+    }
+    if (desc != ~0ULL) {
+        set_err(err, errlen, "failed calculating homog: the pat file is not sorted: the read at byte offset %llu of the input starts before the read before it", desc);
+        return WGBSSEG_E_ARG;
+    }
+    HIP_TRY(hipMemcpyAsync(counts, h->counts.p, (size_t)h->n_blocks * (size_t)h->n_bins * 4, hipMemcpyDeviceToHost, h->st));
+    HIP_TRY(hipStreamSynchronize(h->st));
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_homog_kernel_ms(wgbsseg_homog* h)
+{
+    if (!h) return -1.0;
+    if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess) return -1.0;
+    h->collect(0); h->collect(1);
+    return h->kernel_ms;
+}
+
+int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_total, int8_t* out)
+{
+    if (!range || !out || n_bins < 1 || n_bins > WG_HOMOG_MAX_BINS || max_total < 0 || max_total > 65535) return WGBSSEG_E_ARG;
+    char err[256];
+    const size_t errlen = sizeof(err);
+    const int64_t n = (int64_t)(max_total + 1) * (max_total + 2) / 2;
+    float* d_range = nullptr;
+    int8_t* d_out = nullptr;
+    HIP_TRY(hipMalloc(&d_range, sizeof(float) * (size_t)(n_bins + 1)));
+    if (hipMalloc(&d_out, (size_t)n) != hipSuccess) { (void)hipFree(d_range); return WGBSSEG_E_HIP; }
+    hipError_t e = hipMemcpy(d_range, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_homog_bins, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, 0, d_range, (int)n_bins, (int)max_total, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n, hipMemcpyDeviceToHost);
+    (void)hipFree(d_range);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? WGBSSEG_OK : WGBSSEG_E_HIP;
 }
 
 int wgbsseg_get_timings(const wgbsseg_ctx* c, wgbsseg_timings* out)
