@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 230            /* 0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 240            /* 0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -438,6 +438,29 @@ int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t er
 void wgbsseg_homog_destroy(wgbsseg_homog* h);
 double wgbsseg_homog_kernel_ms(wgbsseg_homog* h);
 int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_total, int8_t* out);
+
+/*
+ * pat -> per-block two-allele EM test (`wgbstools test_bimodal`: test_bimodal.py:25-176 asks tabix for the reads of each block
+ * and runs numpy's EM over them).  create(): the blocks [start_cpg[j], end_cpg[j]) in any order (1 <= startCpG < endCpG < 2^31),
+ * strict (--strict: clip the reads to the block), min_len (>= 1), max_lds_cols (< 0: the default; 0 forces every block onto the
+ * global-memory path: a test hook).  feed(): a chunk of pat TEXT made of whole lines, as for wgbsseg_homog_feed; it first waits for
+ * the previous chunk's parse, runs the EM of the blocks that chunk completed (queued: it overlaps the caller's next inflate) and
+ * drops the reads no pending block can reach.  A block uses the reads starting in [max(1, s1 - 150), s2 - 1] (s1 = startCpG,
+ * s2 = endCpG), skips those ending at or before s1, clips them with strict, drops those shorter than min_len; each line stands for
+ * `count` identical rows; only C and T are observations.  finish(): per block in the order given, ll[3 j ..] = {ll0 (one allele),
+ * ll_em (the EM's last likelihood), the sum of the columns' 2e-3 + #C + #T}, counts[3 j ..] = {columns, rows, EM iterations}
+ * (rows 0: nothing computed, the reference's p = 1).  The sums are taken in the reference's order: see bimodal_kernels.h.
+ * finish() returns WGBSSEG_E_ARG naming the byte offset of the first malformed line, else of the first negative count, else of
+ * the first read that starts before the read before it; WGBSSEG_E_CAPACITY for a block of 2^31 rows or more.
+ * wgbsseg_bimodal_kernel_ms: device time (HIP events) of all launches so far; waits for them.
+ */
+typedef struct wgbsseg_bimodal wgbsseg_bimodal;
+int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, int32_t strict, int32_t min_len,
+                           int32_t max_lds_cols, wgbsseg_bimodal** out, char* err, size_t errlen);
+int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, char* err, size_t errlen);
+int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char* err, size_t errlen);
+void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b);
+double wgbsseg_bimodal_kernel_ms(wgbsseg_bimodal* b);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

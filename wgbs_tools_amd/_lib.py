@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 230          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 240          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -38,7 +38,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_format_fixed', 'wgbsseg_bed_parse', 'wgbsseg_bed_write_annotated', 'wgbsseg_debug_canonical_float',
            'wgbsseg_first_batch_items', 'wgbsseg_plan_shares_weighted',
            'wgbsseg_homog_create', 'wgbsseg_homog_feed', 'wgbsseg_homog_finish', 'wgbsseg_homog_destroy', 'wgbsseg_homog_kernel_ms',
-           'wgbsseg_debug_homog_bins']
+           'wgbsseg_debug_homog_bins',
+           'wgbsseg_bimodal_create', 'wgbsseg_bimodal_feed', 'wgbsseg_bimodal_finish', 'wgbsseg_bimodal_destroy', 'wgbsseg_bimodal_kernel_ms']
 
 
 class NativeLibraryError(RuntimeError):
@@ -223,6 +224,16 @@ def load():
     L.wgbsseg_homog_kernel_ms.argtypes = [vp]
     L.wgbsseg_debug_homog_bins.restype = i32
     L.wgbsseg_debug_homog_bins.argtypes = [vp, i32, i32, vp]
+    L.wgbsseg_bimodal_create.restype = i32
+    L.wgbsseg_bimodal_create.argtypes = [i32, vp, vp, i64, i32, i32, i32, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.wgbsseg_bimodal_feed.restype = i32
+    L.wgbsseg_bimodal_feed.argtypes = [vp, C.c_char_p, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_bimodal_finish.restype = i32
+    L.wgbsseg_bimodal_finish.argtypes = [vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_bimodal_destroy.restype = None
+    L.wgbsseg_bimodal_destroy.argtypes = [vp]
+    L.wgbsseg_bimodal_kernel_ms.restype = C.c_double
+    L.wgbsseg_bimodal_kernel_ms.argtypes = [vp]
     L.wgbsseg_marker_stats.restype = i32
     L.wgbsseg_marker_stats.argtypes = [vp, vp, i32, vp, i32, i64, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_add_loci.restype = i32
@@ -560,6 +571,48 @@ class Homog:
     def close(self):
         if self._h:
             self._L.wgbsseg_homog_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Bimodal:
+    """wgbsseg_bimodal: pat text -> per block [starts, ends) (any order) the two-allele EM test's raw numbers on one GPU.
+    finish() -> (float64 [n][3]: ll0, ll_em, sum of n_per_col; int64 [n][3]: columns, rows, EM iterations)."""
+
+    def __init__(self, starts, ends, strict=False, min_len=1, device=0, max_lds_cols=-1):
+        self._L = load()
+        self._h = C.c_void_p()
+        self._err = C.create_string_buffer(ERRLEN)
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(ends, dtype=np.int64)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError('starts / ends: one value per block')
+        self.n_blocks = int(s.size)
+        _check(self._L.wgbsseg_bimodal_create(int(device), s.ctypes.data, e.ctypes.data, s.size, 1 if strict else 0, int(min_len),
+                                              int(max_lds_cols), C.byref(self._h), self._err, ERRLEN), self._err)
+
+    def feed(self, text):
+        """text: bytes made of whole lines (must end with a newline)"""
+        _check(self._L.wgbsseg_bimodal_feed(self._h, text, len(text), self._err, ERRLEN), self._err)
+
+    def kernel_ms(self):
+        """device time of every launch so far (waits for them)"""
+        return float(self._L.wgbsseg_bimodal_kernel_ms(self._h))
+
+    def finish(self):
+        ll = np.empty((self.n_blocks, 3), dtype=np.float64)
+        cnt = np.empty((self.n_blocks, 3), dtype=np.int64)
+        _check(self._L.wgbsseg_bimodal_finish(self._h, ll.ctypes.data, cnt.ctypes.data, self._err, ERRLEN), self._err)
+        return ll, cnt
+
+    def close(self):
+        if self._h:
+            self._L.wgbsseg_bimodal_destroy(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):

@@ -29,6 +29,7 @@
 #include "../../include/wgbsseg.h"
 #include "seg_kernels.h"
 #include "homog_kernels.h"
+#include "bimodal_kernels.h"
 #include "plain_dp.h"
 #include "stitch.h"
 #include "add_loci.h"
@@ -3012,6 +3013,297 @@ int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_tot
     (void)hipFree(d_range);
     (void)hipFree(d_out);
     return e == hipSuccess ? WGBSSEG_OK : WGBSSEG_E_HIP;
+}
+
+}  // extern "C"
+
+// `wgbstools test_bimodal` accumulator on one device: the blocks, the read table of the live window (two copies: dropping moves
+// the live rows from one to the other), and the per-block results.  A feed() first waits for the work of the previous chunk
+// (the caller inflated this chunk meanwhile), retires the blocks that chunk completed, drops the reads no pending block can
+// reach, and queues the parse of this chunk; the EM of the retired blocks runs while the caller inflates the next one.
+struct wgbsseg_bimodal {
+    struct Table { DevBuf start, len, cnt, woff, words; };
+    int device = 0;
+    hipStream_t st = nullptr;
+    int64_t n_blocks = 0;
+    int strict = 0, min_len = 1, lds_cols = WG_BIM_LDS_COLS;
+    std::vector<int32_t> s1, s2, by_end;          // by_end: block indexes in (endCpG, file) order
+    std::vector<int64_t> lo_after;                // lo_after[p]: min over by_end[p..] of max(1, s1 - 150) (INT64_MAX past the end)
+    int64_t pending = 0;                          // by_end[pending..] have not been retired
+    DevBuf bs1, bs2, ids, meta, scr_off, scratch, res_f, res_i, state, text, tile_cnt, tile_base, pos;
+    Table tab[2];
+    int cur = 0;
+    size_t cap_rows = 0, cap_words = 0;
+    PinnedBuf stage, host_state, host_meta, host_off;
+    unsigned long long fed = 0;
+    bool stop = false;                            // an input error was seen: nothing more is computed
+    double kernel_ms = 0.0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans;     // device time of every queued piece of work
+    hipError_t span_begin(hipEvent_t* a)
+    {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        hipError_t e = hipEventCreate(&e0);
+        if (e == hipSuccess) e = hipEventCreate(&e1);
+        if (e != hipSuccess) { if (e0) (void)hipEventDestroy(e0); return e; }
+        spans.push_back({e0, e1});
+        *a = e1;
+        return hipEventRecord(e0, st);
+    }
+    void collect()
+    {
+        for (auto& s : spans) {
+            float ms = 0.f;
+            if (hipEventElapsedTime(&ms, s.first, s.second) == hipSuccess) kernel_ms += (double)ms;
+            (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second);
+        }
+        spans.clear();
+    }
+    wg_bim_state* hs() const { return reinterpret_cast<wg_bim_state*>(host_state.p); }
+};
+
+static int bim_sync_state(wgbsseg_bimodal* b, char* err, size_t errlen)
+{
+    HIP_TRY(hipMemcpyAsync(b->host_state.p, b->state.p, sizeof(wg_bim_state), hipMemcpyDeviceToHost, b->st));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    b->collect();
+    const wg_bim_state* s = b->hs();
+    if (s->bad != ~0ULL || s->neg != ~0ULL || s->desc != ~0ULL || s->em_cap) b->stop = true;
+    return WGBSSEG_OK;
+}
+
+// both tables hold at least `rows` reads and `words` words; the live rows of the current one are kept (the stream is idle)
+static int bim_reserve(wgbsseg_bimodal* b, size_t rows, size_t words, char* err, size_t errlen)
+{
+    if (rows <= b->cap_rows && words <= b->cap_words) return WGBSSEG_OK;
+    const size_t nr = std::max(rows, 2 * b->cap_rows), nw = std::max(words, 2 * b->cap_words);
+    const size_t R = (size_t)b->hs()->R, W = (size_t)b->hs()->W;
+    for (int t = 0; t < 2; t++) {
+        wgbsseg_bimodal::Table fresh;
+        HIP_TRY(fresh.start.ensure(nr * 4)); HIP_TRY(fresh.len.ensure(nr * 4)); HIP_TRY(fresh.cnt.ensure(nr * 4));
+        HIP_TRY(fresh.woff.ensure(nr * 8)); HIP_TRY(fresh.words.ensure(nw * 4));
+        wgbsseg_bimodal::Table& old = b->tab[t];
+        if (t == b->cur && R) {
+            HIP_TRY(hipMemcpy(fresh.start.p, old.start.p, R * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(fresh.len.p, old.len.p, R * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(fresh.cnt.p, old.cnt.p, R * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(fresh.woff.p, old.woff.p, R * 8, hipMemcpyDeviceToDevice));
+        }
+        if (t == b->cur && W) HIP_TRY(hipMemcpy(fresh.words.p, old.words.p, W * 4, hipMemcpyDeviceToDevice));
+        for (DevBuf* d : {&old.start, &old.len, &old.cnt, &old.woff, &old.words}) d->release();
+        old = fresh;
+        fresh = wgbsseg_bimodal::Table();                       // (ownership moved: nothing to free twice)
+    }
+    b->cap_rows = nr; b->cap_words = nw;
+    return WGBSSEG_OK;
+}
+
+// the EM of by_end[pending .. p1): their rows and columns, scratch for the wide ones, then k_bim_em (queued, not waited for)
+static int bim_retire(wgbsseg_bimodal* b, int64_t p1, char* err, size_t errlen)
+{
+    const int64_t n = p1 - b->pending;
+    if (n <= 0 || b->stop) return WGBSSEG_OK;
+    wgbsseg_bimodal::Table& T = b->tab[b->cur];
+    HIP_TRY(hipMemcpyAsync(b->ids.as<int32_t>(), b->by_end.data() + b->pending, (size_t)n * 4, hipMemcpyHostToDevice, b->st));
+    hipEvent_t e1 = nullptr;
+    HIP_TRY(b->span_begin(&e1));
+    hipLaunchKernelGGL(k_bim_gather, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
+                       b->state.as<wg_bim_state>(), b->bs1.as<int32_t>(), b->bs2.as<int32_t>(), b->ids.as<int32_t>(), b->strict, b->min_len,
+                       b->meta.as<wg_bim_meta>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, b->st));
+    if (!b->host_meta.ensure((size_t)n * sizeof(wg_bim_meta))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    HIP_TRY(hipMemcpyAsync(b->host_meta.p, b->meta.p, (size_t)n * sizeof(wg_bim_meta), hipMemcpyDeviceToHost, b->st));
+    HIP_TRY(hipStreamSynchronize(b->st));
+    const wg_bim_meta* m = reinterpret_cast<const wg_bim_meta*>(b->host_meta.p);
+    if (!b->host_off.ensure((size_t)n * 8)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    long long* off = reinterpret_cast<long long*>(b->host_off.p);     // (read by the copy below after this returns: the next use waits for the stream)
+    size_t used = 0;
+    for (int64_t g = 0; g < n; g++) {
+        if (m[g].rows > 0x7fffffffLL) {
+            set_err(err, errlen, "test_bimodal: block %lld (row %d of the blocks) has %lld rows: more than 2^31 - 1", (long long)g,
+                    (int)b->by_end[(size_t)(b->pending + g)] + 1, m[g].rows);
+            return WGBSSEG_E_CAPACITY;
+        }
+        off[g] = 0;
+        if (m[g].rows > 0 && m[g].ncols > b->lds_cols) { off[g] = (long long)used; used += (size_t)m[g].ncols * 48; }
+    }
+    if (used) HIP_TRY(b->scratch.ensure(used));
+    HIP_TRY(hipMemcpyAsync(b->scr_off.p, off, (size_t)n * 8, hipMemcpyHostToDevice, b->st));
+    HIP_TRY(b->span_begin(&e1));
+    hipLaunchKernelGGL(k_bim_em, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
+                       T.woff.as<long long>(), T.words.as<uint32_t>(), b->bs1.as<int32_t>(), b->bs2.as<int32_t>(), b->ids.as<int32_t>(),
+                       b->meta.as<wg_bim_meta>(), b->scr_off.as<long long>(), b->scratch.as<unsigned char>(), b->lds_cols, b->strict, b->min_len,
+                       b->res_f.as<double>(), b->res_i.as<long long>(), b->state.as<wg_bim_state>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, b->st));
+    b->pending = p1;
+    return WGBSSEG_OK;
+}
+
+extern "C" {
+
+void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b);
+
+int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, int32_t strict, int32_t min_len,
+                           int32_t max_lds_cols, wgbsseg_bimodal** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    if (n_blocks < 1 || n_blocks > 0x7fffffffLL || !start_cpg || !end_cpg) { set_err(err, errlen, "test_bimodal: no blocks"); return WGBSSEG_E_ARG; }
+    if (min_len < 1) { set_err(err, errlen, "test_bimodal: min_len %d < 1", (int)min_len); return WGBSSEG_E_ARG; }
+    for (int64_t j = 0; j < n_blocks; j++) {
+        const int64_t a = start_cpg[j], e = end_cpg[j];
+        if (a < 1 || e <= a || e > 0x7fffffffLL) {
+            set_err(err, errlen, "test_bimodal: block %lld has startCpG %lld, endCpG %lld (1 <= startCpG < endCpG < 2^31)", (long long)j + 1, (long long)a, (long long)e);
+            return WGBSSEG_E_ARG;
+        }
+    }
+    wgbsseg_ctx* probe = nullptr;                                 // device checks (gfx950, index) as for a segment context
+    int rc = wgbsseg_create(device, &probe, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    wgbsseg_destroy(probe);
+    struct Free { void operator()(wgbsseg_bimodal* q) const { wgbsseg_bimodal_destroy(q); } };
+    std::unique_ptr<wgbsseg_bimodal, Free> b(new (std::nothrow) wgbsseg_bimodal());
+    if (!b) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    b->device = device; b->n_blocks = n_blocks; b->strict = strict ? 1 : 0; b->min_len = min_len;
+    b->lds_cols = max_lds_cols < 0 ? WG_BIM_LDS_COLS : std::min<int32_t>(max_lds_cols, WG_BIM_LDS_COLS);
+    const size_t nb = (size_t)n_blocks;
+    b->s1.resize(nb); b->s2.resize(nb); b->by_end.resize(nb); b->lo_after.assign(nb + 1, INT64_MAX);
+    for (size_t j = 0; j < nb; j++) { b->s1[j] = (int32_t)start_cpg[j]; b->s2[j] = (int32_t)end_cpg[j]; b->by_end[j] = (int32_t)j; }
+    std::stable_sort(b->by_end.begin(), b->by_end.end(), [&](int32_t x, int32_t y) { return b->s2[(size_t)x] < b->s2[(size_t)y]; });
+    for (size_t p = nb; p-- > 0;) b->lo_after[p] = std::min<int64_t>(b->lo_after[p + 1], std::max<int64_t>(1, (int64_t)b->s1[(size_t)b->by_end[p]] - WG_BIM_CTX));
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
+    HIP_TRY(b->bs1.ensure(nb * 4)); HIP_TRY(b->bs2.ensure(nb * 4)); HIP_TRY(b->ids.ensure(nb * 4));
+    HIP_TRY(b->meta.ensure(nb * sizeof(wg_bim_meta))); HIP_TRY(b->scr_off.ensure(nb * 8));
+    HIP_TRY(b->res_f.ensure(nb * 24)); HIP_TRY(b->res_i.ensure(nb * 24)); HIP_TRY(b->state.ensure(sizeof(wg_bim_state)));
+    HIP_TRY(hipMemcpy(b->bs1.p, b->s1.data(), nb * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->bs2.p, b->s2.data(), nb * 4, hipMemcpyHostToDevice));
+    if (!b->host_state.ensure(sizeof(wg_bim_state))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    wg_bim_state s0;
+    s0.R = s0.W = s0.R0 = 0; s0.last_start = WG_BIM_NONE; s0.head = s0.whead = 0;
+    s0.bad = s0.neg = s0.desc = ~0ULL; s0.em_cap = 0;
+    *b->hs() = s0;
+    HIP_TRY(hipMemcpy(b->state.p, &s0, sizeof(s0), hipMemcpyHostToDevice));
+    *out = b.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->st) (void)hipStreamSynchronize(b->st);
+    b->collect();
+    for (DevBuf* d : {&b->bs1, &b->bs2, &b->ids, &b->meta, &b->scr_off, &b->scratch, &b->res_f, &b->res_i, &b->state, &b->text, &b->tile_cnt,
+                      &b->tile_base, &b->pos}) d->release();
+    for (auto& t : b->tab) for (DevBuf* d : {&t.start, &t.len, &t.cnt, &t.woff, &t.words}) d->release();
+    b->stage.release(); b->host_state.release(); b->host_meta.release(); b->host_off.release();
+    if (b->st) (void)hipStreamDestroy(b->st);
+    delete b;
+}
+
+int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    if (!b || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to bimodal_feed"); return WGBSSEG_E_ARG; }
+    if (n_bytes == 0) return WGBSSEG_OK;
+    if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "bimodal_feed: a chunk must end with a complete line"); return WGBSSEG_E_ARG; }
+    const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;
+    if (gx > 0x7fffffff) { set_err(err, errlen, "bimodal_feed: chunk too large"); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    int rc = bim_sync_state(b, err, errlen);                     // the previous chunk is parsed and checked
+    if (rc != WGBSSEG_OK) return rc;
+    if (b->stop) { b->fed += (unsigned long long)n_bytes; return WGBSSEG_OK; }     // finish() reports the error
+    const wg_bim_state s = *b->hs();
+    const size_t ub_lines = (size_t)n_bytes / 6 + 1, ub_words = (size_t)n_bytes / 16 + ub_lines + 1;   // a good line has >= 6 bytes
+    rc = bim_reserve(b, (size_t)s.R + ub_lines, (size_t)s.W + ub_words, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    // blocks whose reads have all been seen: a read starting at or after endCpG has come
+    int64_t p1 = b->pending;
+    if (s.last_start != WG_BIM_NONE)
+        while (p1 < b->n_blocks && (long long)b->s2[(size_t)b->by_end[(size_t)p1]] <= s.last_start) p1++;
+    rc = bim_retire(b, p1, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    // drop what no pending block can reach, into the other table
+    hipEvent_t e1 = nullptr;
+    if (s.R > 0) {
+        wgbsseg_bimodal::Table &A = b->tab[b->cur], &B = b->tab[b->cur ^ 1];
+        const long long lo = b->lo_after[(size_t)b->pending] == INT64_MAX ? (long long)INT32_MAX + 1 : (long long)b->lo_after[(size_t)b->pending];
+        HIP_TRY(b->span_begin(&e1));
+        hipLaunchKernelGGL(k_bim_drop_find, dim3(1), dim3(1), 0, b->st, A.start.as<int32_t>(), A.woff.as<long long>(), b->state.as<wg_bim_state>(), lo);
+        const long long big = std::max<long long>(s.R, s.W);
+        hipLaunchKernelGGL(k_bim_drop_copy, dim3((unsigned)((big + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, b->st,
+                           A.start.as<int32_t>(), A.len.as<int32_t>(), A.cnt.as<int32_t>(), A.woff.as<long long>(), A.words.as<uint32_t>(),
+                           B.start.as<int32_t>(), B.len.as<int32_t>(), B.cnt.as<int32_t>(), B.woff.as<long long>(), B.words.as<uint32_t>(),
+                           b->state.as<wg_bim_state>(), (long long)s.R, (long long)s.W);
+        hipLaunchKernelGGL(k_bim_drop_done, dim3(1), dim3(1), 0, b->st, b->state.as<wg_bim_state>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(e1, b->st));
+        b->cur ^= 1;
+    }
+    // this chunk: copy, count, scan, fill, order
+    if (!b->stage.ensure((size_t)n_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    memcpy(b->stage.p, text, (size_t)n_bytes);
+    HIP_TRY(b->text.ensure((size_t)n_bytes));
+    HIP_TRY(b->tile_cnt.ensure((size_t)gx * 8)); HIP_TRY(b->tile_base.ensure((size_t)gx * 16)); HIP_TRY(b->pos.ensure(ub_lines * 8));
+    HIP_TRY(hipMemcpyAsync(b->text.p, b->stage.p, (size_t)n_bytes, hipMemcpyHostToDevice, b->st));
+    wgbsseg_bimodal::Table& T = b->tab[b->cur];
+    HIP_TRY(b->span_begin(&e1));
+    hipLaunchKernelGGL(k_bim_tile_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, b->st, b->text.as<char>(), n_bytes, b->tile_cnt.as<uint32_t>(),
+                       b->state.as<wg_bim_state>(), b->fed);
+    hipLaunchKernelGGL(k_bim_tile_scan, dim3(1), dim3(WG_BLOCK), 0, b->st, b->tile_cnt.as<uint32_t>(), gx, b->tile_base.as<long long>(),
+                       b->state.as<wg_bim_state>());
+    hipLaunchKernelGGL(k_bim_fill, dim3((unsigned)gx), dim3(WG_BLOCK), 0, b->st, b->text.as<char>(), n_bytes, b->tile_base.as<long long>(),
+                       T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(), T.woff.as<long long>(), T.words.as<uint32_t>(),
+                       b->pos.as<long long>(), b->state.as<wg_bim_state>(), b->fed);
+    hipLaunchKernelGGL(k_bim_order, dim3((unsigned)((ub_lines + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, b->st, T.start.as<int32_t>(),
+                       b->pos.as<long long>(), b->state.as<wg_bim_state>(), s.last_start, (int64_t)ub_lines);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1, b->st));
+    b->fed += (unsigned long long)n_bytes;
+    return WGBSSEG_OK;
+}
+
+int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char* err, size_t errlen)
+{
+    if (!b || !ll || !counts) { set_err(err, errlen, "bad arguments to bimodal_finish"); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    int rc = bim_sync_state(b, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (!b->stop) {
+        rc = bim_retire(b, b->n_blocks, err, errlen);             // every read has been seen
+        if (rc != WGBSSEG_OK) return rc;
+        rc = bim_sync_state(b, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+    }
+    const wg_bim_state* s = b->hs();
+    if (s->bad != ~0ULL) {
+        set_err(err, errlen, "test_bimodal: invalid line at byte offset %llu of the input (too few columns, or a site / count that is not a number)", s->bad);
+        return WGBSSEG_E_ARG;
+    }
+    if (s->neg != ~0ULL) {
+        set_err(err, errlen, "test_bimodal: negative read count at byte offset %llu of the input", s->neg);
+        return WGBSSEG_E_ARG;
+    }
+    if (s->desc != ~0ULL) {
+        set_err(err, errlen, "test_bimodal: the pat file is not sorted: the read at byte offset %llu of the input starts before the read before it", s->desc);
+        return WGBSSEG_E_ARG;
+    }
+    if (s->em_cap) {
+        set_err(err, errlen, "test_bimodal: the EM of block %llu (row of the blocks) did not settle within %d iterations", s->em_cap, WG_BIM_MAX_ITERS);
+        return WGBSSEG_E_CAPACITY;
+    }
+    HIP_TRY(hipMemcpy(ll, b->res_f.p, (size_t)b->n_blocks * 24, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, b->res_i.p, (size_t)b->n_blocks * 24, hipMemcpyDeviceToHost));
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_bimodal_kernel_ms(wgbsseg_bimodal* b)
+{
+    if (!b) return -1.0;
+    if (hipSetDevice(b->device) != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess) return -1.0;
+    b->collect();
+    return b->kernel_ms;
 }
 
 int wgbsseg_get_timings(const wgbsseg_ctx* c, wgbsseg_timings* out)
