@@ -504,32 +504,31 @@ class Segmenter:
         return (f, d, g) if want_fast else (f, d)
 
 
-class PatBeta:
-    """wgbsseg_patbeta: pat text -> (#meth, #cov) rows of the CpGs [start_cpg, end_cpg) on one GPU."""
+class _PatFeed:
+    """The handle of one wgbsseg_<_abi>_* engine that pat text is fed to: feed, kernel_ms, close and context management."""
+    _abi = None
 
-    def __init__(self, start_cpg, end_cpg, device=0):
+    def __init__(self):
         self._L = load()
         self._h = C.c_void_p()
         self._err = C.create_string_buffer(ERRLEN)
-        self.n = int(end_cpg) - int(start_cpg)
-        _check(self._L.wgbsseg_patbeta_create(int(device), int(start_cpg), int(end_cpg), C.byref(self._h), self._err, ERRLEN), self._err)
+
+    def _call(self, name, *args):
+        """wgbsseg_<_abi>_<name>(*args, err, errlen), checked"""
+        _check(getattr(self._L, 'wgbsseg_%s_%s' % (self._abi, name))(*args, self._err, ERRLEN), self._err)
 
     def feed(self, text):
         """text: bytes made of whole lines (must end with a newline)"""
-        _check(self._L.wgbsseg_patbeta_feed(self._h, text, len(text), self._err, ERRLEN), self._err)
+        self._call('feed', self._h, text, len(text))
 
     def kernel_ms(self):
-        """device time of the counting kernel over every chunk fed so far (waits for them)"""
-        return float(self._L.wgbsseg_patbeta_kernel_ms(self._h))
-
-    def finish(self, lbeta=False):
-        out = np.empty((self.n, 2), dtype=np.uint16 if lbeta else np.uint8)
-        _check(self._L.wgbsseg_patbeta_finish(self._h, 1 if lbeta else 0, out.ctypes.data, self._err, ERRLEN), self._err)
-        return out
+        """device time of the timed launches over every chunk fed so far (waits for them): the counting kernel of PatBeta and
+        Homog, every launch of Bimodal"""
+        return float(getattr(self._L, 'wgbsseg_%s_kernel_ms' % self._abi)(self._h))
 
     def close(self):
         if self._h:
-            self._L.wgbsseg_patbeta_destroy(self._h)
+            getattr(self._L, 'wgbsseg_%s_destroy' % self._abi)(self._h)
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -539,87 +538,62 @@ class PatBeta:
         self.close()
 
 
-class Homog:
+class PatBeta(_PatFeed):
+    """wgbsseg_patbeta: pat text -> (#meth, #cov) rows of the CpGs [start_cpg, end_cpg) on one GPU."""
+    _abi = 'patbeta'
+
+    def __init__(self, start_cpg, end_cpg, device=0):
+        super().__init__()
+        self.n = int(end_cpg) - int(start_cpg)
+        self._call('create', int(device), int(start_cpg), int(end_cpg), C.byref(self._h))
+
+    def finish(self, lbeta=False):
+        out = np.empty((self.n, 2), dtype=np.uint16 if lbeta else np.uint8)
+        self._call('finish', self._h, 1 if lbeta else 0, out.ctypes.data)
+        return out
+
+
+class Homog(_PatFeed):
     """wgbsseg_homog: pat text -> int32 counts[n_blocks][n_bins] of the blocks [starts, ends) (sorted by (start, end)) on one GPU."""
+    _abi = 'homog'
 
     def __init__(self, starts, ends, edges, min_cpgs, inclusive=False, device=0):
-        self._L = load()
-        self._h = C.c_void_p()
-        self._err = C.create_string_buffer(ERRLEN)
+        super().__init__()
         s = np.ascontiguousarray(starts, dtype=np.int64)
         e = np.ascontiguousarray(ends, dtype=np.int64)
         r = np.ascontiguousarray(edges, dtype=np.float32)
         if s.shape != e.shape or s.ndim != 1 or r.ndim != 1 or r.size < 2:
             raise ValueError('starts / ends: one value per block; edges: n_bins + 1 values')
         self.n_blocks, self.n_bins = int(s.size), int(r.size) - 1
-        _check(self._L.wgbsseg_homog_create(int(device), s.ctypes.data, e.ctypes.data, s.size, r.ctypes.data, self.n_bins, int(min_cpgs),
-                                            1 if inclusive else 0, C.byref(self._h), self._err, ERRLEN), self._err)
-
-    def feed(self, text):
-        """text: bytes made of whole lines (must end with a newline)"""
-        _check(self._L.wgbsseg_homog_feed(self._h, text, len(text), self._err, ERRLEN), self._err)
-
-    def kernel_ms(self):
-        """device time of the counting kernel over every chunk fed so far (waits for them)"""
-        return float(self._L.wgbsseg_homog_kernel_ms(self._h))
+        self._call('create', int(device), s.ctypes.data, e.ctypes.data, s.size, r.ctypes.data, self.n_bins, int(min_cpgs),
+                   1 if inclusive else 0, C.byref(self._h))
 
     def finish(self):
         out = np.empty((self.n_blocks, self.n_bins), dtype=np.int32)
-        _check(self._L.wgbsseg_homog_finish(self._h, out.ctypes.data, self._err, ERRLEN), self._err)
+        self._call('finish', self._h, out.ctypes.data)
         return out
 
-    def close(self):
-        if self._h:
-            self._L.wgbsseg_homog_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class Bimodal:
+class Bimodal(_PatFeed):
     """wgbsseg_bimodal: pat text -> per block [starts, ends) (any order) the two-allele EM test's raw numbers on one GPU.
     finish() -> (float64 [n][3]: ll0, ll_em, sum of n_per_col; int64 [n][3]: columns, rows, EM iterations)."""
+    _abi = 'bimodal'
 
     def __init__(self, starts, ends, strict=False, min_len=1, device=0, max_lds_cols=-1):
-        self._L = load()
-        self._h = C.c_void_p()
-        self._err = C.create_string_buffer(ERRLEN)
+        super().__init__()
         s = np.ascontiguousarray(starts, dtype=np.int64)
         e = np.ascontiguousarray(ends, dtype=np.int64)
         if s.shape != e.shape or s.ndim != 1:
             raise ValueError('starts / ends: one value per block')
         self.n_blocks = int(s.size)
-        _check(self._L.wgbsseg_bimodal_create(int(device), s.ctypes.data, e.ctypes.data, s.size, 1 if strict else 0, int(min_len),
-                                              int(max_lds_cols), C.byref(self._h), self._err, ERRLEN), self._err)
-
-    def feed(self, text):
-        """text: bytes made of whole lines (must end with a newline)"""
-        _check(self._L.wgbsseg_bimodal_feed(self._h, text, len(text), self._err, ERRLEN), self._err)
-
-    def kernel_ms(self):
-        """device time of every launch so far (waits for them)"""
-        return float(self._L.wgbsseg_bimodal_kernel_ms(self._h))
+        self._call('create', int(device), s.ctypes.data, e.ctypes.data, s.size, 1 if strict else 0, int(min_len), int(max_lds_cols),
+                   C.byref(self._h))
 
     def finish(self):
         ll = np.empty((self.n_blocks, 3), dtype=np.float64)
         cnt = np.empty((self.n_blocks, 3), dtype=np.int64)
-        _check(self._L.wgbsseg_bimodal_finish(self._h, ll.ctypes.data, cnt.ctypes.data, self._err, ERRLEN), self._err)
+        self._call('finish', self._h, ll.ctypes.data, cnt.ctypes.data)
         return ll, cnt
-
-    def close(self):
-        if self._h:
-            self._L.wgbsseg_bimodal_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
 
 def debug_homog_bins(edges, max_total):

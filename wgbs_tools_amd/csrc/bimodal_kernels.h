@@ -1,6 +1,6 @@
 // bimodal_kernels.h — `wgbstools test_bimodal` on gfx950: per block, the reference's two-allele hard-assignment EM over the
-// reads of the block and the one-allele likelihood it is tested against.  Included by wgbsseg.hip after homog_kernels.h
-// (WG_BLOCK, WG_PAT_TILE, PatText, wg_pat_tile_lines, wg_pat_parse_line, wg_log2 with g_wg_tables).
+// reads of the block and the one-allele likelihood it is tested against.  The pat text format comes from pat_kernels.h (WG_PAT_TILE,
+// PatTile, PatText, wg_pat_tile_lines, wg_pat_parse_line); WG_BLOCK and wg_log2 with g_wg_tables through its seg_kernels.h.
 //
 // The reference (src/python/test_bimodal.py:25-176) asks tabix, per block [s1, s2), for the reads starting in
 // [max(1, s1 - 150), s2 - 1], builds a dense matrix with one row per read copy and runs its EM in numpy.  Here the pat text
@@ -28,6 +28,7 @@
 //            returns the last new_ll; between passes p_c[z] = 1e-3 + C counts of cluster z, p_t likewise,
 //            l_p = log2(p / (p_c + p_t)); the first pass uses p_c = {0.9, 0.1}, p_t = 1 - p_c.
 #pragma once
+#include "pat_kernels.h"
 
 #define WG_BIM_WAVE 64
 #define WG_BIM_LDS_COLS 256           // LDS path: 256 columns x 48 B = 12 KiB per wavefront (13 wavefronts per CU by LDS)
@@ -81,18 +82,16 @@ __device__ __forceinline__ uint32_t wg_bim_code(char c) { return c == 'C' ? 1u :
 __global__ __launch_bounds__(WG_BLOCK) void k_bim_tile_count(const char* __restrict__ text, int64_t n, uint32_t* __restrict__ tile_cnt,
                                                              wg_bim_state* st, unsigned long long chunk_off)
 {
-    __shared__ __attribute__((aligned(16))) char tx[16 + WG_PAT_TILE + WG_PAT_OVER];
-    __shared__ uint16_t lstart[WG_PAT_TILE / 2 + 1];
-    __shared__ uint32_t wtot[WG_BLOCK / 64];
+    __shared__ PatTile tile;
     __shared__ uint32_t s_lines, s_words;
     const int tid = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * WG_PAT_TILE;
     if (tid == 0) { s_lines = 0; s_words = 0; }
-    const uint32_t total = wg_pat_tile_lines(text, n, base, tx, lstart, wtot);    // (synchronises)
-    const PatText T = {tx + 16, text, base, n};
+    const uint32_t total = wg_pat_tile_lines(text, n, base, tile);    // (synchronises)
+    const PatText T = tile.text(text, base, n);
     uint32_t lines = 0, words = 0;
     for (uint32_t l = (uint32_t)tid; l < total; l += WG_BLOCK) {
-        const int64_t p = base + lstart[l];
+        const int64_t p = base + tile.lstart[l];
         int64_t site = 0, ps = 0, plen = 0, count = 0;
         if (!wg_pat_parse_line(T, p, n, site, ps, plen, count)) { atomicMin(&st->bad, chunk_off + (unsigned long long)p); continue; }
         if (count < 0) { atomicMin(&st->neg, chunk_off + (unsigned long long)p); continue; }
@@ -139,14 +138,12 @@ __global__ __launch_bounds__(WG_BLOCK) void k_bim_fill(const char* __restrict__ 
                                                        long long* __restrict__ r_woff, uint32_t* __restrict__ words, long long* __restrict__ pos,
                                                        const wg_bim_state* st, unsigned long long chunk_off)
 {
-    __shared__ __attribute__((aligned(16))) char tx[16 + WG_PAT_TILE + WG_PAT_OVER];
-    __shared__ uint16_t lstart[WG_PAT_TILE / 2 + 1];
-    __shared__ uint32_t wtot[WG_BLOCK / 64];
+    __shared__ PatTile tile;
     __shared__ uint32_t wl[WG_BLOCK / 64], ww[WG_BLOCK / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t base = (int64_t)blockIdx.x * WG_PAT_TILE;
-    const uint32_t total = wg_pat_tile_lines(text, n, base, tx, lstart, wtot);
-    const PatText T = {tx + 16, text, base, n};
+    const uint32_t total = wg_pat_tile_lines(text, n, base, tile);
+    const PatText T = tile.text(text, base, n);
     const long long R0 = st->R0;
     long long row = tile_base[2 * blockIdx.x], word = tile_base[2 * blockIdx.x + 1];
     for (uint32_t r0 = 0; r0 < total; r0 += WG_BLOCK) {
@@ -154,7 +151,7 @@ __global__ __launch_bounds__(WG_BLOCK) void k_bim_fill(const char* __restrict__ 
         int64_t p = 0, site = 0, ps = 0, plen = 0, count = 0;
         bool ok = false;
         if (l < total) {
-            p = base + lstart[l];
+            p = base + tile.lstart[l];
             ok = wg_pat_parse_line(T, p, n, site, ps, plen, count) && count >= 0;
         }
         const uint32_t a = ok ? 1u : 0u, b = ok ? (uint32_t)((plen + 15) >> 4) : 0u;

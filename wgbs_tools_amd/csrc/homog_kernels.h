@@ -1,6 +1,6 @@
 // homog_kernels.h — `wgbstools homog` on gfx950: per block, the reads that are mostly unmethylated (U), mixed (X) or mostly
-// methylated (M).  Included by wgbsseg.hip after seg_kernels.h (WG_BLOCK, WG_PAT_TILE / WG_PAT_OVER, PatText, wg_pat_tile_lines,
-// wg_pat_parse_line).
+// methylated (M).  The pat text format comes from pat_kernels.h (WG_PAT_TILE, PatTile, PatText, wg_pat_tile_lines, wg_pat_parse_line;
+// WG_BLOCK through its seg_kernels.h).
 //
 // The reference (src/homog/homog.cpp:154-260) streams the sorted blocks beside the sorted reads and keeps a deque of the
 // blocks a read may still reach.  On reads sorted by start and blocks sorted by (startCpG, endCpG) every one of its stop
@@ -34,6 +34,7 @@
 // is found by scanning back from the tile; before a chunk's first line it is the last read of the previous chunk, kept in
 // device memory (prev_in / prev_out: two slots alternating per chunk).
 #pragma once
+#include "pat_kernels.h"
 
 #define WG_HOMOG_MAX_BINS 8
 #define WG_HOMOG_WIN 512
@@ -61,16 +62,16 @@ __device__ __forceinline__ int64_t wg_homog_upper(const int32_t* a, int64_t lo, 
     return lo;
 }
 
-__global__ __launch_bounds__(WG_BLOCK) void k_homog_count(const char* __restrict__ text, int64_t n,
+// (waves_per_eu(6): the kernel's occupancy.  With the tile in one PatTile object the LDS layout puts s_lo / s_hi side by side, the
+// compiler merges their accesses, and the allocation lands 2 VGPRs above the 80 that 6 waves per SIMD allow.)
+__global__ __launch_bounds__(WG_BLOCK) __attribute__((amdgpu_waves_per_eu(6))) void k_homog_count(const char* __restrict__ text, int64_t n,
                                                           const int32_t* __restrict__ bstart, const int32_t* __restrict__ bend,
                                                           const int32_t* __restrict__ bpmax, int64_t nblk, int64_t last_end,
                                                           const float* __restrict__ range, int nb, int min_cpgs, int inclusive,
                                                           int32_t* __restrict__ counts, unsigned long long* bad, unsigned long long* desc,
                                                           const long long* prev_in, long long* prev_out, unsigned long long chunk_off)
 {
-    __shared__ __attribute__((aligned(16))) char tx[16 + WG_PAT_TILE + WG_PAT_OVER];
-    __shared__ uint16_t lstart[WG_PAT_TILE / 2 + 1];
-    __shared__ uint32_t wtot[WG_BLOCK / 64];
+    __shared__ PatTile tile;
     __shared__ long long s_site[WG_BLOCK];                   // the round's starts (WG_HOMOG_NO_SITE: no line / malformed)
     __shared__ int32_t w_start[WG_HOMOG_WIN], w_end[WG_HOMOG_WIN], w_pmax[WG_HOMOG_WIN];
     __shared__ int32_t w_cnt[WG_HOMOG_CELLS];
@@ -89,20 +90,20 @@ __global__ __launch_bounds__(WG_BLOCK) void k_homog_count(const char* __restrict
         if (i < 0) pv = *prev_in;
         else {
             while (i > 0 && text[i - 1] != '\n') i--;
-            const PatText G = {tx, text, INT64_MIN / 4, n};       // (base far below: every byte from global memory)
+            const PatText G = {tile.tx, text, INT64_MIN / 4, n};       // (base far below: every byte from global memory)
             int64_t site = 0, ps = 0, plen = 0, count = 0;
             if (wg_pat_parse_line(G, i, n, site, ps, plen, count)) pv = site;
         }
         s_prev = pv;
     }
-    const uint32_t total = wg_pat_tile_lines(text, n, base, tx, lstart, wtot);   // (synchronises: s_prev, s_range visible)
-    const PatText T = {tx + 16, text, base, n};
+    const uint32_t total = wg_pat_tile_lines(text, n, base, tile);   // (synchronises: s_prev, s_range visible)
+    const PatText T = tile.text(text, base, n);
     for (uint32_t r0 = 0; r0 < total; r0 += WG_BLOCK) {
         const uint32_t l = r0 + (uint32_t)tid;
         int64_t p = 0, site = 0, ps = 0, plen = 0, count = 0;
         bool ok = false;
         if (l < total) {
-            p = base + lstart[l];
+            p = base + tile.lstart[l];
             ok = wg_pat_parse_line(T, p, n, site, ps, plen, count);
             if (!ok) atomicMin(bad, chunk_off + (unsigned long long)p);
         }

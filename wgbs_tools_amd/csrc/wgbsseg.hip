@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <functional>
 #include <memory>
 #include <string>
@@ -28,6 +29,7 @@
 
 #include "../../include/wgbsseg.h"
 #include "seg_kernels.h"
+#include "pat_kernels.h"
 #include "homog_kernels.h"
 #include "bimodal_kernels.h"
 #include "plain_dp.h"
@@ -266,6 +268,26 @@ int wgbsseg_device_count(void)
 namespace {
 int create_ctx(int device, bool scan_low_priority, wgbsseg_ctx** out, char* err, size_t errlen);
 std::atomic<int> g_live_ctx[64];      // contexts alive per device (gated stages want theirs alone on its device)
+
+// what every context and engine asks of its device: it exists and is a gfx950 (it is made the current device)
+int check_device(int device, char* err, size_t errlen)
+{
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) {
+        set_err(err, errlen, "no HIP device available (%s); libwgbsseg has no CPU fallback", hipGetErrorString(e));
+        return WGBSSEG_E_HIP;
+    }
+    if (device < 0 || device >= n) { set_err(err, errlen, "device %d out of range (0..%d)", device, n - 1); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    if (!strstr(prop.gcnArchName, "gfx950")) {
+        set_err(err, errlen, "device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
+        return WGBSSEG_E_HIP;
+    }
+    return WGBSSEG_OK;
+}
 }
 extern "C" {
 
@@ -282,20 +304,8 @@ int create_ctx(int device, bool scan_low_priority, wgbsseg_ctx** out, char* err,
 {
     if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
     *out = nullptr;
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-        set_err(err, errlen, "no HIP device available (%s); libwgbsseg has no CPU fallback", hipGetErrorString(e));
-        return WGBSSEG_E_HIP;
-    }
-    if (device < 0 || device >= n) { set_err(err, errlen, "device %d out of range (0..%d)", device, n - 1); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device));
-    if (!strstr(prop.gcnArchName, "gfx950")) {
-        set_err(err, errlen, "device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
-        return WGBSSEG_E_HIP;
-    }
+    const int rc = check_device(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     HIP_TRY(set_kernel_attributes());        // per device, checked: k_dp / k_cost ask for more than 64 KB of dynamic LDS
     wgbsseg_ctx* c = new (std::nothrow) wgbsseg_ctx();
     if (!c) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
@@ -2706,28 +2716,122 @@ int wgbsseg_convert_regions(wgbsseg_ctx* c, const int64_t* chrom_lo, const int64
 
 }  // extern "C"
 
-// pat -> beta accumulator: counts on one device, text chunks through two page-locked staging buffers so that the caller's
-// decompression of chunk k+1 overlaps the copy and the kernel of chunk k.
-struct wgbsseg_patbeta {
+// The pat-text feed of an engine (wgbsseg_patbeta / _homog / _bimodal): one device and stream; text chunks through two page-locked
+// staging buffers and two device buffers, so that the caller's decompression of chunk k+1 overlaps the copy and the kernels of
+// chunk k; the input offset of the next chunk; and the device time of the launches the engine brackets with span_begin / span_end.
+struct PatFeed {
     int device = 0;
     hipStream_t st = nullptr;
-    int64_t start = 1, end = 1;
-    DevBuf meth, cov, text[2], outb, bad;
     PinnedBuf stage[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    DevBuf text[2];
+    hipEvent_t ev[2] = {nullptr, nullptr};                        // after the work on slot k's text
     bool busy[2] = {false, false};
-    int k = 0;
-    unsigned long long fed = 0;
-    double kernel_ms = 0.0;                                       // k_pat_count launches whose events have been read
-    hipEvent_t k0[2] = {nullptr, nullptr}, k1[2] = {nullptr, nullptr};   // around the counting kernel of the chunk in slot k
-    bool timed[2] = {false, false};                               // slot k holds a pair not yet added to kernel_ms
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    void collect(int k)                                           // (after the slot's work is known to be complete)
+    int k = 0;                                                    // the slot of the next chunk
+    unsigned long long fed = 0;                                   // bytes fed so far
+    double span_ms = 0.0;                                         // the spans read so far
+    std::deque<std::pair<hipEvent_t, hipEvent_t>> spans;          // recorded, in stream order, not read yet
+    std::vector<hipEvent_t> spare;                                // the events of read spans, for the next ones
+
+    int open(int dev, char* err, size_t errlen)
     {
-        float ms = 0.f;
-        if (timed[k] && hipEventElapsedTime(&ms, k0[k], k1[k]) == hipSuccess) kernel_ms += (double)ms;
-        timed[k] = false;
+        const int rc = check_device(dev, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        device = dev;
+        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        for (auto& e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return WGBSSEG_OK;
     }
+    void close()                                                  // (the engine frees its own buffers after this)
+    {
+        (void)hipSetDevice(device);
+        if (st) (void)hipStreamSynchronize(st);
+        collect();
+        for (auto& b : text) b.release();
+        for (auto& s : stage) s.release();
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto& s : spans) { (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second); }
+        for (hipEvent_t e : spare) (void)hipEventDestroy(e);
+        if (st) (void)hipStreamDestroy(st);
+    }
+    // the checks of a feed call: -1 when refused (err set), 0 for an empty chunk, else the chunk's number of tiles
+    static int64_t tiles(const char* name, const void* engine, const char* text, int64_t n_bytes, char* err, size_t errlen)
+    {
+        if (!engine || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to %s_feed", name); return -1; }
+        if (n_bytes == 0) return 0;
+        if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "%s_feed: a chunk must end with a complete line", name); return -1; }
+        const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;     // one workgroup per tile of text
+        if (gx > 0x7fffffff) { set_err(err, errlen, "%s_feed: chunk too large", name); return -1; }
+        return gx;
+    }
+    // waits until the chunk before last (same slot) has been consumed, then queues the copy of this one; *dev: its device copy
+    int stage_chunk(const char* host, int64_t n_bytes, const char** dev, char* err, size_t errlen)
+    {
+        if (busy[k]) { HIP_TRY(hipEventSynchronize(ev[k])); collect(); }
+        if (!stage[k].ensure((size_t)n_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+        HIP_TRY(text[k].ensure((size_t)n_bytes));
+        memcpy(stage[k].p, host, (size_t)n_bytes);
+        HIP_TRY(hipMemcpyAsync(text[k].p, stage[k].p, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+        *dev = text[k].as<char>();
+        return WGBSSEG_OK;
+    }
+    // the chunk's work has been queued: the slot is busy until the stream passes here
+    hipError_t chunk_queued(int64_t n_bytes)
+    {
+        const hipError_t e = hipEventRecord(ev[k], st);
+        busy[k] = true;
+        k ^= 1;
+        fed += (unsigned long long)n_bytes;
+        return e;
+    }
+    hipError_t span_begin()
+    {
+        hipEvent_t e[2] = {nullptr, nullptr};
+        for (auto& x : e) {
+            if (!spare.empty()) { x = spare.back(); spare.pop_back(); continue; }
+            const hipError_t r = hipEventCreate(&x);
+            if (r != hipSuccess) { if (e[0]) spare.push_back(e[0]); return r; }
+        }
+        spans.push_back({e[0], e[1]});
+        return hipEventRecord(e[0], st);
+    }
+    hipError_t span_end() { return hipEventRecord(spans.back().second, st); }
+    // adds the spans the stream has passed to span_ms (in order: the first one still running ends the walk)
+    void collect()
+    {
+        while (!spans.empty()) {
+            float ms = 0.f;
+            const hipError_t e = hipEventElapsedTime(&ms, spans.front().first, spans.front().second);
+            if (e == hipErrorNotReady) break;
+            if (e == hipSuccess) span_ms += (double)ms;
+            spare.push_back(spans.front().first); spare.push_back(spans.front().second);
+            spans.pop_front();
+        }
+    }
+    double kernel_ms()                                            // waits for the stream; -1 on a HIP error
+    {
+        if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1.0;
+        collect();
+        return span_ms;
+    }
+};
+
+// the refusals of the input that the pat engines share, "<prefix> <what> at byte offset <off> ..."; false when off is ~0 (none)
+enum class PatRefusal { bad_line, unsorted };
+static bool pat_refused(PatRefusal why, unsigned long long off, const char* prefix, char* err, size_t errlen)
+{
+    if (off == ~0ULL) return false;
+    if (why == PatRefusal::bad_line)
+        set_err(err, errlen, "%s invalid line at byte offset %llu of the input (too few columns, or a site / count that is not a number)", prefix, off);
+    else
+        set_err(err, errlen, "%s the pat file is not sorted: the read at byte offset %llu of the input starts before the read before it", prefix, off);
+    return true;
+}
+
+// pat -> beta accumulator: counts on one device; k_pat_count is timed.
+struct wgbsseg_patbeta {
+    PatFeed feed;
+    int64_t start = 1, end = 1;
+    DevBuf meth, cov, outb, bad;
 };
 
 extern "C" {
@@ -2739,26 +2843,19 @@ int wgbsseg_patbeta_create(int device, int64_t start_cpg, int64_t end_cpg, wgbss
     if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
     *out = nullptr;
     if (start_cpg < 1 || end_cpg <= start_cpg || end_cpg - start_cpg > 0x7fffffff) { set_err(err, errlen, "patbeta: bad CpG range [%lld, %lld)", (long long)start_cpg, (long long)end_cpg); return WGBSSEG_E_ARG; }
-    wgbsseg_ctx* probe = nullptr;                                 // device checks (gfx950, index) as for a segment context
-    int rc = wgbsseg_create(device, &probe, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    wgbsseg_destroy(probe);
     // (the struct's members are plain handles: whatever has been created when a HIP call fails is released by the destroy
     // function, which is what the owner calls on every early return)
     struct Free { void operator()(wgbsseg_patbeta* q) const { wgbsseg_patbeta_destroy(q); } };
     std::unique_ptr<wgbsseg_patbeta, Free> p(new (std::nothrow) wgbsseg_patbeta());
     if (!p) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
-    p->device = device; p->start = start_cpg; p->end = end_cpg;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&p->st, hipStreamNonBlocking));
-    for (auto& e : p->ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventCreate(&p->t0)); HIP_TRY(hipEventCreate(&p->t1));
-    for (int k = 0; k < 2; k++) { HIP_TRY(hipEventCreate(&p->k0[k])); HIP_TRY(hipEventCreate(&p->k1[k])); }
+    const int rc = p->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    p->start = start_cpg; p->end = end_cpg;
     const size_t nb = (size_t)(end_cpg - start_cpg) * 4;
     HIP_TRY(p->meth.ensure(nb)); HIP_TRY(p->cov.ensure(nb)); HIP_TRY(p->bad.ensure(8));
-    HIP_TRY(hipMemsetAsync(p->meth.p, 0, nb, p->st));            // (the reference leaves its arrays uninitialised: stdin2beta.cpp:48-49)
-    HIP_TRY(hipMemsetAsync(p->cov.p, 0, nb, p->st));
-    HIP_TRY(hipMemsetAsync(p->bad.p, 0xff, 8, p->st));
+    HIP_TRY(hipMemsetAsync(p->meth.p, 0, nb, p->feed.st));       // (the reference leaves its arrays uninitialised: stdin2beta.cpp:48-49)
+    HIP_TRY(hipMemsetAsync(p->cov.p, 0, nb, p->feed.st));
+    HIP_TRY(hipMemsetAsync(p->bad.p, 0xff, 8, p->feed.st));
     *out = p.release();
     return WGBSSEG_OK;
 }
@@ -2766,99 +2863,63 @@ int wgbsseg_patbeta_create(int device, int64_t start_cpg, int64_t end_cpg, wgbss
 void wgbsseg_patbeta_destroy(wgbsseg_patbeta* p)
 {
     if (!p) return;
-    (void)hipSetDevice(p->device);
-    if (p->st) { (void)hipStreamSynchronize(p->st); }
-    for (DevBuf* b : {&p->meth, &p->cov, &p->text[0], &p->text[1], &p->outb, &p->bad}) b->release();
-    for (auto& s : p->stage) s.release();
-    for (auto& e : p->ev) if (e) (void)hipEventDestroy(e);
-    if (p->t0) (void)hipEventDestroy(p->t0);
-    if (p->t1) (void)hipEventDestroy(p->t1);
-    for (int k = 0; k < 2; k++) { if (p->k0[k]) (void)hipEventDestroy(p->k0[k]); if (p->k1[k]) (void)hipEventDestroy(p->k1[k]); }
-    if (p->st) (void)hipStreamDestroy(p->st);
+    p->feed.close();
+    for (DevBuf* b : {&p->meth, &p->cov, &p->outb, &p->bad}) b->release();
     delete p;
 }
 
 int wgbsseg_patbeta_feed(wgbsseg_patbeta* p, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    if (!p || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to patbeta_feed"); return WGBSSEG_E_ARG; }
-    if (n_bytes == 0) return WGBSSEG_OK;
-    if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "patbeta_feed: a chunk must end with a complete line"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(p->device));
-    const int k = p->k;
-    if (p->busy[k]) { HIP_TRY(hipEventSynchronize(p->ev[k])); p->collect(k); }      // its previous chunk has been consumed
-    if (!p->stage[k].ensure((size_t)n_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
-    HIP_TRY(p->text[k].ensure((size_t)n_bytes));
-    memcpy(p->stage[k].p, text, (size_t)n_bytes);
-    HIP_TRY(hipMemcpyAsync(p->text[k].p, p->stage[k].p, (size_t)n_bytes, hipMemcpyHostToDevice, p->st));
-    const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;     // one workgroup per tile of text
-    if (gx > 0x7fffffff) { set_err(err, errlen, "patbeta_feed: chunk too large"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipEventRecord(p->k0[k], p->st));
-    hipLaunchKernelGGL(k_pat_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, p->st, p->text[k].as<char>(), n_bytes, p->start, p->end,
-                       p->meth.as<int32_t>(), p->cov.as<int32_t>(), p->bad.as<unsigned long long>(), p->fed);
+    const int64_t gx = PatFeed::tiles("patbeta", p, text, n_bytes, err, errlen);
+    if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
+    PatFeed& f = p->feed;
+    HIP_TRY(hipSetDevice(f.device));
+    const char* dtext = nullptr;
+    const int rc = f.stage_chunk(text, n_bytes, &dtext, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    HIP_TRY(f.span_begin());
+    hipLaunchKernelGGL(k_pat_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, p->start, p->end,
+                       p->meth.as<int32_t>(), p->cov.as<int32_t>(), p->bad.as<unsigned long long>(), f.fed);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(p->k1[k], p->st));
-    p->timed[k] = true;
-    HIP_TRY(hipEventRecord(p->ev[k], p->st));
-    p->busy[k] = true;
-    p->k ^= 1;
-    p->fed += (unsigned long long)n_bytes;
+    HIP_TRY(f.span_end());
+    HIP_TRY(f.chunk_queued(n_bytes));
     return WGBSSEG_OK;
 }
 
 int wgbsseg_patbeta_finish(wgbsseg_patbeta* p, int32_t lbeta, void* out, char* err, size_t errlen)
 {
     if (!p || !out) { set_err(err, errlen, "bad arguments to patbeta_finish"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(p->device));
+    const hipStream_t st = p->feed.st;
+    HIP_TRY(hipSetDevice(p->feed.device));
     const int64_t n = p->end - p->start;
     const size_t ob = (size_t)n * (lbeta ? 4 : 2);
     HIP_TRY(p->outb.ensure(ob));
     unsigned long long bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, p->bad.p, 8, hipMemcpyDeviceToHost, p->st));
-    HIP_TRY(hipStreamSynchronize(p->st));
-    if (bad != ~0ULL) {
-        set_err(err, errlen, "failed calculating beta: invalid line at byte offset %llu of the input (too few columns, or a site / count that is not a number)", bad);
-        return WGBSSEG_E_ARG;
-    }
-    hipLaunchKernelGGL(k_pat_trim, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, p->st, p->meth.as<int32_t>(), p->cov.as<int32_t>(), n,
+    HIP_TRY(hipMemcpyAsync(&bad, p->bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (pat_refused(PatRefusal::bad_line, bad, "failed calculating beta:", err, errlen)) return WGBSSEG_E_ARG;
+    hipLaunchKernelGGL(k_pat_trim, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, p->meth.as<int32_t>(), p->cov.as<int32_t>(), n,
                        (int)lbeta, p->outb.p);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, p->outb.p, ob, hipMemcpyDeviceToHost, p->st));
-    HIP_TRY(hipStreamSynchronize(p->st));
+    HIP_TRY(hipMemcpyAsync(out, p->outb.p, ob, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return WGBSSEG_OK;
 }
 
 double wgbsseg_patbeta_kernel_ms(wgbsseg_patbeta* p)
 {
-    if (!p) return -1.0;
-    if (hipSetDevice(p->device) != hipSuccess || hipStreamSynchronize(p->st) != hipSuccess) return -1.0;
-    p->collect(0); p->collect(1);
-    return p->kernel_ms;
+    return p ? p->feed.kernel_ms() : -1.0;
 }
 
 }  // extern "C"
 
-// `wgbstools homog` accumulator: (block, bin) read counts on one device; text chunks through two page-locked staging buffers as
-// for wgbsseg_patbeta (the caller inflates chunk k+1 while chunk k is copied and counted).
+// `wgbstools homog` accumulator: (block, bin) read counts on one device; k_homog_count is timed.
 struct wgbsseg_homog {
-    int device = 0;
-    hipStream_t st = nullptr;
+    PatFeed feed;
     int64_t n_blocks = 0, last_end = 0;
     int n_bins = 0, min_cpgs = 0, inclusive = 0;
-    DevBuf bstart, bend, bpmax, range, counts, text[2], bad, desc, prev;
-    PinnedBuf stage[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool busy[2] = {false, false};
-    int k = 0;
-    unsigned long long fed = 0, chunks = 0;
-    double kernel_ms = 0.0;
-    hipEvent_t k0[2] = {nullptr, nullptr}, k1[2] = {nullptr, nullptr};
-    bool timed[2] = {false, false};
-    void collect(int k)
-    {
-        float ms = 0.f;
-        if (timed[k] && hipEventElapsedTime(&ms, k0[k], k1[k]) == hipSuccess) kernel_ms += (double)ms;
-        timed[k] = false;
-    }
+    DevBuf bstart, bend, bpmax, range, counts, bad, desc, prev;
+    unsigned long long chunks = 0;
 };
 
 extern "C" {
@@ -2888,19 +2949,14 @@ int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* en
         run = std::max(run, (int32_t)b);
         pm[(size_t)j] = run;
     }
-    wgbsseg_ctx* probe = nullptr;                                 // device checks (gfx950, index) as for a segment context
-    int rc = wgbsseg_create(device, &probe, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    wgbsseg_destroy(probe);
     struct Free { void operator()(wgbsseg_homog* q) const { wgbsseg_homog_destroy(q); } };
     std::unique_ptr<wgbsseg_homog, Free> h(new (std::nothrow) wgbsseg_homog());
     if (!h) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
-    h->device = device; h->n_blocks = n_blocks; h->last_end = end_cpg[n_blocks - 1];
+    const int rc = h->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    h->n_blocks = n_blocks; h->last_end = end_cpg[n_blocks - 1];
     h->n_bins = n_bins; h->min_cpgs = min_cpgs; h->inclusive = inclusive ? 1 : 0;
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&h->st, hipStreamNonBlocking));
-    for (auto& e : h->ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (int q = 0; q < 2; q++) { HIP_TRY(hipEventCreate(&h->k0[q])); HIP_TRY(hipEventCreate(&h->k1[q])); }
+    const hipStream_t st = h->feed.st;
     const size_t nb4 = (size_t)n_blocks * 4, cb = (size_t)n_blocks * (size_t)n_bins * 4;
     HIP_TRY(h->bstart.ensure(nb4)); HIP_TRY(h->bend.ensure(nb4)); HIP_TRY(h->bpmax.ensure(nb4));
     HIP_TRY(h->range.ensure(sizeof(float) * (size_t)(n_bins + 1))); HIP_TRY(h->counts.ensure(cb));
@@ -2911,9 +2967,9 @@ int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* en
     HIP_TRY(hipMemcpy(h->range.p, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice));
     const long long none[2] = {WG_HOMOG_NO_SITE, WG_HOMOG_NO_SITE};
     HIP_TRY(hipMemcpy(h->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(h->counts.p, 0, cb, h->st));
-    HIP_TRY(hipMemsetAsync(h->bad.p, 0xff, 8, h->st));
-    HIP_TRY(hipMemsetAsync(h->desc.p, 0xff, 8, h->st));
+    HIP_TRY(hipMemsetAsync(h->counts.p, 0, cb, st));
+    HIP_TRY(hipMemsetAsync(h->bad.p, 0xff, 8, st));
+    HIP_TRY(hipMemsetAsync(h->desc.p, 0xff, 8, st));
     *out = h.release();
     return WGBSSEG_OK;
 }
@@ -2921,46 +2977,32 @@ int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* en
 void wgbsseg_homog_destroy(wgbsseg_homog* h)
 {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->st) { (void)hipStreamSynchronize(h->st); }
-    for (DevBuf* b : {&h->bstart, &h->bend, &h->bpmax, &h->range, &h->counts, &h->text[0], &h->text[1], &h->bad, &h->desc, &h->prev}) b->release();
-    for (auto& s : h->stage) s.release();
-    for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
-    for (int q = 0; q < 2; q++) { if (h->k0[q]) (void)hipEventDestroy(h->k0[q]); if (h->k1[q]) (void)hipEventDestroy(h->k1[q]); }
-    if (h->st) (void)hipStreamDestroy(h->st);
+    h->feed.close();
+    for (DevBuf* b : {&h->bstart, &h->bend, &h->bpmax, &h->range, &h->counts, &h->bad, &h->desc, &h->prev}) b->release();
     delete h;
 }
 
 int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    if (!h || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to homog_feed"); return WGBSSEG_E_ARG; }
-    if (n_bytes == 0) return WGBSSEG_OK;
-    if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "homog_feed: a chunk must end with a complete line"); return WGBSSEG_E_ARG; }
-    const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;     // one workgroup per tile of text
-    if (gx > 0x7fffffff) { set_err(err, errlen, "homog_feed: chunk too large"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(h->device));
-    const int k = h->k;
-    if (h->busy[k]) { HIP_TRY(hipEventSynchronize(h->ev[k])); h->collect(k); }      // its previous chunk has been consumed
-    if (!h->stage[k].ensure((size_t)n_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
-    HIP_TRY(h->text[k].ensure((size_t)n_bytes));
-    memcpy(h->stage[k].p, text, (size_t)n_bytes);
-    HIP_TRY(hipMemcpyAsync(h->text[k].p, h->stage[k].p, (size_t)n_bytes, hipMemcpyHostToDevice, h->st));
+    const int64_t gx = PatFeed::tiles("homog", h, text, n_bytes, err, errlen);
+    if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
+    PatFeed& f = h->feed;
+    HIP_TRY(hipSetDevice(f.device));
+    const char* dtext = nullptr;
+    const int rc = f.stage_chunk(text, n_bytes, &dtext, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
     long long* prev = h->prev.as<long long>();
     const int out_slot = (int)(h->chunks & 1), in_slot = out_slot ^ 1;
-    HIP_TRY(hipMemcpyAsync(prev + out_slot, prev + in_slot, 8, hipMemcpyDeviceToDevice, h->st));
-    HIP_TRY(hipEventRecord(h->k0[k], h->st));
-    hipLaunchKernelGGL(k_homog_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, h->st, h->text[k].as<char>(), n_bytes,
+    HIP_TRY(hipMemcpyAsync(prev + out_slot, prev + in_slot, 8, hipMemcpyDeviceToDevice, f.st));
+    HIP_TRY(f.span_begin());
+    hipLaunchKernelGGL(k_homog_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes,
                        h->bstart.as<int32_t>(), h->bend.as<int32_t>(), h->bpmax.as<int32_t>(), h->n_blocks, h->last_end,
                        h->range.as<float>(), h->n_bins, h->min_cpgs, h->inclusive, h->counts.as<int32_t>(),
-                       h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), prev + in_slot, prev + out_slot, h->fed);
+                       h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), prev + in_slot, prev + out_slot, f.fed);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(h->k1[k], h->st));
-    h->timed[k] = true;
-    HIP_TRY(hipEventRecord(h->ev[k], h->st));
-    h->busy[k] = true;
-    h->k ^= 1;
-    h->fed += (unsigned long long)n_bytes;
+    HIP_TRY(f.span_end());
+    HIP_TRY(f.chunk_queued(n_bytes));
     h->chunks += 1;
     return WGBSSEG_OK;
 }
@@ -2968,30 +3010,22 @@ int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char
 int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t errlen)
 {
     if (!h || !counts) { set_err(err, errlen, "bad arguments to homog_finish"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(h->device));
+    const hipStream_t st = h->feed.st;
+    HIP_TRY(hipSetDevice(h->feed.device));
     unsigned long long bad = 0, desc = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, h->st));
-    HIP_TRY(hipMemcpyAsync(&desc, h->desc.p, 8, hipMemcpyDeviceToHost, h->st));
-    HIP_TRY(hipStreamSynchronize(h->st));
-    if (bad != ~0ULL) {
-        set_err(err, errlen, "failed calculating homog: invalid line at byte offset %llu of the input (too few columns, or a site / count that is not a number)", bad);
-        return WGBSSEG_E_ARG;
-    }
-    if (desc != ~0ULL) {
-        set_err(err, errlen, "failed calculating homog: the pat file is not sorted: the read at byte offset %llu of the input starts before the read before it", desc);
-        return WGBSSEG_E_ARG;
-    }
-    HIP_TRY(hipMemcpyAsync(counts, h->counts.p, (size_t)h->n_blocks * (size_t)h->n_bins * 4, hipMemcpyDeviceToHost, h->st));
-    HIP_TRY(hipStreamSynchronize(h->st));
+    HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&desc, h->desc.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (pat_refused(PatRefusal::bad_line, bad, "failed calculating homog:", err, errlen)) return WGBSSEG_E_ARG;
+    if (pat_refused(PatRefusal::unsorted, desc, "failed calculating homog:", err, errlen)) return WGBSSEG_E_ARG;
+    HIP_TRY(hipMemcpyAsync(counts, h->counts.p, (size_t)h->n_blocks * (size_t)h->n_bins * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return WGBSSEG_OK;
 }
 
 double wgbsseg_homog_kernel_ms(wgbsseg_homog* h)
 {
-    if (!h) return -1.0;
-    if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->st) != hipSuccess) return -1.0;
-    h->collect(0); h->collect(1);
-    return h->kernel_ms;
+    return h ? h->feed.kernel_ms() : -1.0;
 }
 
 int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_total, int8_t* out)
@@ -3020,52 +3054,30 @@ int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_tot
 // `wgbstools test_bimodal` accumulator on one device: the blocks, the read table of the live window (two copies: dropping moves
 // the live rows from one to the other), and the per-block results.  A feed() first waits for the work of the previous chunk
 // (the caller inflated this chunk meanwhile), retires the blocks that chunk completed, drops the reads no pending block can
-// reach, and queues the parse of this chunk; the EM of the retired blocks runs while the caller inflates the next one.
+// reach, and queues the parse of this chunk; the EM of the retired blocks runs while the caller inflates the next one.  Every
+// launch is timed.
 struct wgbsseg_bimodal {
     struct Table { DevBuf start, len, cnt, woff, words; };
-    int device = 0;
-    hipStream_t st = nullptr;
+    PatFeed feed;
     int64_t n_blocks = 0;
     int strict = 0, min_len = 1, lds_cols = WG_BIM_LDS_COLS;
     std::vector<int32_t> s1, s2, by_end;          // by_end: block indexes in (endCpG, file) order
     std::vector<int64_t> lo_after;                // lo_after[p]: min over by_end[p..] of max(1, s1 - 150) (INT64_MAX past the end)
     int64_t pending = 0;                          // by_end[pending..] have not been retired
-    DevBuf bs1, bs2, ids, meta, scr_off, scratch, res_f, res_i, state, text, tile_cnt, tile_base, pos;
+    DevBuf bs1, bs2, ids, meta, scr_off, scratch, res_f, res_i, state, tile_cnt, tile_base, pos;
     Table tab[2];
     int cur = 0;
     size_t cap_rows = 0, cap_words = 0;
-    PinnedBuf stage, host_state, host_meta, host_off;
-    unsigned long long fed = 0;
+    PinnedBuf host_state, host_meta, host_off;
     bool stop = false;                            // an input error was seen: nothing more is computed
-    double kernel_ms = 0.0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> spans;     // device time of every queued piece of work
-    hipError_t span_begin(hipEvent_t* a)
-    {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        hipError_t e = hipEventCreate(&e0);
-        if (e == hipSuccess) e = hipEventCreate(&e1);
-        if (e != hipSuccess) { if (e0) (void)hipEventDestroy(e0); return e; }
-        spans.push_back({e0, e1});
-        *a = e1;
-        return hipEventRecord(e0, st);
-    }
-    void collect()
-    {
-        for (auto& s : spans) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, s.first, s.second) == hipSuccess) kernel_ms += (double)ms;
-            (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second);
-        }
-        spans.clear();
-    }
     wg_bim_state* hs() const { return reinterpret_cast<wg_bim_state*>(host_state.p); }
 };
 
 static int bim_sync_state(wgbsseg_bimodal* b, char* err, size_t errlen)
 {
-    HIP_TRY(hipMemcpyAsync(b->host_state.p, b->state.p, sizeof(wg_bim_state), hipMemcpyDeviceToHost, b->st));
-    HIP_TRY(hipStreamSynchronize(b->st));
-    b->collect();
+    HIP_TRY(hipMemcpyAsync(b->host_state.p, b->state.p, sizeof(wg_bim_state), hipMemcpyDeviceToHost, b->feed.st));
+    HIP_TRY(hipStreamSynchronize(b->feed.st));
+    b->feed.collect();
     const wg_bim_state* s = b->hs();
     if (s->bad != ~0ULL || s->neg != ~0ULL || s->desc != ~0ULL || s->em_cap) b->stop = true;
     return WGBSSEG_OK;
@@ -3103,17 +3115,16 @@ static int bim_retire(wgbsseg_bimodal* b, int64_t p1, char* err, size_t errlen)
     const int64_t n = p1 - b->pending;
     if (n <= 0 || b->stop) return WGBSSEG_OK;
     wgbsseg_bimodal::Table& T = b->tab[b->cur];
-    HIP_TRY(hipMemcpyAsync(b->ids.as<int32_t>(), b->by_end.data() + b->pending, (size_t)n * 4, hipMemcpyHostToDevice, b->st));
-    hipEvent_t e1 = nullptr;
-    HIP_TRY(b->span_begin(&e1));
-    hipLaunchKernelGGL(k_bim_gather, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
+    HIP_TRY(hipMemcpyAsync(b->ids.as<int32_t>(), b->by_end.data() + b->pending, (size_t)n * 4, hipMemcpyHostToDevice, b->feed.st));
+    HIP_TRY(b->feed.span_begin());
+    hipLaunchKernelGGL(k_bim_gather, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->feed.st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
                        b->state.as<wg_bim_state>(), b->bs1.as<int32_t>(), b->bs2.as<int32_t>(), b->ids.as<int32_t>(), b->strict, b->min_len,
                        b->meta.as<wg_bim_meta>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, b->st));
+    HIP_TRY(b->feed.span_end());
     if (!b->host_meta.ensure((size_t)n * sizeof(wg_bim_meta))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
-    HIP_TRY(hipMemcpyAsync(b->host_meta.p, b->meta.p, (size_t)n * sizeof(wg_bim_meta), hipMemcpyDeviceToHost, b->st));
-    HIP_TRY(hipStreamSynchronize(b->st));
+    HIP_TRY(hipMemcpyAsync(b->host_meta.p, b->meta.p, (size_t)n * sizeof(wg_bim_meta), hipMemcpyDeviceToHost, b->feed.st));
+    HIP_TRY(hipStreamSynchronize(b->feed.st));
     const wg_bim_meta* m = reinterpret_cast<const wg_bim_meta*>(b->host_meta.p);
     if (!b->host_off.ensure((size_t)n * 8)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
     long long* off = reinterpret_cast<long long*>(b->host_off.p);     // (read by the copy below after this returns: the next use waits for the stream)
@@ -3128,14 +3139,14 @@ static int bim_retire(wgbsseg_bimodal* b, int64_t p1, char* err, size_t errlen)
         if (m[g].rows > 0 && m[g].ncols > b->lds_cols) { off[g] = (long long)used; used += (size_t)m[g].ncols * 48; }
     }
     if (used) HIP_TRY(b->scratch.ensure(used));
-    HIP_TRY(hipMemcpyAsync(b->scr_off.p, off, (size_t)n * 8, hipMemcpyHostToDevice, b->st));
-    HIP_TRY(b->span_begin(&e1));
-    hipLaunchKernelGGL(k_bim_em, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
+    HIP_TRY(hipMemcpyAsync(b->scr_off.p, off, (size_t)n * 8, hipMemcpyHostToDevice, b->feed.st));
+    HIP_TRY(b->feed.span_begin());
+    hipLaunchKernelGGL(k_bim_em, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->feed.st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
                        T.woff.as<long long>(), T.words.as<uint32_t>(), b->bs1.as<int32_t>(), b->bs2.as<int32_t>(), b->ids.as<int32_t>(),
                        b->meta.as<wg_bim_meta>(), b->scr_off.as<long long>(), b->scratch.as<unsigned char>(), b->lds_cols, b->strict, b->min_len,
                        b->res_f.as<double>(), b->res_i.as<long long>(), b->state.as<wg_bim_state>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, b->st));
+    HIP_TRY(b->feed.span_end());
     b->pending = p1;
     return WGBSSEG_OK;
 }
@@ -3158,22 +3169,18 @@ int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* 
             return WGBSSEG_E_ARG;
         }
     }
-    wgbsseg_ctx* probe = nullptr;                                 // device checks (gfx950, index) as for a segment context
-    int rc = wgbsseg_create(device, &probe, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    wgbsseg_destroy(probe);
     struct Free { void operator()(wgbsseg_bimodal* q) const { wgbsseg_bimodal_destroy(q); } };
     std::unique_ptr<wgbsseg_bimodal, Free> b(new (std::nothrow) wgbsseg_bimodal());
     if (!b) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
-    b->device = device; b->n_blocks = n_blocks; b->strict = strict ? 1 : 0; b->min_len = min_len;
+    const int rc = b->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    b->n_blocks = n_blocks; b->strict = strict ? 1 : 0; b->min_len = min_len;
     b->lds_cols = max_lds_cols < 0 ? WG_BIM_LDS_COLS : std::min<int32_t>(max_lds_cols, WG_BIM_LDS_COLS);
     const size_t nb = (size_t)n_blocks;
     b->s1.resize(nb); b->s2.resize(nb); b->by_end.resize(nb); b->lo_after.assign(nb + 1, INT64_MAX);
     for (size_t j = 0; j < nb; j++) { b->s1[j] = (int32_t)start_cpg[j]; b->s2[j] = (int32_t)end_cpg[j]; b->by_end[j] = (int32_t)j; }
     std::stable_sort(b->by_end.begin(), b->by_end.end(), [&](int32_t x, int32_t y) { return b->s2[(size_t)x] < b->s2[(size_t)y]; });
     for (size_t p = nb; p-- > 0;) b->lo_after[p] = std::min<int64_t>(b->lo_after[p + 1], std::max<int64_t>(1, (int64_t)b->s1[(size_t)b->by_end[p]] - WG_BIM_CTX));
-    HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
     HIP_TRY(b->bs1.ensure(nb * 4)); HIP_TRY(b->bs2.ensure(nb * 4)); HIP_TRY(b->ids.ensure(nb * 4));
     HIP_TRY(b->meta.ensure(nb * sizeof(wg_bim_meta))); HIP_TRY(b->scr_off.ensure(nb * 8));
     HIP_TRY(b->res_f.ensure(nb * 24)); HIP_TRY(b->res_i.ensure(nb * 24)); HIP_TRY(b->state.ensure(sizeof(wg_bim_state)));
@@ -3192,28 +3199,23 @@ int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* 
 void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b)
 {
     if (!b) return;
-    (void)hipSetDevice(b->device);
-    if (b->st) (void)hipStreamSynchronize(b->st);
-    b->collect();
-    for (DevBuf* d : {&b->bs1, &b->bs2, &b->ids, &b->meta, &b->scr_off, &b->scratch, &b->res_f, &b->res_i, &b->state, &b->text, &b->tile_cnt,
+    b->feed.close();
+    for (DevBuf* d : {&b->bs1, &b->bs2, &b->ids, &b->meta, &b->scr_off, &b->scratch, &b->res_f, &b->res_i, &b->state, &b->tile_cnt,
                       &b->tile_base, &b->pos}) d->release();
     for (auto& t : b->tab) for (DevBuf* d : {&t.start, &t.len, &t.cnt, &t.woff, &t.words}) d->release();
-    b->stage.release(); b->host_state.release(); b->host_meta.release(); b->host_off.release();
-    if (b->st) (void)hipStreamDestroy(b->st);
+    b->host_state.release(); b->host_meta.release(); b->host_off.release();
     delete b;
 }
 
 int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    if (!b || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to bimodal_feed"); return WGBSSEG_E_ARG; }
-    if (n_bytes == 0) return WGBSSEG_OK;
-    if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "bimodal_feed: a chunk must end with a complete line"); return WGBSSEG_E_ARG; }
-    const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;
-    if (gx > 0x7fffffff) { set_err(err, errlen, "bimodal_feed: chunk too large"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(b->device));
+    const int64_t gx = PatFeed::tiles("bimodal", b, text, n_bytes, err, errlen);
+    if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
+    PatFeed& f = b->feed;
+    HIP_TRY(hipSetDevice(f.device));
     int rc = bim_sync_state(b, err, errlen);                     // the previous chunk is parsed and checked
     if (rc != WGBSSEG_OK) return rc;
-    if (b->stop) { b->fed += (unsigned long long)n_bytes; return WGBSSEG_OK; }     // finish() reports the error
+    if (b->stop) { f.fed += (unsigned long long)n_bytes; return WGBSSEG_OK; }     // finish() reports the error
     const wg_bim_state s = *b->hs();
     const size_t ub_lines = (size_t)n_bytes / 6 + 1, ub_words = (size_t)n_bytes / 16 + ub_lines + 1;   // a good line has >= 6 bytes
     rc = bim_reserve(b, (size_t)s.R + ub_lines, (size_t)s.W + ub_words, err, errlen);
@@ -3225,49 +3227,47 @@ int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, 
     rc = bim_retire(b, p1, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     // drop what no pending block can reach, into the other table
-    hipEvent_t e1 = nullptr;
     if (s.R > 0) {
         wgbsseg_bimodal::Table &A = b->tab[b->cur], &B = b->tab[b->cur ^ 1];
         const long long lo = b->lo_after[(size_t)b->pending] == INT64_MAX ? (long long)INT32_MAX + 1 : (long long)b->lo_after[(size_t)b->pending];
-        HIP_TRY(b->span_begin(&e1));
-        hipLaunchKernelGGL(k_bim_drop_find, dim3(1), dim3(1), 0, b->st, A.start.as<int32_t>(), A.woff.as<long long>(), b->state.as<wg_bim_state>(), lo);
+        HIP_TRY(f.span_begin());
+        hipLaunchKernelGGL(k_bim_drop_find, dim3(1), dim3(1), 0, f.st, A.start.as<int32_t>(), A.woff.as<long long>(), b->state.as<wg_bim_state>(), lo);
         const long long big = std::max<long long>(s.R, s.W);
-        hipLaunchKernelGGL(k_bim_drop_copy, dim3((unsigned)((big + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, b->st,
+        hipLaunchKernelGGL(k_bim_drop_copy, dim3((unsigned)((big + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, f.st,
                            A.start.as<int32_t>(), A.len.as<int32_t>(), A.cnt.as<int32_t>(), A.woff.as<long long>(), A.words.as<uint32_t>(),
                            B.start.as<int32_t>(), B.len.as<int32_t>(), B.cnt.as<int32_t>(), B.woff.as<long long>(), B.words.as<uint32_t>(),
                            b->state.as<wg_bim_state>(), (long long)s.R, (long long)s.W);
-        hipLaunchKernelGGL(k_bim_drop_done, dim3(1), dim3(1), 0, b->st, b->state.as<wg_bim_state>());
+        hipLaunchKernelGGL(k_bim_drop_done, dim3(1), dim3(1), 0, f.st, b->state.as<wg_bim_state>());
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e1, b->st));
+        HIP_TRY(f.span_end());
         b->cur ^= 1;
     }
     // this chunk: copy, count, scan, fill, order
-    if (!b->stage.ensure((size_t)n_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
-    memcpy(b->stage.p, text, (size_t)n_bytes);
-    HIP_TRY(b->text.ensure((size_t)n_bytes));
     HIP_TRY(b->tile_cnt.ensure((size_t)gx * 8)); HIP_TRY(b->tile_base.ensure((size_t)gx * 16)); HIP_TRY(b->pos.ensure(ub_lines * 8));
-    HIP_TRY(hipMemcpyAsync(b->text.p, b->stage.p, (size_t)n_bytes, hipMemcpyHostToDevice, b->st));
+    const char* dtext = nullptr;
+    rc = f.stage_chunk(text, n_bytes, &dtext, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     wgbsseg_bimodal::Table& T = b->tab[b->cur];
-    HIP_TRY(b->span_begin(&e1));
-    hipLaunchKernelGGL(k_bim_tile_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, b->st, b->text.as<char>(), n_bytes, b->tile_cnt.as<uint32_t>(),
-                       b->state.as<wg_bim_state>(), b->fed);
-    hipLaunchKernelGGL(k_bim_tile_scan, dim3(1), dim3(WG_BLOCK), 0, b->st, b->tile_cnt.as<uint32_t>(), gx, b->tile_base.as<long long>(),
+    HIP_TRY(f.span_begin());
+    hipLaunchKernelGGL(k_bim_tile_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, b->tile_cnt.as<uint32_t>(),
+                       b->state.as<wg_bim_state>(), f.fed);
+    hipLaunchKernelGGL(k_bim_tile_scan, dim3(1), dim3(WG_BLOCK), 0, f.st, b->tile_cnt.as<uint32_t>(), gx, b->tile_base.as<long long>(),
                        b->state.as<wg_bim_state>());
-    hipLaunchKernelGGL(k_bim_fill, dim3((unsigned)gx), dim3(WG_BLOCK), 0, b->st, b->text.as<char>(), n_bytes, b->tile_base.as<long long>(),
+    hipLaunchKernelGGL(k_bim_fill, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, b->tile_base.as<long long>(),
                        T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(), T.woff.as<long long>(), T.words.as<uint32_t>(),
-                       b->pos.as<long long>(), b->state.as<wg_bim_state>(), b->fed);
-    hipLaunchKernelGGL(k_bim_order, dim3((unsigned)((ub_lines + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, b->st, T.start.as<int32_t>(),
+                       b->pos.as<long long>(), b->state.as<wg_bim_state>(), f.fed);
+    hipLaunchKernelGGL(k_bim_order, dim3((unsigned)((ub_lines + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, f.st, T.start.as<int32_t>(),
                        b->pos.as<long long>(), b->state.as<wg_bim_state>(), s.last_start, (int64_t)ub_lines);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1, b->st));
-    b->fed += (unsigned long long)n_bytes;
+    HIP_TRY(f.span_end());
+    HIP_TRY(f.chunk_queued(n_bytes));
     return WGBSSEG_OK;
 }
 
 int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char* err, size_t errlen)
 {
     if (!b || !ll || !counts) { set_err(err, errlen, "bad arguments to bimodal_finish"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipSetDevice(b->feed.device));
     int rc = bim_sync_state(b, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     if (!b->stop) {
@@ -3277,18 +3277,12 @@ int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char
         if (rc != WGBSSEG_OK) return rc;
     }
     const wg_bim_state* s = b->hs();
-    if (s->bad != ~0ULL) {
-        set_err(err, errlen, "test_bimodal: invalid line at byte offset %llu of the input (too few columns, or a site / count that is not a number)", s->bad);
-        return WGBSSEG_E_ARG;
-    }
+    if (pat_refused(PatRefusal::bad_line, s->bad, "test_bimodal:", err, errlen)) return WGBSSEG_E_ARG;
     if (s->neg != ~0ULL) {
         set_err(err, errlen, "test_bimodal: negative read count at byte offset %llu of the input", s->neg);
         return WGBSSEG_E_ARG;
     }
-    if (s->desc != ~0ULL) {
-        set_err(err, errlen, "test_bimodal: the pat file is not sorted: the read at byte offset %llu of the input starts before the read before it", s->desc);
-        return WGBSSEG_E_ARG;
-    }
+    if (pat_refused(PatRefusal::unsorted, s->desc, "test_bimodal:", err, errlen)) return WGBSSEG_E_ARG;
     if (s->em_cap) {
         set_err(err, errlen, "test_bimodal: the EM of block %llu (row of the blocks) did not settle within %d iterations", s->em_cap, WG_BIM_MAX_ITERS);
         return WGBSSEG_E_CAPACITY;
@@ -3300,10 +3294,7 @@ int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char
 
 double wgbsseg_bimodal_kernel_ms(wgbsseg_bimodal* b)
 {
-    if (!b) return -1.0;
-    if (hipSetDevice(b->device) != hipSuccess || hipStreamSynchronize(b->st) != hipSuccess) return -1.0;
-    b->collect();
-    return b->kernel_ms;
+    return b ? b->feed.kernel_ms() : -1.0;
 }
 
 int wgbsseg_get_timings(const wgbsseg_ctx* c, wgbsseg_timings* out)

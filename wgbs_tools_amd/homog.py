@@ -46,7 +46,7 @@ import numpy as np
 from .beta_to_blocks import load_blocks_file
 from .convert import delete_or_skip
 from .genome import IllegalArgumentError
-from .pat2beta import pat_chunks, splitextgz
+from .pat2beta import feed_pat, splitextgz
 from .cliutil import default_threads
 
 
@@ -147,18 +147,8 @@ def count_blocks(pat, blocks, edges, args, timings=None):
     from . import _lib
     order = np.lexsort((blocks.endCpG, blocks.startCpG))
     t = timings if timings is not None else {}
-    t_inflate = t_feed = 0.0
     with _lib.Homog(blocks.startCpG[order], blocks.endCpG[order], edges, args.rlen, args.inclusive, device=getattr(args, 'device', 0)) as h:
-        it = iter(pat_chunks(pat))
-        while True:
-            t0 = time.perf_counter()
-            chunk = next(it, None)
-            t1 = time.perf_counter()
-            t_inflate += t1 - t0
-            if chunk is None:
-                break
-            h.feed(chunk)
-            t_feed += time.perf_counter() - t1
+        feed_pat(h, pat, t)
         t0 = time.perf_counter()
         try:
             counts = h.finish()
@@ -166,7 +156,6 @@ def count_blocks(pat, blocks, edges, args, timings=None):
             raise IllegalArgumentError(f'{pat}: {e.msg}')
         t['finish_s'] = time.perf_counter() - t0
         t['kernel_ms'] = h.kernel_ms()
-    t['inflate_s'], t['feed_s'] = t_inflate, t_feed
     counts = counts.astype(np.int64)
     rank = np.argsort(blocks.startCpG, kind='stable')            # homog.py:113-118: the row of sorted position r goes to rank[r]
     inv = np.argsort(rank, kind='stable')

@@ -37,7 +37,7 @@ import numpy as np
 
 from .cliutil import add_threads_option, add_where_options, require_file
 from .genome import GenomeRefPaths, GenomicRegion, IllegalArgumentError, eprint
-from .pat2beta import pat_chunks
+from .pat2beta import feed_pat
 
 
 def _stats():
@@ -52,18 +52,8 @@ def run_blocks(pat, starts, ends, strict, min_len, device=0, timings=None, max_l
     """the device's raw numbers per block: (float64 [n][3] ll0, ll_em, sum of n_per_col; int64 [n][3] columns, rows, iterations)"""
     from . import _lib
     t = timings if timings is not None else {}
-    t_inflate = t_feed = 0.0
     with _lib.Bimodal(starts, ends, strict, min_len, device=device, max_lds_cols=max_lds_cols) as b:
-        it = iter(pat_chunks(pat))
-        while True:
-            t0 = time.perf_counter()
-            chunk = next(it, None)
-            t1 = time.perf_counter()
-            t_inflate += t1 - t0
-            if chunk is None:
-                break
-            b.feed(chunk)
-            t_feed += time.perf_counter() - t1
+        feed_pat(b, pat, t)
         t0 = time.perf_counter()
         try:
             ll, cnt = b.finish()
@@ -71,7 +61,6 @@ def run_blocks(pat, starts, ends, strict, min_len, device=0, timings=None, max_l
             raise IllegalArgumentError(f'{pat}: {e.msg}')
         t['finish_s'] = time.perf_counter() - t0
         t['kernel_ms'] = b.kernel_ms()
-    t['inflate_s'], t['feed_s'] = t_inflate, t_feed
     return ll, cnt
 
 
