@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — CpG-sites/sec segmented on synthetic hg19-shaped betas (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--samples 32] [--sites 28217448] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--samples 32] [--sites 28217448] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one whole `segment` job over the resident beta bytes: scan/validate pass, window extents, block scoring,
@@ -17,6 +17,11 @@ N > 1 under torch.distributed.run (one process per GPU): the product's multi-pro
 N > 1 WITHOUT the launcher: one process drives N GPUs through a share group (`wgbstools segment --gpus N`).
 Total work is fixed as N grows => "scaling": "strong".
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: its figures all come from the timed
+steps themselves.  Everything that takes runs of its own (the scan pass alone, and every item below from `roofline_scan_carries`
+on) runs only with --full; there the options --block-sums, --scan-carries, --matrix, --extras, --e2e and --cpu-seconds still
+switch single items off.
+
 The JSON line carries
   roofline        the dominant kernel, k_cost (block log-likelihoods: ~85 % of a step).  Neither HBM- nor MFMA-bound: integer
                   scan + scalar fp32/fp64 cost on the vector ALUs.  achieved = algorithmic flops (~55
@@ -24,7 +29,9 @@ The JSON line carries
                   events on the kernel's stream inside the timed steps), against the 78.6 TFLOP/s vector-fp64 peak; `issue` gives
                   the instruction-issue bound of the kernel's actual instruction mix (profiles/*cost_isa_mix.json x the guide's
                   cycle table).
-  roofline_scan   the HBM-bound scan pass (k_validate / k_scan): algorithmic bytes = 2 x samples x sites per launch.
+  roofline_scan   the HBM-bound scan pass (k_validate / k_scan): algorithmic bytes = 2 x samples x sites per launch.  Its
+                  duration is the launch's inside the timed steps, or with --full (one GPU) that of 20 launches of the kernel alone.
+  roofline_scan_carries  the prefix-sum pass with carries forced (k_scan) on the workload's chunk grid.
   block_sums      the block reduction (beta_to_blocks / beta_to_table kernel) over the blocks just found.
   matrix          the same step at the other sample counts of the metric (x8, x200, x512), a few steps each.
   cpu_baseline    the reference's own `segmentor` (oracle/_ref) on this host: 1 core, one process per physical core, one per
@@ -72,12 +79,14 @@ def parse():
     ap.add_argument('--max-bp', type=int, default=2000)
     ap.add_argument('--pcount', type=float, default=15.0)
     ap.add_argument('--islands', action='store_true', help='add CpG islands to the synthetic loci (windows of several hundred sites; not the BASELINE workload)')
-    ap.add_argument('--block-sums', type=int, default=1, help='also time the block reduction over the blocks just found (0: skip)')
-    ap.add_argument('--scan-carries', type=int, default=1, help='also time the prefix-sum pass with carries (k_scan) on the chunk grid (0: skip)')
-    ap.add_argument('--matrix', type=int, default=1, help='also run a few steps at x8, x200 and x512 (1 GPU only; 0: skip)')
-    ap.add_argument('--cpu-seconds', type=float, default=25.0, help='wall-time budget of the CPU baseline runs (0: skip)')
-    ap.add_argument('--extras', type=int, default=1, help='also time convert, pat2beta and the find_markers statistics (1 GPU only; 0: skip)')
-    ap.add_argument('--e2e', type=int, default=1, help='also time the CLI end to end on page-cached files (1 GPU only; 0: skip)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure and check everything beyond the headline figure: the scan pass alone and the items below')
+    ap.add_argument('--block-sums', type=int, default=1, help='with --full: also time the block reduction over the blocks just found (0: skip)')
+    ap.add_argument('--scan-carries', type=int, default=1, help='with --full: also time the prefix-sum pass with carries (k_scan) on the chunk grid (0: skip)')
+    ap.add_argument('--matrix', type=int, default=1, help='with --full: also run a few steps at x8, x200 and x512 (1 GPU only; 0: skip)')
+    ap.add_argument('--cpu-seconds', type=float, default=25.0, help='with --full: wall-time budget of the CPU baseline runs (0: skip)')
+    ap.add_argument('--extras', type=int, default=1, help='with --full: also time convert, pat2beta and the find_markers statistics (1 GPU only; 0: skip)')
+    ap.add_argument('--e2e', type=int, default=1, help='with --full: also time the CLI end to end on page-cached files (1 GPU only; 0: skip)')
     ap.add_argument('--oversubscribe', action='store_true',
                     help='dry runs of the N > 1 forms on fewer GPUs than shares / ranks (several shares per device): without this flag such a launch is refused')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
@@ -85,6 +94,9 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:
+        args.block_sums = args.scan_carries = args.matrix = args.extras = args.e2e = 0
+        args.cpu_seconds = 0.0
     return args
 
 
@@ -831,13 +843,14 @@ def main():
             traffic_note = ('traffic (bytes per launch) = 2 x FETCH_SIZE + WRITE_SIZE from profiles/%s (rocprofv3 PMC passes of this command on this '
                             'source state; gfx950 FETCH_SIZE x2 correction)' % tr['_file'])
         # Round 6: inside the step the scan pass no longer has the chip to itself — it starts with the batch on the lowest-priority stream, beside the
-        # windows pass, the tile plan and the first scoring tiles — so its duration THERE says how well it hides, not how fast the kernel reads.  The
-        # kernel's own rate (the roofline figure) is timed like `roofline_scan_carries`: 20 back-to-back launches on this workload's chunk grid.
+        # windows pass, the tile plan and the first scoring tiles — so its duration THERE says how well it hides, not how fast the kernel reads.  With
+        # --full the kernel's own rate (the roofline figure) is timed like `roofline_scan_carries`: 20 back-to-back launches on this workload's chunk grid.
         scan_in_step = {'avg_launch_ms': main_ms, 'GB/s': scan_gbs, 'frac_of_hbm_peak': scan_gbs / HBM_PEAK_GBS,
                         'note': 'HIP events around the launch INSIDE the timed steps, where it runs on the lowest-priority stream beside the windows pass, the tile plan and the '
                                 'first scoring tiles (round 6: scoring begins 0.3 ms into the batch instead of 0.7)'}
-        scan_alone_note = 'rank 0 / share 0, HIP events on the kernel stream inside the timed steps; '
-        if seg is not None and not multi:
+        alone = seg is not None and not multi       # one GPU: the kernel alone can be timed
+        scan_alone_note = 'rank 0 / share 0, HIP events on the kernel stream inside the timed steps%s; ' % (' (the kernel alone: --full)' if alone and not args.full else '')
+        if args.full and alone:
             grid_s = parallel.chunk_grid(regions, args.chunk)
             a_ms, a_bytes = seg.scan_only(np.array([s0 - 1 for _, s0, _ in grid_s], dtype=np.int64), np.array([e0 - s0 for _, s0, e0 in grid_s], dtype=np.int32),
                                           repeat=20, want_carry=stats_wide)[:2]

@@ -5,7 +5,7 @@
 set -u
 O=gpurun_out/${1:-check}; mkdir -p $O
 K=${2:-}
-B="--matrix 0 --cpu-seconds 0 --e2e 0 --extras 0 --block-sums 0 --scan-carries 0"
+B="--full --matrix 0 --cpu-seconds 0 --e2e 0 --extras 0 --block-sums 0 --scan-carries 0"
 if [ -n "$K" ]; then
   timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_fuzz.py tests/test_gpu_driver.py tests/test_gpu_segmentor_bin.py tests/test_gpu_integration_stub.py -x -q -m gpu -k "$K" > $O/pytest.log 2>&1
 else

@@ -3,7 +3,7 @@
 # behind the windows pass (1), or behind the tile plan, beside the first scoring tiles only (2): time lines + bench lines, three alternating repetitions.
 set -u
 O=gpurun_out/${1:-front_ab}; mkdir -p $O
-B="--matrix 0 --cpu-seconds 0 --e2e 0 --extras 0 --block-sums 0 --scan-carries 0"
+B="--full --matrix 0 --cpu-seconds 0 --e2e 0 --extras 0 --block-sums 0 --scan-carries 0"
 for rep in 1 2 3; do
   for m in 0 1 2; do
     for a in "" "--samples 8" "--samples 200" "--sites 3527181"; do

@@ -4,7 +4,7 @@
 set -u
 R=${R:-r06}
 REPO=$PWD; O=$REPO/gpurun_out/rows; mkdir -p $O
-B="--cpu-seconds 0 --e2e 0 --extras 0 --matrix 0 --block-sums 0 --scan-carries 0"
+B="--full --cpu-seconds 0 --e2e 0 --extras 0 --matrix 0 --block-sums 0 --scan-carries 0"
 cd /tmp; export TMPDIR=/tmp
 run() {  # name, bench args
   local name=$1; shift
