@@ -734,17 +734,18 @@ def test_16_medium_tiles_match_oracle_and_wide_tiles(monkeypatch, n_samples, cov
         slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
     chunks = [(0, 3000), (1999, 1203), (2005, 700), (4103, 1531), (8000, 1000), (8737, 263), (5, 253)]
     starts, lens = [c[0] for c in chunks], [c[1] for c in chunks]
-    with _lib.Segmenter(0) as sg:
-        sg.set_betas(slices)
-        sg.set_loci(loci)
-        for pcount, max_cpg in [(15.0, 252), (15.0, 253), (15.0, 61), (1.0, 130), (0.25, 200), (0.0, 252), (7.77, 189), (15.0, 1000)]:
-            want = oracle.segment_chunks(slices, loci, starts, lens, pcount, max_cpg, 10**6, threads=os.cpu_count() or 1)
-            for wm in ('252', '0', '124'):
-                monkeypatch.setenv('WGBSSEG_MEDIUM_WMAX', wm)
+    params = [(15.0, 252), (15.0, 253), (15.0, 61), (1.0, 130), (0.25, 200), (0.0, 252), (7.77, 189), (15.0, 1000)]
+    wants = [oracle.segment_chunks(slices, loci, starts, lens, pcount, max_cpg, 10**6, threads=os.cpu_count() or 1) for pcount, max_cpg in params]
+    for wm in ('252', '0', '124'):
+        monkeypatch.setenv('WGBSSEG_MEDIUM_WMAX', wm)                      # (read when a context is created)
+        with _lib.Segmenter(0) as sg:
+            sg.set_betas(slices)
+            sg.set_loci(loci)
+            for (pcount, max_cpg), want in zip(params, wants):
                 got = sg.segment_chunks(starts, lens, pcount, max_cpg, 10**6)
                 for c, (a, b) in enumerate(zip(got, want)):
                     assert a.tolist() == b.tolist(), 'pcount %r max_cpg %d medium<=%s chunk [%d,+%d): %s' % (pcount, max_cpg, wm, starts[c], lens[c], _first_diff(a, b))
-        monkeypatch.delenv('WGBSSEG_MEDIUM_WMAX')
+    monkeypatch.delenv('WGBSSEG_MEDIUM_WMAX')
 
 
 def test_17_lean_step_in_the_narrow_batches_of_a_wide_job(monkeypatch):
@@ -769,20 +770,22 @@ def test_17_lean_step_in_the_narrow_batches_of_a_wide_job(monkeypatch):
         slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
     chunks = [(0, 9000), (37, 9003), (4096 + 32, 8000), (9000, 11000), (14000, 3000), (123, 700)]
     starts, lens = [c[0] for c in chunks], [c[1] for c in chunks]
-    with _lib.Segmenter(0) as sg:
-        sg.set_betas(slices)
-        sg.set_loci(loci)
-        for pcount, max_cpg, max_bp in [(15.0, 1000, 2000), (15.0, 200, 2000), (1.0, 100, 1200), (0.5, 1000, 900), (15.0, 65, 2000)]:
-            want = oracle.segment_chunks(slices, loci, starts, lens, pcount, max_cpg, max_bp, threads=os.cpu_count() or 1)
-            assert max(int(w.size) for w in want) > 10
-            for wlean in ('1', '0'):
-                monkeypatch.setenv('WGBSSEG_DP_WLEAN', wlean)
+    params = [(15.0, 1000, 2000), (15.0, 200, 2000), (1.0, 100, 1200), (0.5, 1000, 900), (15.0, 65, 2000)]
+    wants = [oracle.segment_chunks(slices, loci, starts, lens, pcount, max_cpg, max_bp, threads=os.cpu_count() or 1) for pcount, max_cpg, max_bp in params]
+    for want in wants:
+        assert max(int(w.size) for w in want) > 10
+    for wlean in ('1', '0'):
+        monkeypatch.setenv('WGBSSEG_DP_WLEAN', wlean)                       # (read when a context is created)
+        with _lib.Segmenter(0) as sg:
+            sg.set_betas(slices)
+            sg.set_loci(loci)
+            for (pcount, max_cpg, max_bp), want in zip(params, wants):
                 got = sg.segment_chunks(starts, lens, pcount, max_cpg, max_bp)
                 if wlean == '1':
                     assert sg.timings()['max_window'] > 64 or max_cpg <= 65, 'the case must be a wide job'
                 for c, (a, b) in enumerate(zip(got, want)):
                     assert a.tolist() == b.tolist(), 'pcount %r max_cpg %d max_bp %d lean %s chunk [%d,+%d): %s' % (pcount, max_cpg, max_bp, wlean, starts[c], lens[c], _first_diff(a, b))
-        monkeypatch.delenv('WGBSSEG_DP_WLEAN')
+    monkeypatch.delenv('WGBSSEG_DP_WLEAN')
 
 
 # ---------------------------------------------------------------------------------------------------------

@@ -85,6 +85,8 @@ void set_err(char* err, size_t errlen, const char* fmt, ...)
 hipError_t set_kernel_attributes();      // defined below, next to the kernel launchers
 inline int ceil_pow2(int v) { int r = 1; while (r < v) r <<= 1; return r; }
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+// a switch of the environment, as an integer (`def` when it is not set): read when a context is created
+inline int env_int(const char* name, int def) { const char* e = getenv(name); return e ? atoi(e) : def; }
 
 }  // namespace
 
@@ -116,6 +118,10 @@ struct PinnedBuf {          // grow-only page-locked host buffer (fast, truly as
 #define WG_MAX_CPUS 8192
 struct NearCpus { std::vector<unsigned long> bits; bool valid = false; };      // affinity mask of the CPUs next to a device
 
+// The events of a batch: stream A: it begins, its tables are up, windows done, statistics copied, tile plan done; the scan stream: k_validate, k_scan
+// (jobs with wide tiles only), the pass is done (its verdict may be copied); stream B: traceback + border lists, results on the host.
+enum BatchEvent { EV_BEGIN, EV_WINDOWS, EV_SCAN_END, EV_PLAN, EV_TRACE0, EV_TRACE1, EV_HOME, EV_STATS, EV_VALIDATE0, EV_VALIDATE1, EV_SCAN0, EV_SCAN1, EV_UPLOADED, EV_COUNT };
+
 struct wgbsseg_ctx {
     int device = 0;
     NearCpus near_cpus;          // the upload threads run there (worked out once, at create)
@@ -132,10 +138,10 @@ struct wgbsseg_ctx {
     int64_t n_loci = 0;
     // scratch
     DevBuf chunks, wtile, carry, W16, cum32, back16, chunk_pairs, status, tile_tot, tile_base, tile_chunk;
-    DevBuf plan_cbase, plan_cum0, plan_tbase, plan_pairs, plan_tiles, plan_cnt, tilesA, tilesB, tilesM, umax16;
+    DevBuf plan_cbase, plan_cum0, plan_tbase, plan_pairs, plan_tiles, plan_cnt, umax16;
     std::vector<PinnedBuf> pinned;
     std::vector<PinnedBuf> up_stage;   // two page-locked staging pieces per upload thread (set_betas_host)
-    DevBuf cost[3], stage_ctr, dpstate, tmp_borders, nb, boff, out_borders[2], edges, dbg_a, dbg_b, dbg_c, lookup;
+    DevBuf tiles[3], cost[3], stage_ctr, dpstate, tmp_borders, nb, boff, out_borders[2], edges, dbg_a, dbg_b, dbg_c, lookup;
     int out_par = 0;              // which of the two result buffers the batch in flight writes: the lists of the previous batch may still be on their way home (below)
     // early delivery (segment_regions' first batch): k_copy_out (on the scan stream) writes the chunks' border lists into the page-locked result ...
     hipEvent_t evS = nullptr;     // the scan stream's last command of the batch in flight (the copy of its verdict)
@@ -145,9 +151,7 @@ struct wgbsseg_ctx {
     std::vector<wg_d2> h_lookup;   // host copy of the k-scaled log tables of the call in flight (source of an async upload)
     float lookup_pc = -1.0f;       // what the device copy `lookup` was built for: pseudo count and exponent rows of the narrow / wide / medium class
     int lookup_rows[3] = {-1, -1, -1};
-    // events
-    hipEvent_t ev[13] = {};  // [0] batch begins, [1] windows done, [7] statistics copied, [3] plan done, [4]-[6] traceback / borders; the scan pass (stream C): [12] inputs uploaded,
-                             // [8]..[9] k_validate, [10]..[11] k_scan (jobs with wide tiles only), [2] its verdict may be copied
+    hipEvent_t ev[EV_COUNT] = {};   // a batch's events (BatchEvent); the context's other calls time themselves between ev[0] and ev[1]
     PinnedBuf h_status;      // page-locked landing area of the status words: D2H copies that really are asynchronous
     PinnedBuf h_job, h_pieces, h_sb;   // ... the staging areas of a job's tables on their way up (chunk table, window tiles, cleared status | k_validate's pieces)
     PinnedBuf h_out;         // ... and of a batch's CSR offsets (a small batch: of its border lists too)
@@ -186,6 +190,11 @@ struct wgbsseg_ctx {
     bool divs_enabled = true;  // WGBSSEG_DIV_SHORT=0: always the 8-instruction core
     bool bs_general = false;   // WGBSSEG_BLOCK_SUMS_GENERAL=1: never the streaming block-sums kernel
     int64_t scan_piece_sites = 4096;    // WGBSSEG_SCAN_PIECE_SITES: sites per wave task of k_validate (multiple of 1024)
+    int medium_wmax = WG_MEDIUM_WMAX;   // WGBSSEG_MEDIUM_WMAX: widest window of a medium tile (0: no medium class)
+    bool dp_wlean = true;      // WGBSSEG_DP_WLEAN=0: the narrow batches of a wide job on k_dp's generic step
+    bool early = true;         // WGBSSEG_NO_EARLY=1: the first batch of a region-level call delivers everything at once
+    bool speculate = true;     // WGBSSEG_NO_SPECULATION=1: junction patches only when the reference would ask for them
+    bool batch_marks = false;  // WGBSSEG_PROFILE >= 2: every batch's device time line and host clock on stderr
 };
 
 namespace {
@@ -320,34 +329,32 @@ int create_ctx(int device, bool scan_low_priority, wgbsseg_ctx** out, char* err,
         // ... and the scan stream ranks below it: k_validate starts with the batch, beside the windows pass, and must not take the wavefront
         // slots of the kernels that are on the way to the first scoring tile (measured, hg19 x 32: scoring begins 0.36 ms into the batch
         // instead of 0.46, profiles/r06_front_ab.txt)
-        const char* sp = getenv("WGBSSEG_SCAN_PRIO");          // (A/B) 0: the scan stream at the scoring stream's priority
-        if (scan_low_priority && !(sp && atoi(sp) == 0)) HIP_TRY(hipStreamCreateWithPriority(&c->sC, hipStreamNonBlocking, lo_p));
+        HIP_TRY(scan_low_priority ? hipStreamCreateWithPriority(&c->sC, hipStreamNonBlocking, lo_p) : hipStreamCreateWithFlags(&c->sC, hipStreamNonBlocking));
     }
-    if (!c->sC) HIP_TRY(hipStreamCreateWithFlags(&c->sC, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&c->sA2, hipStreamNonBlocking));
     HIP_TRY(hipEventCreateWithFlags(&c->evD, hipEventDisableTiming));
     HIP_TRY(hipEventCreateWithFlags(&c->evS, hipEventDisableTiming));
     for (auto& v : c->ev) HIP_TRY(hipEventCreate(&v));
     const char* b = getenv("WGBSSEG_COST_BUDGET_MB");
     c->cost_budget_bytes = (b && atoll(b) > 0 ? atoll(b) : 6144LL) << 20;
-    const char* fs = getenv("WGBSSEG_FORCE_STAGES");
-    c->force_stages = fs ? atoi(fs) : 0;
+    c->force_stages = env_int("WGBSSEG_FORCE_STAGES", 0);
     { const char* e = getenv("WGBSSEG_STAGE_GATE"); if (e) c->stage_gate = std::max(0, atoi(e)); }
     { const char* e = getenv("WGBSSEG_STAGE_GATE_SHARED"); c->stage_gate_shared = e && atoi(e) != 0; }
     { const char* e = getenv("WGBSSEG_STAGE_GATE_WIDE_EVALS"); if (e) c->stage_gate_wide_evals = atof(e); }
     { const char* e = getenv("WGBSSEG_STAGE_MIN_EVALS"); if (e) c->stage_min_evals_per_step = atof(e); }
     { const char* e = getenv("WGBSSEG_LAST_STAGE_PCT"); if (e) c->last_stage_pct = std::min(800, std::max(5, atoi(e))); }      // (A/B, tests; default: chosen per job)
     { const char* e = getenv("WGBSSEG_DP_MODE"); c->force_dp_mode = e ? std::min(2, std::max(0, atoi(e))) : 0; }
-    const char* fn = getenv("WGBSSEG_NS");
-    c->force_ns = fn ? atoi(fn) : 0;
-    const char* ft = getenv("WGBSSEG_TI");
-    c->force_ti = ft ? atoi(ft) : 0;
-    const char* bg = getenv("WGBSSEG_BLOCK_SUMS_GENERAL");
-    if (bg) c->bs_general = atoi(bg) != 0;
-    const char* dv = getenv("WGBSSEG_DIV_SHORT");
-    if (dv) c->divs_enabled = atoi(dv) != 0;
-    const char* sp = getenv("WGBSSEG_SCAN_PIECE_SITES");
-    if (sp && atoi(sp) >= 1024) c->scan_piece_sites = (int64_t)(atoi(sp) & ~1023);
+    c->force_ns = env_int("WGBSSEG_NS", 0);
+    c->force_ti = env_int("WGBSSEG_TI", 0);
+    c->bs_general = env_int("WGBSSEG_BLOCK_SUMS_GENERAL", 0) != 0;
+    c->divs_enabled = env_int("WGBSSEG_DIV_SHORT", 1) != 0;
+    { const int sp = env_int("WGBSSEG_SCAN_PIECE_SITES", 0); if (sp >= 1024) c->scan_piece_sites = (int64_t)(sp & ~1023); }
+    const int wm = std::max(0, std::min(WG_MEDIUM_WMAX, env_int("WGBSSEG_MEDIUM_WMAX", WG_MEDIUM_WMAX)));
+    c->medium_wmax = wm > WG_NARROW_WMAX ? wm : 0;
+    c->dp_wlean = env_int("WGBSSEG_DP_WLEAN", 1) != 0;
+    c->early = env_int("WGBSSEG_NO_EARLY", 0) == 0;
+    c->speculate = env_int("WGBSSEG_NO_SPECULATION", 0) == 0;
+    c->batch_marks = env_int("WGBSSEG_PROFILE", 0) >= 2;
     g_live_ctx[device & 63].fetch_add(1, std::memory_order_relaxed);
     c->counted_live = true;
     *out = c;
@@ -364,7 +371,7 @@ void wgbsseg_destroy(wgbsseg_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     DevBuf* all[] = {&c->betas_own, &c->loci_own, &c->chunks, &c->wtile, &c->carry, &c->W16, &c->cum32, &c->back16, &c->chunk_pairs, &c->tile_tot, &c->tile_base, &c->tile_chunk,
-                     &c->status, &c->plan_cbase, &c->plan_cum0, &c->plan_tbase, &c->plan_pairs, &c->plan_tiles, &c->plan_cnt, &c->tilesA, &c->tilesB, &c->tilesM, &c->umax16,
+                     &c->status, &c->plan_cbase, &c->plan_cum0, &c->plan_tbase, &c->plan_pairs, &c->plan_tiles, &c->plan_cnt, &c->tiles[0], &c->tiles[1], &c->tiles[2], &c->umax16,
                      &c->cost[0], &c->cost[1], &c->cost[2], &c->stage_ctr, &c->dpstate, &c->tmp_borders, &c->nb, &c->boff, &c->out_borders[0], &c->out_borders[1], &c->edges,
                      &c->dbg_a, &c->dbg_b, &c->dbg_c, &c->lookup, &c->scan_pieces, &c->divcheck, &c->plan_sb, &c->bs_desc};
     for (auto* b : all) b->release();
@@ -636,16 +643,22 @@ hipError_t launch_cost(const JobView& v, const StageView& sv, const CostArgs& a,
     return hipGetLastError();
 }
 
-// narrow tiles: TI start sites (64 / 32 / 16); wide tiles: WG_WIDE_TS start sites x WG_WIDE_TK end sites
+// k_cost of a tile class: 0 narrow tiles, TI start sites (128 / 64 / 32 / 16); 1 wide tiles, WG_WIDE_TS start sites x WG_WIDE_TK end sites;
+// 2 medium tiles, WG_MEDIUM_TS start sites.  FAST = wg_term_mode of the pseudo count, or 3: mode 2 with the short division core
 template <int FAST>
-hipError_t launch_cost_ti(int TI, bool wide, const JobView& v, const StageView& sv, const CostArgs& a, const TileDesc* td, int64_t tiles, double* cost, size_t lds, hipStream_t s)
+hipError_t launch_cost_fast(int cls, int TI, const JobView& v, const StageView& sv, const CostArgs& a, const TileDesc* td, int64_t tiles, double* cost, size_t lds, hipStream_t s)
 {
-    if (TI < 0) return launch_cost<WG_MEDIUM_TS, FAST, 2>(v, sv, a, td, tiles, cost, lds, s);                     // medium tiles (TI = -1)
-    if (wide) return launch_cost<WG_WIDE_TS, FAST == 3 ? 2 : FAST, 1>(v, sv, a, td, tiles, cost, lds, s);      // (the short division is a form of the tiles with few operand pairs)
+    if (cls == 2) return launch_cost<WG_MEDIUM_TS, FAST, 2>(v, sv, a, td, tiles, cost, lds, s);
+    if (cls == 1) return launch_cost<WG_WIDE_TS, FAST == 3 ? 2 : FAST, 1>(v, sv, a, td, tiles, cost, lds, s);      // (the short division is a form of the tiles with few operand pairs)
     if (TI == 128) return launch_cost<128, FAST, 0>(v, sv, a, td, tiles, cost, lds, s);
     if (TI == 64) return launch_cost<64, FAST, 0>(v, sv, a, td, tiles, cost, lds, s);
     if (TI == 32) return launch_cost<32, FAST, 0>(v, sv, a, td, tiles, cost, lds, s);
     return launch_cost<16, FAST, 0>(v, sv, a, td, tiles, cost, lds, s);
+}
+hipError_t launch_cost_class(int cls, int fast, int TI, const JobView& v, const StageView& sv, const CostArgs& a, const TileDesc* td, int64_t tiles, double* cost, size_t lds, hipStream_t s)
+{
+    return fast == 3 ? launch_cost_fast<3>(cls, TI, v, sv, a, td, tiles, cost, lds, s) : fast == 2 ? launch_cost_fast<2>(cls, TI, v, sv, a, td, tiles, cost, lds, s)
+         : fast == 1 ? launch_cost_fast<1>(cls, TI, v, sv, a, td, tiles, cost, lds, s) : launch_cost_fast<0>(cls, TI, v, sv, a, td, tiles, cost, lds, s);
 }
 
 // Kernels that ask for more than 64 KB of dynamic LDS need the attribute on EVERY device they run on: set once per
@@ -685,13 +698,6 @@ void grow_events(std::vector<hipEvent_t>& v, size_t n)
     while (v.size() < n) { hipEvent_t e; (void)hipEventCreate(&e); v.push_back(e); }
 }
 
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 typedef std::function<int32_t*(int64_t)> BorderAlloc;       // total border count -> destination (NULL: too small)
 
 // Early delivery of a batch's result (the first batch of a region-level call; the destination must be page-locked, i.e. device-visible):
@@ -712,9 +718,6 @@ int wait_pending_output(wgbsseg_ctx* c, char* err, size_t errlen)
     HIP_TRY(hipEventSynchronize(c->evD));
     return WGBSSEG_OK;
 }
-
-int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32_t* chunk_len, int64_t n_chunks,
-                        const wgbsseg_params* P, const BorderAlloc& alloc, int64_t* borders_off, char* err, size_t errlen, bool allow_plain = true, EarlyOut* early = nullptr);
 
 // One chunk whose loci are not ascending, the reference's loops as written (csrc/plain_dp.h): ascending borders incl. 0 and len.
 int plain_segment_chunk(wgbsseg_ctx* c, int64_t start0, int32_t n, const wgbsseg_params* P, std::vector<int32_t>& borders, char* err, size_t errlen)
@@ -770,58 +773,236 @@ int plain_segment_chunk(wgbsseg_ctx* c, int64_t start0, int32_t n, const wgbsseg
     return WGBSSEG_OK;
 }
 
-// A batch in which k_window found chunks with non-ascending loci: those chunks take the plain path, the others the batch path (again,
-// without them), and the border lists are put back in the caller's order.
-int segment_chunks_with_disorder(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32_t* chunk_len, int64_t n_chunks, const wgbsseg_params* P,
-                                 const wgbsseg_params* Peff, const Job& job, const BorderAlloc& alloc, int64_t* borders_off, char* err, size_t errlen)
+// ---- one batch: a plan decided on the host, then the phases that launch it ------------------------------------------------
+
+// How a batch is tiled, staged and recurred, decided on the host from the window statistics (plan_tiles, plan_stages: no HIP call).  Tile classes: 0 narrow, 1 wide, 2 medium.
+struct BatchPlan {
+    int Wmax = 0;                  // the job's widest window
+    int WA = 0;                    // widest window of a narrow tile: min(Wmax, WG_NARROW_WMAX)
+    int WMED = 0;                  // widest window of a medium tile (0: no medium class)
+    int term_mode[3] = {};         // per class: the form of the likelihood term (wg_term_mode)
+    int rows[3] = {};              // per class: exponent rows of the k-scaled lookup tables (term mode 2 only)
+    int TI = 64;                   // start sites of a narrow tile
+    int NS[3] = {1, 1, 1};         // per class: samples per LDS group
+    size_t lds[3] = {};            // per class: dynamic LDS of k_cost
+    int n_stages = 1;
+    bool gated = false;            // the stages alternate between the two scoring streams behind k_stage_gate
+    int last_pct = 100;            // length of the last stage in percent of the others'
+    const int32_t* sb = nullptr;   // [n_stages + 1] stage bounds (held by the context: the source of an async upload)
+    bool all_narrow = false;       // no window beyond the narrow tiles': the tile and pair counts below are the host's own
+    std::vector<int64_t> stage_pairs, stage_tiles;   // per stage: scored blocks; tiles per class at [3 * stage + class] (read back from k_stage_plan unless all narrow)
+    int dp_mode = 0;               // k_dp: 0 64-step batches, 1 32-step batches, 2 the same with 15 worker waves (deep windows)
+    int ringN = 0; int64_t state_stride = 0;   // k_dp's ring of pending maxima (0: none) and its state per chunk, in doubles
+    int nbuf = 1;                  // scored-block buffers
+};
+
+// dynamic LDS of a k_cost tile of class cls with ti start sites and ns samples per LDS group
+size_t cost_lds(const BatchPlan& p, int ti, int cls, int ns)
 {
-    DevBuf flags;
-    struct Free { DevBuf& a; ~Free() { a.release(); } } fr{flags};
-    HIP_TRY(flags.ensure((size_t)n_chunks * 4));
-    HIP_TRY(hipMemsetAsync(flags.p, 0, (size_t)n_chunks * 4, c->sA));
-    hipLaunchKernelGGL(k_find_disorder, dim3((unsigned)n_chunks), dim3(WG_BLOCK), 0, c->sA, job.v, flags.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> hf((size_t)n_chunks);
-    HIP_TRY(hipMemcpyAsync(hf.data(), flags.p, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, c->sA));
-    HIP_TRY(hipStreamSynchronize(c->sA));
-    std::vector<int64_t> os, ooff;
-    std::vector<int32_t> ol, ob;
-    std::vector<int64_t> oidx;
-    for (int64_t i = 0; i < n_chunks; i++) if (!hf[(size_t)i]) { os.push_back(chunk_start0[i]); ol.push_back(chunk_len[i]); oidx.push_back(i); }
-    if (!os.empty()) {
-        ooff.resize(os.size() + 1);
-        const int rc = segment_chunks_impl(c, os.data(), ol.data(), (int64_t)os.size(), P,
-                                           [&](int64_t total) { ob.resize((size_t)std::max<int64_t>(1, total)); return ob.data(); }, ooff.data(), err, errlen, false);
-        if (rc != WGBSSEG_OK) return rc;
+    const int wm = cls == 2 ? WG_MEDIUM_WMAX : WG_NARROW_WMAX;
+    const size_t rows = cls == 1 ? ((((size_t)ns * (WG_WIDE_TK + 1 + WG_WIDE_TS + 1) + 1) & ~(size_t)1) * 8)    // P of the ends + P of the starts, (meth, cov) as two dwords
+                                 : ((((size_t)ns * (ti + wm + 1) + 3) & ~(size_t)3) * 4);             // tile-local prefixes, packed in one dword
+    // guard-free kernels: just the two lookup tables, sized to the pseudo count and the tile class; otherwise the general fast tables
+    const size_t tabs = p.term_mode[cls] == 2 ? (size_t)p.rows[cls] * (16 + 64) * sizeof(wg_d2) : sizeof(wg_fast_tables);
+    // one 16-byte record per start (+ the closing one), 8 ints, and for narrow / medium tiles the block -> start map: a byte per eight blocks + forward steps
+    // (CostArgs::cmap = 3; a byte per block was measured for small cohorts, x8 scoring 6.73 ms against 6.59, x16 12.50 / 12.07: profiles/r04_cost_rec_ab.txt)
+    return tabs + rows + (size_t)(ti + 1) * 16 + 32 + (cls == 1 ? 0 : ((size_t)ti * wm >> 3) + 8);
+}
+
+// Tiling of the scoring kernel.
+// Narrow tiles (class 0): TI aligned start sites whose windows are all <= WA = min(widest window, WG_NARROW_WMAX);
+// LDS per workgroup: fast log tables + NS sample rows of TI+61 tile-local prefixes (one packed dword each) + small
+// per-tile arrays.  The kernel is a long dependent chain per evaluation, so resident wavefronts matter: pick the
+// shape that maximises (workgroups per CU) x (lane occupancy of the block rounds).
+// Wide tiles (class 1): 16 start sites x 128 end sites, for every 16-site unit that shares an aligned TI-group with
+// a window > WA (CpG islands; everything in deep mode); prefixes of starts and ends as (meth, cov) dword pairs.
+// Medium tiles (class 2, round 3): units of a non-narrow group whose windows stay <= WG_MEDIUM_WMAX = 252 sites (block counts < 2^16): CpG islands.
+int plan_tiles(const wgbsseg_ctx* c, const Job& job, const JobStatus& st, float pc, BatchPlan& p, char* err, size_t errlen)
+{
+    p.Wmax = (int)st.max_window;
+    p.WA = std::min(p.Wmax, WG_NARROW_WMAX);
+    p.WMED = c->medium_wmax;
+    // exponent rows of the k-scaled log tables (pseudo count >= 1): narrow tiles score blocks of <= WG_NARROW_WMAX sites,
+    // wide tiles blocks up to the job's widest window
+    // The guard-free form of the term (pseudo count >= 1) rests on block totals below 2^21 (csrc/exact_log2.h: p < 1 after the
+    // three float roundings, table rows down to 2^-23): the narrow tiles (blocks of <= 60 sites) always have them, the wide
+    // tiles only while 255 * (the job's widest window) < 2^21 — windows beyond 8224 sites (max_cpg > 8000: round 3) score with
+    // the general guarded form, which assumes nothing about the totals.
+    const int tmA = wg_term_mode(pc);
+    const int tmB = (tmA == 2 && 255.0 * std::max(p.Wmax, 1) >= 0x1p21) ? 1 : tmA;
+    p.term_mode[0] = p.term_mode[2] = tmA;
+    p.term_mode[1] = tmB;
+    p.rows[0] = tmA == 2 ? wg_lookup_rows(pc, 255.0 * WG_NARROW_WMAX) : 0;
+    p.rows[1] = tmB == 2 ? wg_lookup_rows(pc, 255.0 * std::max(p.Wmax, 1)) : 0;
+    p.rows[2] = tmA == 2 ? wg_lookup_rows(pc, 255.0 * WG_MEDIUM_WMAX) : 0;
+    if (p.rows[0] > WG_KY_KMIN + 1 || p.rows[1] > WG_KY_KMIN + 1 || p.rows[2] > WG_KY_KMIN + 1) {
+        set_err(err, errlen, "internal: %d / %d / %d lookup rows", p.rows[0], p.rows[1], p.rows[2]);
+        return WGBSSEG_E_ARG;
     }
-    std::vector<std::vector<int32_t>> plain((size_t)n_chunks);
-    for (int64_t i = 0; i < n_chunks; i++)
-        if (hf[(size_t)i]) {
-            wgbsseg_params Pc = *Peff;                         // (max_cpg is already cut to the longest chunk of the call; the kernels cut it to this chunk)
-            const int rc = plain_segment_chunk(c, chunk_start0[i], chunk_len[i], &Pc, plain[(size_t)i], err, errlen);
-            if (rc != WGBSSEG_OK) return rc;
+    const int Nsmp = (int)c->n_samples;
+    const double Favg = (double)(int64_t)st.total_pairs / (double)std::max<int64_t>(1, job.sites);
+    const int ti128_max_n = 16;
+    double best = -1;
+    for (int ti = 128; ti >= 16; ti >>= 1) {
+        if (c->force_ti > 0 && ti != c->force_ti) continue;
+        for (int ns : {Nsmp, 32, 16, 8, 4}) {
+            if (ns > Nsmp) continue;
+            // 128-start tiles: half the per-tile overhead for small cohorts; only with every sample in LDS at once (one group),
+            // and not by default above 16 samples, where their larger rows cost a workgroup per CU
+            if (ti == 128 && (ns != Nsmp || (c->force_ti != 128 && Nsmp > ti128_max_n))) continue;
+            if (c->force_ns > 0 && ns != std::min(c->force_ns, Nsmp)) continue;
+            const size_t l = cost_lds(p, ti, 0, ns);
+            if (l > 64 * 1024) continue;
+            // workgroups per CU the score counts on: LDS is handed out in granules of 1280 bytes; 5 for the 64-start tiles and below (the form
+            // with partial sums across sample groups has 95 VGPRs = 5 per CU; the one-group form has 63, but letting it count 7 makes small
+            // cohorts pick 64-start tiles, measured slower than 128-start ones: x8 scoring 6.92 vs 6.59 ms, profiles/r04_cost_rec_ab.txt)
+            const int wgs = (int)std::min<size_t>(ti == 128 ? 8 : 5, (160 * 1024) / (size_t)round_up((int64_t)l, 1280));
+            const double q = ti * std::min<double>(Favg, p.WA), eff = q / (256.0 * std::ceil(q / 256.0));
+            const double groups = std::ceil((double)Nsmp / ns);
+            const double score = wgs * eff / (1.0 + 0.02 * (groups - 1)) * (1.0 + 0.04 * (ti / 16));   // bias to big tiles (less staging)
+            if (score > best) { best = score; p.TI = ti; p.NS[0] = ns; }
         }
-    int64_t total = 0;
-    size_t oi = 0;
-    for (int64_t i = 0; i < n_chunks; i++) {
-        borders_off[i] = total;
-        if (hf[(size_t)i]) total += (int64_t)plain[(size_t)i].size();
-        else { total += ooff[oi + 1] - ooff[oi]; oi++; }
     }
-    borders_off[n_chunks] = total;
-    int32_t* out = alloc(total);
-    if (!out) { set_err(err, errlen, "borders_out too small: need %lld ints", (long long)total); return WGBSSEG_E_CAPACITY; }
-    oi = 0;
-    for (int64_t i = 0; i < n_chunks; i++) {
-        if (hf[(size_t)i]) memcpy(out + borders_off[i], plain[(size_t)i].data(), plain[(size_t)i].size() * 4);
-        else { memcpy(out + borders_off[i], ob.data() + ooff[oi], (size_t)(ooff[oi + 1] - ooff[oi]) * 4); oi++; }
-    }
-    c->last_valid = false;
+    if (best < 0) { p.TI = 16; p.NS[0] = 1; }
+    // wide and medium tiles: the samples per group that fit the most workgroups per CU (wide: 103 VGPRs, 4 at most; medium: rows of 269 dwords per sample, 5)
+    auto pick_ns = [&](int cls, int ti, int max_wgs, bool forced) {
+        int pick = 1;
+        double top = -1;
+        for (int ns : {Nsmp, 32, 16, 8, 4, 1}) {
+            if (ns > Nsmp) continue;
+            if (forced && c->force_ns > 0 && ns != std::min(c->force_ns, Nsmp)) continue;
+            const size_t l = cost_lds(p, ti, cls, ns);
+            if (l > 64 * 1024) continue;
+            const int wgs = (int)std::min<size_t>(max_wgs, (160 * 1024) / (size_t)round_up((int64_t)l, 1280));
+            const double score = wgs / (1.0 + 0.02 * (std::ceil((double)Nsmp / ns) - 1));
+            if (score > top) { top = score; pick = ns; }
+        }
+        return pick;
+    };
+    p.NS[1] = pick_ns(1, WG_WIDE_TS, 4, true);
+    p.NS[2] = pick_ns(2, WG_MEDIUM_TS, 5, false);
+    const int tile_ti[3] = {p.TI, WG_WIDE_TS, WG_MEDIUM_TS};
+    for (int k = 0; k < 3; k++) p.lds[k] = (size_t)round_up((int64_t)cost_lds(p, tile_ti[k], k, p.NS[k]), 16);
     return WGBSSEG_OK;
 }
 
+// Stages: bound the scored-block buffer and overlap scoring (stream A) with the recurrence (stream B); the recurrence kernel's form.
+void plan_stages(wgbsseg_ctx* c, const Job& job, const JobStatus& st, BatchPlan& p)
+{
+    const int64_t total_pairs = (int64_t)st.total_pairs;
+    const long long bytes = total_pairs * 8;
+    int n_stages = (int)std::max<long long>(1, (bytes + c->cost_budget_bytes - 1) / c->cost_budget_bytes);
+    // Few chunks (one rank's share of a sharded genome): the recurrence occupies a fraction of the CUs, so let it
+    // chase the scoring kernel stage by stage (measured: 71 chunks 10.1 -> 8.7 ms, 132 chunks 16.2 -> 15.0 ms).  With
+    // hundreds of chunks k_dp alone (3.9 ms per 60k-site chunk, all chunks at once) beats k_dp competing for CUs.
+    // (the junction patches that ride along in the batch are a few hundred sites each: they do not count)
+    int n_long = 0;
+    for (const ChunkDesc& d : job.h) n_long += d.len >= 8192;
+    // ... unless the recurrence is the longer of the two anyway (a share of a SMALL cohort): beside the scoring kernel a step of the recurrence
+    // takes ~50 ns against ~21 alone, so staging pays only when the scoring lasts longer than the ~30 ns per step it costs: at 7e11
+    // evaluations/s, from ~21,000 evaluations per step of the longest chunk on (round 6, one GPU's share of 8, 71 chunks: x 8 3.69 ms in eight
+    // stages, 2.63 in one; x 32 4.09 against 5.08; profiles/r06_stage_gate_ab.txt)
+    const bool worth = (double)total_pairs * c->n_samples >= (double)job.max_len * c->stage_min_evals_per_step;
+    if (job.max_len >= 8192) n_stages = std::max(n_stages, n_long <= 160 && worth ? 8 : 1);
+    // Many chunks, all windows <= 64: one stage scores and k_dp<7,64> follows alone (1.7 ms exposed).  (Two uneven stages — the
+    // recurrence of the first part of every chunk beside the scoring of the rest — were measured in round 2: 27.1-27.3 ms against 27.0
+    // whatever the split, profiles/r02_tail_split_sweep.txt: the scoring kernel loses what the recurrence no longer shows.)
+    if (c->force_stages > 0) n_stages = c->force_stages;
+    n_stages = std::min<int>(n_stages, std::max(1, (job.max_len + 63) / 64));
+    // Gated stages (k_stage_gate): the two scoring streams swap roles from stage to stage — the narrow tiles of an even stage on A with its medium / wide tiles
+    // beside them on A2, an odd stage the other way round (a second PAIR of streams was measured: six streams of one priority share hardware queues, every
+    // share lost 10-15 %)
+    p.all_narrow = p.Wmax <= WG_NARROW_WMAX;
+    // (one context per device: the streams of several contexts share hardware queues, where a gate could sit ahead of the very launch another context's gate waits for —
+    // the waits are bounded, but nothing would be gained)
+    // A job with medium / wide tiles (its recurrences are the 32-step kernels with the full LDS footprint, which lived on the drains: a share of 8, x 32 with islands,
+    // 5.95 -> 6.4 ms under the gate) is gated only when it is clearly scoring-bound (x 100 with islands: 14.0 -> 13.3 ms): from 100,000 evaluations per step on.
+    const double evals_per_step = (double)total_pairs * c->n_samples / std::max<double>(1.0, (double)job.max_len);
+    p.gated = c->stage_gate > 0 && n_stages > 1 && (p.all_narrow || evals_per_step >= c->stage_gate_wide_evals || c->stage_gate_shared) &&
+              (c->stage_gate_shared || g_live_ctx[c->device & 63].load(std::memory_order_relaxed) == 1);
+    // equal stages but the last (gated jobs only): its recurrence is the only one that runs with the chip to itself, at twice the pace of the others.
+    // Which length: the recurrences of the other stages take ~50 ns per step beside the scoring, so while the scoring of a stage lasts no longer than 1.5 x its
+    // recurrence (at 7e11 evaluations/s: up to ~52,000 evaluations per step of the longest chunk) the chain of recurrences is what the step waits for, and a last
+    // stage three times the others' shortens it (a share of 8, x 32: 4.08 -> 3.79 ms with the gate; equal stages + gate alone: 4.2); a scoring-bound job keeps equal
+    // stages (x 200: 20.4 -> 18.35 ms with the gate, 18.7 with a last stage twice the others').  profiles/r06_stage_gate_ab.txt
+    p.last_pct = !p.gated ? 100 : (c->last_stage_pct > 0 ? c->last_stage_pct : (evals_per_step <= 52500.0 ? 300 : 100));
+    const double parts = n_stages > 1 ? (double)(n_stages - 1) + p.last_pct / 100.0 : 1.0;
+    const int S = (int)round_up((int64_t)std::ceil((double)job.max_len / parts), 64);
+    n_stages = std::min<int>(n_stages, (job.max_len + S - 1) / S);
+    std::vector<int32_t>& sb = c->h_stage_bounds;
+    sb.resize((size_t)n_stages + 1);
+    for (int q = 0; q < n_stages; q++) sb[(size_t)q] = (int32_t)std::min<int64_t>((int64_t)q * S, job.max_len);
+    sb[(size_t)n_stages] = (int32_t)job.max_len;
+    p.sb = sb.data();
+    p.n_stages = n_stages;
+    p.stage_pairs.assign((size_t)n_stages, 0);
+    p.stage_tiles.assign((size_t)n_stages * 3, 0);
+    // No window beyond the narrow tiles' (every default-parameter genome outside CpG islands): every aligned group of TI starts is ONE narrow
+    // tile, so the host knows the tile counts without asking the device (round 6: one host round trip less in front of the scoring of every
+    // batch); the scored blocks per stage — what sizes the cost buffer — from the windows' statistics: all of them in one stage, at most
+    // (sites of the stage) x (widest window) otherwise.
+    if (p.all_narrow) {
+        for (int stg = 0; stg < n_stages; stg++) {
+            int64_t nt = 0, sites_in = 0;
+            for (const ChunkDesc& d : job.h) {
+                const int64_t s0 = sb[(size_t)stg], s1 = std::min<int64_t>(sb[(size_t)stg + 1], d.len);
+                if (s1 > s0) { nt += (s1 - s0 + p.TI - 1) / p.TI; sites_in += s1 - s0; }
+            }
+            p.stage_tiles[3 * (size_t)stg] = nt;
+            p.stage_pairs[(size_t)stg] = n_stages == 1 ? total_pairs : std::min<int64_t>(total_pairs, sites_in * std::max(p.Wmax, 1));
+        }
+    }
+    p.nbuf = n_stages > 1 ? (p.gated && n_stages > 2 ? 3 : 2) : 1;      // (gated: a stage's scoring must not wait for the recurrence two stages back when its gate opens)
+    // k_dp: 64-step batches when no window of the job exceeds 64 sites; otherwise 32-step batches with a second pending
+    // register per lane and, for blocks longer than 128 sites, a ring of pending maxima per chunk in global memory
+    p.dp_mode = std::max(p.Wmax > 512 ? 2 : (p.Wmax > 64 ? 1 : 0), c->force_dp_mode);
+    p.ringN = p.dp_mode ? ceil_pow2(p.Wmax + 128) : 0;
+    p.state_stride = round_up(WG_DP_STATE_HDR + (int64_t)p.ringN + (p.ringN + 1) / 2, 2);
+}
+
+// k_check_div on stream A: is the short division core exact on every operand pair of a block of <= wmax sites?  Its verdict (0: yes) lands in dst.
+int queue_div_check(wgbsseg_ctx* c, float pc, int wmax, void* dst, char* err, size_t errlen)
+{
+    HIP_TRY(c->divcheck.ensure(4));
+    HIP_TRY(hipMemsetAsync(c->divcheck.p, 0, 4, c->sA));
+    const int max_total = 255 * wmax;
+    hipLaunchKernelGGL(k_check_div, dim3((unsigned)max_total + 1), dim3(WG_BLOCK), 0, c->sA, pc, pc + pc, max_total, c->divcheck.as<unsigned int>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dst, c->divcheck.p, 4, hipMemcpyDeviceToHost, c->sA));
+    return WGBSSEG_OK;
+}
+
+// One batch in flight: the call, its job, statistics and plan, where its results go.  segment_chunks_impl runs its phases in this order.
+struct Batch {
+    wgbsseg_ctx* c = nullptr;
+    // the call as the caller made it
+    const int64_t* chunk_start0 = nullptr; const int32_t* chunk_len = nullptr; int64_t n_chunks = 0;
+    const BorderAlloc* alloc = nullptr; int64_t* borders_off = nullptr; EarlyOut* early = nullptr;
+    bool allow_plain = true;
+    wgbsseg_params P = {};               // the parameters with max_cpg cut to the longest chunk of the call
+    Job job;
+    int nC = 0; int64_t J = 0;           // chunks and sites of the batch
+    JobStatus* hst = nullptr;            // page-locked landing area: [0] the window statistics, [1] / [3] k_check_div's verdicts (narrow / medium), [2] the scan's verdict
+    JobStatus st = {};                   // the window statistics
+    BatchPlan plan;
+    CostArgs ca[3];                      // per tile class
+    std::vector<int64_t> tile0[3];       // per tile class: first tile of every stage (+ the total)
+    DevBuf* outb = nullptr; size_t out_head = 0;   // the result on the device: the CSR offsets, then from out_head the border lists
+    bool marks = false;                  // (WGBSSEG_PROFILE=2) host clock: entry, tables up, windows queued, statistics here, scoring queued, everything queued, results here, return
+    double hm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void mark(int i) { if (marks) hm[i] = wall_s(); }
+
+    int front(char* err, size_t errlen);           // the scan pass starts with the batch on its own stream (round 6); the windows pass; the window statistics come home
+    int disorder_exit(char* err, size_t errlen);   // loci not ascending inside a chunk, or a chunk of more than 2^32 blocks: the batch ends after the front
+    int tile_plan(char* err, size_t errlen);       // lookup tables and stage bounds up, tiles counted (k_tile_count: not all narrow), laid out (k_stage_plan), written (k_tile_emit)
+    int stages(char* err, size_t errlen);          // per stage: its scoring (stream A, A2 beside it), then its recurrence (stream B)
+    int deliver(char* err, size_t errlen);         // traceback, the border lists and their CSR offsets, home (one copy, or early delivery)
+    int timings(char* err, size_t errlen);         // the device time line (WGBSSEG_PROFILE=2) and the context's totals
+};
+
+// One batch: the front, the host's plan (plan_tiles, plan_stages), the tile plan, the stages, traceback and delivery, timings.
 int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32_t* chunk_len, int64_t n_chunks,
-                        const wgbsseg_params* P, const BorderAlloc& alloc, int64_t* borders_off, char* err, size_t errlen, bool allow_plain, EarlyOut* early)
+                        const wgbsseg_params* P, const BorderAlloc& alloc, int64_t* borders_off, char* err, size_t errlen, bool allow_plain = true, EarlyOut* early = nullptr)
 {
     if (!P || !borders_off) { set_err(err, errlen, "NULL params/borders pointer"); return WGBSSEG_E_ARG; }
     if (P->max_bp == 0) { set_err(err, errlen, "max_bp must be >= 1 (the reference reads uninitialised loci when it is 0: segmentor.cpp:38,114)"); return WGBSSEG_E_ARG; }
@@ -832,18 +1013,18 @@ int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32
     // only up to the longest chunk of the call.
     int32_t longest = 1;
     if (chunk_len) for (int64_t i = 0; i < n_chunks; i++) longest = std::max(longest, chunk_len[i]);
-    wgbsseg_params Peff = *P;
-    Peff.max_cpg = std::min<uint32_t>(P->max_cpg, (uint32_t)longest);
-    if ((uint64_t)Peff.max_cpg * 255u >= (1u << 24) || Peff.max_cpg > WGBSSEG_MAX_CPG) {
+    Batch b;
+    b.c = c; b.chunk_start0 = chunk_start0; b.chunk_len = chunk_len; b.n_chunks = n_chunks;
+    b.alloc = &alloc; b.borders_off = borders_off; b.early = early; b.allow_plain = allow_plain;
+    b.P = *P;
+    b.P.max_cpg = std::min<uint32_t>(P->max_cpg, (uint32_t)longest);
+    if ((uint64_t)b.P.max_cpg * 255u >= (1u << 24) || b.P.max_cpg > WGBSSEG_MAX_CPG) {
         set_err(err, errlen, "max_cpg %u with chunks of up to %d sites unsupported: blocks of more than %d sites (255 * sites >= 2^24) do not keep their counts exact "
                 "in the float sums of the reference itself (segmentor.cpp:122-123), and windows are stored in 16 bits", P->max_cpg, (int)longest, WGBSSEG_MAX_CPG);
         return WGBSSEG_E_ARG;
     }
-    const wgbsseg_params* const P0 = P;
-    P = &Peff;
-    static const bool host_marks = getenv("WGBSSEG_PROFILE") && atoi(getenv("WGBSSEG_PROFILE")) >= 2;
-    double hm[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // (WGBSSEG_PROFILE=2) host clock: entry, tables up, windows queued, statistics here, scoring queued, everything queued, results here, return
-    if (host_marks) hm[0] = wall_s();
+    b.marks = c && c->batch_marks;
+    b.mark(0);
     if (!(P->pseudo_count >= 0.0f)) { set_err(err, errlen, "pseudo_count must be >= 0"); return WGBSSEG_E_ARG; }
     // A batch that failed half way may have left work behind on the scoring / scan streams that reads the staging areas: such a context is drained before it is
     // used again.  (A clean one is NOT synchronised stream by stream here: the follow-up batch of an early delivery starts while k_copy_out still writes the first
@@ -854,16 +1035,30 @@ int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32
         c->out_pending = false;
     }
     if (c) c->batch_open = true;
-    Job job;
-    int rc = build_job(c, chunk_start0, chunk_len, n_chunks, job, true, err, errlen);
+    int rc = build_job(c, chunk_start0, chunk_len, n_chunks, b.job, true, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
-    rc = plan_validation(c, job, !c->accumulate, err, errlen);
+    rc = plan_validation(c, b.job, !c->accumulate, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     c->last_valid = false;
-    const int nC = (int)n_chunks;
-    const int64_t J = job.sites;
-    JobView& v = job.v;
+    b.nC = (int)n_chunks;
+    b.J = b.job.sites;
 
+    rc = b.front(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (b.st.loci_disorder || b.st.overflow) return b.disorder_exit(err, errlen);
+    rc = plan_tiles(c, b.job, b.st, b.P.pseudo_count, b.plan, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    plan_stages(c, b.job, b.st, b.plan);
+    rc = b.tile_plan(err, errlen);
+    if (rc == WGBSSEG_OK) rc = b.stages(err, errlen);
+    if (rc == WGBSSEG_OK) rc = b.deliver(err, errlen);
+    if (rc == WGBSSEG_OK) rc = b.timings(err, errlen);
+    return rc;
+}
+
+int Batch::front(char* err, size_t errlen)
+{
+    JobView& v = job.v;
     const int64_t Jp = job.sites_padded;                         // every chunk's slice of the job-site arrays begins at a multiple of 8 entries
     const int64_t nT = job.wtile_off[(size_t)nC];                // 1024-site tiles of the windows pass
     if (nT > 0x7fffffff) { set_err(err, errlen, "too many sites in one call"); return WGBSSEG_E_ARG; }
@@ -878,492 +1073,293 @@ int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32
     v.W16 = c->W16.as<uint16_t>(); v.cum32 = c->cum32.as<uint32_t>(); v.back16 = c->back16.as<uint16_t>();
     v.chunk_pairs = c->chunk_pairs.as<int64_t>(); v.umax16 = c->umax16.as<uint16_t>();
     if (!c->h_status.ensure(4 * sizeof(JobStatus))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    hst = reinterpret_cast<JobStatus*>(c->h_status.p);
 
-    // ---- the scan pass starts with the batch, on its own stream (round 6) ---------------------------------------
     // k_validate needs the beta bytes and the list of pieces, nothing from the windows: it runs beside k_window (HBM-bound beside
     // instruction-bound) instead of behind it, and the scoring kernel of a job without wide tiles — which needs nothing from the scan
     // but its verdict, read at the end of the batch — no longer queues behind either.  (Rounds 1-5: windows 0.28 ms, then the scan
     // 0.32 ms, then the tile plan: scoring began 0.71 ms into the hg19 x 32 batch.)
-    if (host_marks) hm[1] = wall_s();
-    HIP_TRY(hipEventRecord(c->ev[0], c->sA));
-    HIP_TRY(hipEventRecord(c->ev[12], c->sA));                   // chunk table, pieces and the cleared status block are on the device
-    hipStream_t const sS = c->sC;
-    // where k_validate starts (WGBSSEG_SCAN_AFTER, A/B): 0 with the batch, beside the windows pass; 1 behind the windows pass, beside the tile plan; 2 behind the
-    // tile plan, beside the first scoring tiles only (the latency-bound kernels of the front — row offsets, stage plan, tile descriptors — keep the memory system to themselves)
-    static const int scan_after = getenv("WGBSSEG_SCAN_AFTER") ? atoi(getenv("WGBSSEG_SCAN_AFTER")) : 0;
-    bool validate_queued = false;
-    HIP_TRY(hipStreamWaitEvent(sS, c->ev[12], 0));
-    if (!scan_after) {
-        validate_queued = true;
-        HIP_TRY(hipEventRecord(c->ev[8], sS));
-        rc = launch_validate(c, job, sS, err, errlen);
-        if (rc != WGBSSEG_OK) return rc;
-        HIP_TRY(hipEventRecord(c->ev[9], sS));
-    }
+    mark(1);
+    HIP_TRY(hipEventRecord(c->ev[EV_BEGIN], c->sA));
+    HIP_TRY(hipEventRecord(c->ev[EV_UPLOADED], c->sA));
+    HIP_TRY(hipStreamWaitEvent(c->sC, c->ev[EV_UPLOADED], 0));
+    HIP_TRY(hipEventRecord(c->ev[EV_VALIDATE0], c->sC));
+    int rc = launch_validate(c, job, c->sC, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    HIP_TRY(hipEventRecord(c->ev[EV_VALIDATE1], c->sC));
 
-    // ---- window extents ------------------------------------------------------------------------------------------
     // a pseudo count this context has not scored with yet: may the narrow tiles use the short division core?  Every operand
     // pair they can form is tried on the device (0.1 ms, once); the verdict arrives with the window statistics.
-    const bool check_div = c->divs_enabled && wg_term_mode(P->pseudo_count) == 2 && c->divs_pc != P->pseudo_count;
-    if (check_div) {
-        HIP_TRY(c->divcheck.ensure(4));
-        HIP_TRY(hipMemsetAsync(c->divcheck.p, 0, 4, c->sA));
-        const int max_total = 255 * WG_NARROW_WMAX;
-        hipLaunchKernelGGL(k_check_div, dim3((unsigned)max_total + 1), dim3(WG_BLOCK), 0, c->sA, P->pseudo_count, P->pseudo_count + P->pseudo_count,
-                           max_total, c->divcheck.as<unsigned int>());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(reinterpret_cast<JobStatus*>(c->h_status.p) + 1, c->divcheck.p, 4, hipMemcpyDeviceToHost, c->sA));
-    }
+    const bool check_div = c->divs_enabled && wg_term_mode(P.pseudo_count) == 2 && c->divs_pc != P.pseudo_count;
+    if (check_div && (rc = queue_div_check(c, P.pseudo_count, WG_NARROW_WMAX, hst + 1, err, errlen)) != WGBSSEG_OK) return rc;
     // the search's first step when a wavefront has windows of 64 sites and more: 2^floor(log2(max_cpg - 1))
     int top_step = 1;
-    while (2 * (int64_t)top_step <= (int64_t)P->max_cpg - 1) top_step *= 2;
+    while (2 * (int64_t)top_step <= (int64_t)P.max_cpg - 1) top_step *= 2;
     // loci of a 1024-site tile, of the site before it and of everything a PROBE of its searches can touch, in LDS (<= 48 KB; deeper windows search in L2)
     const int64_t win_want = 1 + (int64_t)WG_WIN_TILE + 2 * (int64_t)std::max(top_step, 32) + 8;
     const int win_lds = win_want <= 12288 ? (int)win_want : 0;
-    // medium tiles (round 3): units of a non-narrow group whose windows stay <= WG_MEDIUM_WMAX = 252 sites (block counts < 2^16): CpG islands
-    const int wm_env = getenv("WGBSSEG_MEDIUM_WMAX") ? std::max(0, std::min(WG_MEDIUM_WMAX, atoi(getenv("WGBSSEG_MEDIUM_WMAX")))) : WG_MEDIUM_WMAX;   // 0: no medium class (A/B, tests; read per call)
-    const int WMED = wm_env > WG_NARROW_WMAX ? wm_env : 0;
     const int64_t* const d_wtile = c->wtile.as<int64_t>();
     hipLaunchKernelGGL(k_window, dim3((unsigned)nT), dim3(WG_BLOCK), (size_t)win_lds * 4, c->sA, v, c->status.as<JobStatus>(),
-                       d_wtile, reinterpret_cast<const int32_t*>(d_wtile + nC + 1), P->max_cpg, P->max_bp, win_lds, top_step, std::max(WMED, WG_NARROW_WMAX),
+                       d_wtile, reinterpret_cast<const int32_t*>(d_wtile + nC + 1), P.max_cpg, P.max_bp, win_lds, top_step, std::max(c->medium_wmax, WG_NARROW_WMAX),
                        c->tile_tot.as<uint32_t>(), c->tile_chunk.as<int4>());
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_window_scan, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sA, v, c->status.as<JobStatus>(), d_wtile, c->tile_tot.as<uint32_t>(), c->tile_base.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[1], c->sA));
-    if (scan_after == 1) {
-        validate_queued = true;
-        HIP_TRY(hipStreamWaitEvent(sS, c->ev[1], 0));
-        HIP_TRY(hipEventRecord(c->ev[8], sS));
-        rc = launch_validate(c, job, sS, err, errlen);
-        if (rc != WGBSSEG_OK) return rc;
-        HIP_TRY(hipEventRecord(c->ev[9], sS));
-    }
-    JobStatus* hst = reinterpret_cast<JobStatus*>(c->h_status.p);
+    HIP_TRY(hipEventRecord(c->ev[EV_WINDOWS], c->sA));
     HIP_TRY(hipMemcpyAsync(&hst[0], c->status.p, sizeof(JobStatus), hipMemcpyDeviceToHost, c->sA));
-    HIP_TRY(hipEventRecord(c->ev[7], c->sA));
+    HIP_TRY(hipEventRecord(c->ev[EV_STATS], c->sA));
     // (the row offsets are not in the statistics: this pass runs while the host reads them and plans the tiles)
     hipLaunchKernelGGL(k_window_cum, dim3((unsigned)((nT + WG_CUM_TILES - 1) / WG_CUM_TILES)), dim3(WG_BLOCK), 0, c->sA, (const uint16_t*)v.W16, v.cum32, (const int4*)c->tile_chunk.as<int4>(),
                        (const uint32_t*)c->tile_base.as<uint32_t>(), nT);
     HIP_TRY(hipGetLastError());
-    if (host_marks) hm[2] = wall_s();
-    HIP_TRY(hipEventSynchronize(c->ev[7]));                    // window statistics are here; the scan pass is still running
-    if (host_marks) hm[3] = wall_s();
-    const JobStatus st = hst[0];
+    mark(2);
+    HIP_TRY(hipEventSynchronize(c->ev[EV_STATS]));              // window statistics are here; the scan pass is still running
+    mark(3);
+    st = hst[0];
     if (check_div) {
         c->divs_ok = *reinterpret_cast<const unsigned int*>(&hst[1]) == 0u;
-        c->divs_pc = P->pseudo_count;
-        if (profiling()) fprintf(stderr, "[wgbsseg] short division core for pseudo count %g: %s\n", (double)P->pseudo_count, c->divs_ok ? "verified on every operand pair of a narrow tile" : "NOT exact, the full core stays");
+        c->divs_pc = P.pseudo_count;
+        if (profiling()) fprintf(stderr, "[wgbsseg] short division core for pseudo count %g: %s\n", (double)P.pseudo_count, c->divs_ok ? "verified on every operand pair of a narrow tile" : "NOT exact, the full core stays");
     }
     // wide tiles read the carries of k_scan: behind k_validate on the scan stream, as soon as the windows are known
     if (st.wide_units && !st.loci_disorder && !st.overflow) {
-        HIP_TRY(hipStreamWaitEvent(sS, c->ev[1], 0));
-        HIP_TRY(hipEventRecord(c->ev[10], sS));
-        rc = launch_scan(c, job, sS, err, errlen);
+        HIP_TRY(hipStreamWaitEvent(c->sC, c->ev[EV_WINDOWS], 0));
+        HIP_TRY(hipEventRecord(c->ev[EV_SCAN0], c->sC));
+        rc = launch_scan(c, job, c->sC, err, errlen);
         if (rc != WGBSSEG_OK) return rc;
-        HIP_TRY(hipEventRecord(c->ev[11], sS));
+        HIP_TRY(hipEventRecord(c->ev[EV_SCAN1], c->sC));
     }
-    // (k_scan checks every byte k_validate would: a job with wide tiles that has not queued k_validate yet does without it)
-    const bool validate_late = !validate_queued && !(st.wide_units && !st.loci_disorder && !st.overflow);
-    auto close_scan_stream = [&]() -> hipError_t {             // the scan's verdict, read at the end of the batch
-        hipError_t e = hipEventRecord(c->ev[2], sS);
-        if (e == hipSuccess) e = hipMemcpyAsync(&hst[2], c->status.p, sizeof(JobStatus), hipMemcpyDeviceToHost, sS);
-        if (e == hipSuccess) e = hipEventRecord(c->evS, sS);
-        return e;
-    };
-    auto queue_validate_now = [&]() -> int {
-        HIP_TRY(hipEventRecord(c->ev[8], sS));
-        const int r = launch_validate(c, job, sS, err, errlen);
-        if (r != WGBSSEG_OK) return r;
-        HIP_TRY(hipEventRecord(c->ev[9], sS));
-        return WGBSSEG_OK;
-    };
-    if (!validate_queued && !validate_late) { HIP_TRY(hipEventRecord(c->ev[8], sS)); HIP_TRY(hipEventRecord(c->ev[9], sS)); }
-    if (!validate_late) HIP_TRY(close_scan_stream());
-    if (st.loci_disorder || st.overflow) {
-        JobStatus st2;                                        // the scan's verdict takes precedence, as it always has
-        if (validate_late) { rc = queue_validate_now(); if (rc != WGBSSEG_OK) return rc; HIP_TRY(close_scan_stream()); }
-        HIP_TRY(hipStreamSynchronize(sS));
-        HIP_TRY(hipStreamSynchronize(c->sA));
-        HIP_TRY(hipMemcpyAsync(&st2, c->status.p, sizeof(st2), hipMemcpyDeviceToHost, c->sA));
-        HIP_TRY(hipStreamSynchronize(c->sA));
-        if (st2.first_bad != ~0ULL) return report_bad_site(c, st2, err, errlen);
-        if (st.loci_disorder) {
-            // loci not ascending inside a chunk: the reference bars such an extension and leaves the site out of its running sums
-            // (segmentor.cpp:114-117).  The batch path rests on ascending loci (windows, prefix sums); the chunks concerned take
-            // the plain path (csrc/plain_dp.h: the reference's loops as written), the rest of the batch runs again without them.
-            if (allow_plain) return segment_chunks_with_disorder(c, chunk_start0, chunk_len, n_chunks, P0, &Peff, job, alloc, borders_off, err, errlen);
-            set_err(err, errlen, "internal: loci not ascending inside chunk %u (0-based sites [%lld, +%d)) of a batch that was filtered for such chunks",
-                    st.loci_disorder - 1, (long long)(job.h[st.loci_disorder - 1].start0 + c->site_base), (int)job.h[st.loci_disorder - 1].len);
-            return WGBSSEG_E_LOCI_ORDER;
-        }
-        set_err(err, errlen, "a chunk scores more than 2^32 blocks; use a smaller chunk_size"); return WGBSSEG_E_ARG;
-    }
-    const int Wmax = (int)st.max_window;
-    const int64_t total_pairs = (int64_t)st.total_pairs;
+    // the scan's verdict, read at the end of the batch
+    HIP_TRY(hipEventRecord(c->ev[EV_SCAN_END], c->sC));
+    HIP_TRY(hipMemcpyAsync(&hst[2], c->status.p, sizeof(JobStatus), hipMemcpyDeviceToHost, c->sC));
+    HIP_TRY(hipEventRecord(c->evS, c->sC));
+    return WGBSSEG_OK;
+}
 
-    // ---- tiling of the scoring kernel ----------------------------------------------------------------------
-    // Narrow tiles (class A): TI aligned start sites whose windows are all <= WA = min(widest window, WG_NARROW_WMAX);
-    // LDS per workgroup: fast log tables + NS sample rows of TI+61 tile-local prefixes (one packed dword each) + small
-    // per-tile arrays.  The kernel is a long dependent chain per evaluation, so resident wavefronts matter: pick the
-    // shape that maximises (workgroups per CU) x (lane occupancy of the block rounds).
-    // Wide tiles (class B): 16 start sites x 128 end sites, for every 16-site unit that shares an aligned TI-group with
-    // a window > WA (CpG islands; everything in deep mode); prefixes of starts and ends as (meth, cov) dword pairs.
-    const int Nsmp = (int)c->n_samples;
-    const double Favg = (double)total_pairs / (double)std::max<int64_t>(1, J);
-    const int WA = std::min(Wmax, WG_NARROW_WMAX);
-    const int TKB = WG_WIDE_TK;
-    // exponent rows of the k-scaled log tables (pseudo count >= 1): narrow tiles score blocks of <= WG_NARROW_WMAX sites,
-    // wide tiles blocks up to the job's widest window
-    // The guard-free form of the term (pseudo count >= 1) rests on block totals below 2^21 (csrc/exact_log2.h: p < 1 after the
-    // three float roundings, table rows down to 2^-23): the narrow tiles (blocks of <= 60 sites) always have them, the wide
-    // tiles only while 255 * (the job's widest window) < 2^21 — windows beyond 8224 sites (max_cpg > 8000: round 3) score with
-    // the general guarded form, which assumes nothing about the totals.
-    const int term_modeA = wg_term_mode(P->pseudo_count);
-    const int term_modeB = (term_modeA == 2 && 255.0 * std::max(Wmax, 1) >= 0x1p21) ? 1 : term_modeA;
-    const bool ks = term_modeA == 2, ksB = term_modeB == 2;
-    const int rowsA = ks ? wg_lookup_rows(P->pseudo_count, 255.0 * WG_NARROW_WMAX) : 0;
-    const int rowsB = ksB ? wg_lookup_rows(P->pseudo_count, 255.0 * std::max(Wmax, 1)) : 0;
-    const int rowsM = ks ? wg_lookup_rows(P->pseudo_count, 255.0 * WG_MEDIUM_WMAX) : 0;
-    if (rowsA > WG_KY_KMIN + 1 || rowsB > WG_KY_KMIN + 1 || rowsM > WG_KY_KMIN + 1) { set_err(err, errlen, "internal: %d / %d / %d lookup rows", rowsA, rowsB, rowsM); return WGBSSEG_E_ARG; }
-    // tile class: 0 narrow (ti starts), 1 wide, 2 medium
-    // block -> start map of the narrow / medium tiles: a byte per eight blocks + forward steps.  (A byte per block — no steps — was measured for
-    // the 128-start tiles of small cohorts, whose LDS has room: x8 scoring 6.73 ms against 6.59 with the coarse map, x16 12.50 / 12.07: the
-    // workgroup per CU it costs outweighs the steps it saves; profiles/r04_cost_rec_ab.txt.)
-    auto cmap_shift = [&](int, int) { return 3; };
-    auto lds_for = [&](int ti, int cls, int ns) -> size_t {
-        const int wm = cls == 2 ? WG_MEDIUM_WMAX : WG_NARROW_WMAX;
-        const size_t rows = cls == 1 ? ((((size_t)ns * (WG_WIDE_TK + 1 + WG_WIDE_TS + 1) + 1) & ~(size_t)1) * 8)    // P of the ends + P of the starts, (meth, cov) as two dwords
-                                     : ((((size_t)ns * (ti + wm + 1) + 3) & ~(size_t)3) * 4);             // tile-local prefixes, packed in one dword
-        // guard-free kernels: just the two lookup tables, sized to the pseudo count and the tile class; otherwise the general fast tables
-        const size_t tabs = (cls == 1 ? ksB : ks) ? (size_t)(cls == 1 ? rowsB : cls == 2 ? rowsM : rowsA) * (16 + 64) * sizeof(wg_d2) : sizeof(wg_fast_tables);
-        return tabs + rows + (size_t)(ti + 1) * 16 + 32 +      // one 16-byte record per start (+ the closing one), 8 ints
-               (cls == 1 ? 0 : ((size_t)ti * wm >> cmap_shift(ti, cls)) + 8);      // (+ the block -> start map)
-    };
-    int TI = 64, NSA = 1, NSB = 1, NSM = 1;
-    const int ti128_max_n = 16;
-    {
-        double best = -1;
-        for (int ti = 128; ti >= 16; ti >>= 1) {
-            if (c->force_ti > 0 && ti != c->force_ti) continue;
-            const int ns_opts[5] = {Nsmp, 32, 16, 8, 4};
-            for (int ns : ns_opts) {
-                if (ns > Nsmp) continue;
-                // 128-start tiles: half the per-tile overhead for small cohorts; only with every sample in LDS at once (one group),
-                // and not by default above 16 samples, where their larger rows cost a workgroup per CU
-                if (ti == 128 && (ns != Nsmp || (c->force_ti != 128 && Nsmp > ti128_max_n))) continue;
-                if (c->force_ns > 0 && ns != std::min(c->force_ns, Nsmp)) continue;
-                const size_t l = lds_for(ti, 0, ns);
-                if (l > 64 * 1024) continue;
-                // workgroups per CU the score counts on: LDS is handed out in granules of 1280 bytes; 5 for the 64-start tiles and below (the form
-                // with partial sums across sample groups has 95 VGPRs = 5 per CU; the one-group form has 63, but letting it count 7 makes small
-                // cohorts pick 64-start tiles, measured slower than 128-start ones: x8 scoring 6.92 vs 6.59 ms, profiles/r04_cost_rec_ab.txt)
-                const int wgs = (int)std::min<size_t>(ti == 128 ? 8 : 5, (160 * 1024) / (size_t)round_up((int64_t)l, 1280));
-                const double q = ti * std::min<double>(Favg, WA), eff = q / (256.0 * std::ceil(q / 256.0));
-                const double groups = std::ceil((double)Nsmp / ns);
-                const double score = wgs * eff / (1.0 + 0.02 * (groups - 1)) * (1.0 + 0.04 * (ti / 16));   // bias to big tiles (less staging)
-                if (score > best) { best = score; TI = ti; NSA = ns; }
-            }
-        }
-        if (best < 0) { TI = 16; NSA = 1; }
-        best = -1;
-        const int ns_opts[6] = {Nsmp, 32, 16, 8, 4, 1};
-        for (int ns : ns_opts) {
-            if (ns > Nsmp) continue;
-            if (c->force_ns > 0 && ns != std::min(c->force_ns, Nsmp)) continue;
-            const size_t l = lds_for(WG_WIDE_TS, 1, ns);
-            if (l > 64 * 1024) continue;
-            const int wgs = (int)std::min<size_t>(4, (160 * 1024) / (size_t)round_up((int64_t)l, 1280));      // 103 VGPRs: 4 workgroups per CU at most
-            const double groups = std::ceil((double)Nsmp / ns);
-            const double score = wgs / (1.0 + 0.02 * (groups - 1));
-            if (score > best) { best = score; NSB = ns; }
-        }
-        best = -1;
-        for (int ns : ns_opts) {                                   // medium tiles: rows of 269 dwords per sample
-            if (ns > Nsmp) continue;
-            const size_t l = lds_for(WG_MEDIUM_TS, 2, ns);
-            if (l > 64 * 1024) continue;
-            const int wgs = (int)std::min<size_t>(5, (160 * 1024) / (size_t)round_up((int64_t)l, 1280));
-            const double groups = std::ceil((double)Nsmp / ns);
-            const double score = wgs / (1.0 + 0.02 * (groups - 1));
-            if (score > best) { best = score; NSM = ns; }
-        }
+int Batch::disorder_exit(char* err, size_t errlen)
+{
+    JobStatus st2;                                        // the scan's verdict takes precedence, as it always has
+    HIP_TRY(hipStreamSynchronize(c->sC));
+    HIP_TRY(hipStreamSynchronize(c->sA));
+    HIP_TRY(hipMemcpyAsync(&st2, c->status.p, sizeof(st2), hipMemcpyDeviceToHost, c->sA));
+    HIP_TRY(hipStreamSynchronize(c->sA));
+    if (st2.first_bad != ~0ULL) return report_bad_site(c, st2, err, errlen);
+    if (!st.loci_disorder) { set_err(err, errlen, "a chunk scores more than 2^32 blocks; use a smaller chunk_size"); return WGBSSEG_E_ARG; }
+    if (!allow_plain) {
+        set_err(err, errlen, "internal: loci not ascending inside chunk %u (0-based sites [%lld, +%d)) of a batch that was filtered for such chunks",
+                st.loci_disorder - 1, (long long)(job.h[st.loci_disorder - 1].start0 + c->site_base), (int)job.h[st.loci_disorder - 1].len);
+        return WGBSSEG_E_LOCI_ORDER;
     }
-    CostArgs caA, caB;
-    memset(&caA, 0, sizeof(caA));
-    caA.pc = P->pseudo_count; caA.pc2 = P->pseudo_count + P->pseudo_count;
-    caA.xcd_group = 64;
-    caA.cmap = 3;
-    caB = caA;
-    CostArgs caM = caA;
-    caA.cmap = cmap_shift(TI, 0);
-    caA.NS = NSA; caA.rows = rowsA;
-    caB.NS = NSB; caB.rows = rowsB;
-    caM.NS = NSM; caM.rows = rowsM;
-    if (ks) {   // the k-scaled tables of the tile classes (same IEEE operations as on the device): built and uploaded when the pseudo count or a
-                // class's exponent rows differ from what the context holds — a follow-up batch of the same call, the next call of a bench, reuse them
-        const bool same = c->lookup_pc == P->pseudo_count && c->lookup_rows[0] == rowsA && c->lookup_rows[1] == rowsB && c->lookup_rows[2] == rowsM && c->lookup.p;
+    // loci not ascending inside a chunk: the reference bars such an extension and leaves the site out of its running sums
+    // (segmentor.cpp:114-117).  The batch path rests on ascending loci (windows, prefix sums); the chunks concerned (k_find_disorder) take
+    // the plain path (csrc/plain_dp.h: the reference's loops as written), the rest of the batch runs again without them, and the border
+    // lists are put back in the caller's order.
+    DevBuf flags;
+    struct Free { DevBuf& a; ~Free() { a.release(); } } fr{flags};
+    HIP_TRY(flags.ensure((size_t)n_chunks * 4));
+    HIP_TRY(hipMemsetAsync(flags.p, 0, (size_t)n_chunks * 4, c->sA));
+    hipLaunchKernelGGL(k_find_disorder, dim3((unsigned)n_chunks), dim3(WG_BLOCK), 0, c->sA, job.v, flags.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> hf((size_t)n_chunks);
+    HIP_TRY(hipMemcpyAsync(hf.data(), flags.p, (size_t)n_chunks * 4, hipMemcpyDeviceToHost, c->sA));
+    HIP_TRY(hipStreamSynchronize(c->sA));
+    std::vector<int64_t> os, ooff;
+    std::vector<int32_t> ol, ob;
+    for (int64_t i = 0; i < n_chunks; i++) if (!hf[(size_t)i]) { os.push_back(chunk_start0[i]); ol.push_back(chunk_len[i]); }
+    if (!os.empty()) {
+        ooff.resize(os.size() + 1);
+        const int rc = segment_chunks_impl(c, os.data(), ol.data(), (int64_t)os.size(), &P,
+                                           [&](int64_t total) { ob.resize((size_t)std::max<int64_t>(1, total)); return ob.data(); }, ooff.data(), err, errlen, false);
+        if (rc != WGBSSEG_OK) return rc;
+    }
+    std::vector<std::vector<int32_t>> plain((size_t)n_chunks);
+    for (int64_t i = 0; i < n_chunks; i++)
+        if (hf[(size_t)i]) {
+            wgbsseg_params Pc = P;                             // (max_cpg is already cut to the longest chunk of the call; the kernels cut it to this chunk)
+            const int rc = plain_segment_chunk(c, chunk_start0[i], chunk_len[i], &Pc, plain[(size_t)i], err, errlen);
+            if (rc != WGBSSEG_OK) return rc;
+        }
+    int64_t total = 0;
+    size_t oi = 0;
+    for (int64_t i = 0; i < n_chunks; i++) {
+        borders_off[i] = total;
+        if (hf[(size_t)i]) total += (int64_t)plain[(size_t)i].size();
+        else { total += ooff[oi + 1] - ooff[oi]; oi++; }
+    }
+    borders_off[n_chunks] = total;
+    int32_t* out = (*alloc)(total);
+    if (!out) { set_err(err, errlen, "borders_out too small: need %lld ints", (long long)total); return WGBSSEG_E_CAPACITY; }
+    oi = 0;
+    for (int64_t i = 0; i < n_chunks; i++) {
+        if (hf[(size_t)i]) memcpy(out + borders_off[i], plain[(size_t)i].data(), plain[(size_t)i].size() * 4);
+        else { memcpy(out + borders_off[i], ob.data() + ooff[oi], (size_t)(ooff[oi + 1] - ooff[oi]) * 4); oi++; }
+    }
+    c->last_valid = false;
+    return WGBSSEG_OK;
+}
+
+int Batch::tile_plan(char* err, size_t errlen)
+{
+    BatchPlan& p = plan;
+    const float pc = P.pseudo_count;
+    const int n_stages = p.n_stages;
+    CostArgs base;
+    memset(&base, 0, sizeof(base));
+    base.pc = pc; base.pc2 = pc + pc;
+    base.xcd_group = 64;
+    base.cmap = 3;                                             // the block -> start map: a byte per eight blocks (cost_lds)
+    for (int k = 0; k < 3; k++) { ca[k] = base; ca[k].NS = p.NS[k]; ca[k].rows = p.rows[k]; }
+    if (p.term_mode[0] == 2) {   // the k-scaled tables of the tile classes (same IEEE operations as on the device): built and uploaded when the pseudo count or a
+                                 // class's exponent rows differ from what the context holds — a follow-up batch of the same call, the next call of a bench, reuse them
+        const bool same = c->lookup_pc == pc && c->lookup_rows[0] == p.rows[0] && c->lookup_rows[1] == p.rows[1] && c->lookup_rows[2] == p.rows[2] && c->lookup.p;
         if (!same) {
             static const wg_log_tables host_tabs = WG_LOG_TABLES_INIT;
-            c->h_lookup.resize((size_t)(rowsA + rowsB + rowsM) * 80);
+            c->h_lookup.resize((size_t)(p.rows[0] + p.rows[1] + p.rows[2]) * 80);
             wg_d2* dst = c->h_lookup.data();
-            for (int rows : {rowsA, rowsB, rowsM}) {
+            for (int rows : p.rows) {
                 for (int x = 0; x < rows * 16; x++) dst[x] = wg_ks_iy_entry(&host_tabs, rows, x);
                 for (int x = 0; x < rows * 64; x++) dst[rows * 16 + x] = wg_ks_ky_entry(&host_tabs, rows, x);
                 dst += (size_t)rows * 80;
             }
             HIP_TRY(c->lookup.ensure(c->h_lookup.size() * sizeof(wg_d2)));
             HIP_TRY(hipMemcpyAsync(c->lookup.p, c->h_lookup.data(), c->h_lookup.size() * sizeof(wg_d2), hipMemcpyHostToDevice, c->sA));   // h_lookup lives in the context
-            c->lookup_pc = P->pseudo_count; c->lookup_rows[0] = rowsA; c->lookup_rows[1] = rowsB; c->lookup_rows[2] = rowsM;
+            c->lookup_pc = pc;
+            for (int k = 0; k < 3; k++) c->lookup_rows[k] = p.rows[k];
         }
-        caA.tab = c->lookup.as<wg_d2>();
-        caB.tab = caA.tab + (size_t)rowsA * 80;
-        caM.tab = caB.tab + (size_t)rowsB * 80;
+        const wg_d2* tab = c->lookup.as<wg_d2>();
+        for (int k = 0; k < 3; k++) { ca[k].tab = tab; tab += (size_t)p.rows[k] * 80; }
     }
-    const size_t ldsA = (size_t)round_up((int64_t)lds_for(TI, 0, NSA), 16);
-    const size_t ldsB = (size_t)round_up((int64_t)lds_for(WG_WIDE_TS, 1, NSB), 16);
-    const size_t ldsM = (size_t)round_up((int64_t)lds_for(WG_MEDIUM_TS, 2, NSM), 16);
-    const int term_mode = term_modeA;
-
-    // ---- stages: bound the scored-block buffer and overlap scoring (stream A) with the recurrence (stream B) --
-    int n_stages = 1;
-    {
-        const long long bytes = total_pairs * 8;
-        n_stages = (int)std::max<long long>(1, (bytes + c->cost_budget_bytes - 1) / c->cost_budget_bytes);
-        // Few chunks (one rank's share of a sharded genome): the recurrence occupies a fraction of the CUs, so let it
-        // chase the scoring kernel stage by stage (measured: 71 chunks 10.1 -> 8.7 ms, 132 chunks 16.2 -> 15.0 ms).  With
-        // hundreds of chunks k_dp alone (3.9 ms per 60k-site chunk, all chunks at once) beats k_dp competing for CUs.
-        // (the junction patches that ride along in the batch are a few hundred sites each: they do not count)
-        int n_long = 0;
-        for (const ChunkDesc& d : job.h) n_long += d.len >= 8192;
-        // ... unless the recurrence is the longer of the two anyway (a share of a SMALL cohort): beside the scoring kernel a step of the recurrence
-        // takes ~50 ns against ~21 alone, so staging pays only when the scoring lasts longer than the ~30 ns per step it costs: at 7e11
-        // evaluations/s, from ~21,000 evaluations per step of the longest chunk on (round 6, one GPU's share of 8, 71 chunks: x 8 3.69 ms in eight
-        // stages, 2.63 in one; x 32 4.09 against 5.08; profiles/r06_stage_gate_ab.txt)
-        const bool worth = (double)total_pairs * c->n_samples >= (double)job.max_len * c->stage_min_evals_per_step;
-        if (job.max_len >= 8192) n_stages = std::max(n_stages, n_long <= 160 && worth ? 8 : 1);
-        // Many chunks, all windows <= 64: one stage scores and k_dp<7,64> follows alone (1.7 ms exposed).  (Two uneven stages — the
-        // recurrence of the first part of every chunk beside the scoring of the rest — were measured in round 2: 27.1-27.3 ms against 27.0
-        // whatever the split, profiles/r02_tail_split_sweep.txt: the scoring kernel loses what the recurrence no longer shows.)
-        if (c->force_stages > 0) n_stages = c->force_stages;
-        n_stages = std::min<int>(n_stages, std::max(1, (job.max_len + 63) / 64));
-    }
-    // Gated stages (k_stage_gate): the two scoring streams swap roles from stage to stage — the narrow tiles of an even stage on A with its medium / wide tiles
-    // beside them on A2, an odd stage the other way round (a second PAIR of streams was measured: six streams of one priority share hardware queues, every
-    // share lost 10-15 %)
-    const bool all_narrow = Wmax <= WG_NARROW_WMAX;
-    // (one context per device: the streams of several contexts share hardware queues, where a gate could sit ahead of the very launch another context's gate waits for —
-    // the waits are bounded, but nothing would be gained)
-    // A job with medium / wide tiles (its recurrences are the 32-step kernels with the full LDS footprint, which lived on the drains: a share of 8, x 32 with islands,
-    // 5.95 -> 6.4 ms under the gate) is gated only when it is clearly scoring-bound (x 100 with islands: 14.0 -> 13.3 ms): from 100,000 evaluations per step on.
-    const double evals_per_step = (double)total_pairs * c->n_samples / std::max<double>(1.0, (double)job.max_len);
-    const bool gated = c->stage_gate > 0 && n_stages > 1 && (all_narrow || evals_per_step >= c->stage_gate_wide_evals || c->stage_gate_shared) &&
-                       (c->stage_gate_shared || g_live_ctx[c->device & 63].load(std::memory_order_relaxed) == 1);
-    std::vector<int32_t>& sb = c->h_stage_bounds;              // (lives in the context: source of an async upload)
-    {
-        // equal stages but the last (gated jobs only): its recurrence is the only one that runs with the chip to itself, at twice the pace of the others.
-        // Which length: the recurrences of the other stages take ~50 ns per step beside the scoring, so while the scoring of a stage lasts no longer than 1.5 x its
-        // recurrence (at 7e11 evaluations/s: up to ~52,000 evaluations per step of the longest chunk) the chain of recurrences is what the step waits for, and a last
-        // stage three times the others' shortens it (a share of 8, x 32: 4.08 -> 3.79 ms with the gate; equal stages + gate alone: 4.2); a scoring-bound job keeps equal
-        // stages (x 200: 20.4 -> 18.35 ms with the gate, 18.7 with a last stage twice the others').  profiles/r06_stage_gate_ab.txt
-        const int pct = !gated ? 100 : (c->last_stage_pct > 0 ? c->last_stage_pct : (evals_per_step <= 52500.0 ? 300 : 100));
-        const double parts = n_stages > 1 ? (double)(n_stages - 1) + pct / 100.0 : 1.0;
-        const int S = (int)round_up((int64_t)std::ceil((double)job.max_len / parts), 64);
-        n_stages = std::min<int>(n_stages, (job.max_len + S - 1) / S);
-        sb.resize((size_t)n_stages + 1);
-        for (int q = 0; q < n_stages; q++) sb[(size_t)q] = (int32_t)std::min<int64_t>((int64_t)q * S, job.max_len);
-        sb[(size_t)n_stages] = (int32_t)job.max_len;
-    }
-    HIP_TRY(c->plan_sb.ensure(sb.size() * 4));
-    {
-        const void* src = sb.data();
-        if (c->h_sb.ensure(sb.size() * 4)) { memcpy(c->h_sb.p, src, sb.size() * 4); src = c->h_sb.p; }      // (page-locked: the copy does not block)
-        HIP_TRY(hipMemcpyAsync(c->plan_sb.p, src, sb.size() * 4, hipMemcpyHostToDevice, c->sA));
-    }
+    const size_t sb_bytes = (size_t)(n_stages + 1) * 4;
+    HIP_TRY(c->plan_sb.ensure(sb_bytes));
+    const void* src = p.sb;
+    if (c->h_sb.ensure(sb_bytes)) { memcpy(c->h_sb.p, src, sb_bytes); src = c->h_sb.p; }      // (page-locked: the copy does not block)
+    HIP_TRY(hipMemcpyAsync(c->plan_sb.p, src, sb_bytes, hipMemcpyHostToDevice, c->sA));
     HIP_TRY(c->plan_cbase.ensure((size_t)n_stages * nC * 8));
     HIP_TRY(c->plan_cum0.ensure((size_t)n_stages * nC * 4));
     HIP_TRY(c->plan_tbase.ensure((size_t)n_stages * (nC + 1) * 8 * 3));
     HIP_TRY(c->plan_cnt.ensure((size_t)n_stages * nC * 4 * 3));
     HIP_TRY(c->plan_pairs.ensure((size_t)n_stages * 8));
     HIP_TRY(c->plan_tiles.ensure((size_t)n_stages * 8 * 3));
-    PlanArgs pa = {c->plan_sb.as<int32_t>(), TI, WA, TKB, n_stages, WMED};
+    PlanArgs pa = {c->plan_sb.as<int32_t>(), p.TI, p.WA, WG_WIDE_TK, n_stages, p.WMED};
     uint32_t* cntA = c->plan_cnt.as<uint32_t>();
     uint32_t* cntB = cntA + (size_t)n_stages * nC;
     uint32_t* cntM = cntB + (size_t)n_stages * nC;
     int64_t* tbaseA = c->plan_tbase.as<int64_t>();
     int64_t* tbaseB = tbaseA + (size_t)n_stages * (nC + 1);
     int64_t* tbaseM = tbaseB + (size_t)n_stages * (nC + 1);
-    std::vector<int64_t> stage_pairs((size_t)n_stages), stage_tiles((size_t)n_stages * 3, 0);
-    // No window beyond the narrow tiles' (every default-parameter genome outside CpG islands): every aligned group of TI starts is ONE narrow
-    // tile, so the host knows the tile counts without asking the device (round 6: one host round trip less in front of the scoring of every
-    // batch); the scored blocks per stage — what sizes the cost buffer — from the windows' statistics: all of them in one stage, at most
-    // (sites of the stage) x (widest window) otherwise.
-    bool check_div_m = false;
-    if (all_narrow) {
-        for (int stg = 0; stg < n_stages; stg++) {
-            int64_t nt = 0, sites_in = 0;
-            for (const ChunkDesc& d : job.h) {
-                const int64_t s0 = sb[(size_t)stg], s1 = std::min<int64_t>(sb[(size_t)stg + 1], d.len);
-                if (s1 > s0) { nt += (s1 - s0 + TI - 1) / TI; sites_in += s1 - s0; }
-            }
-            stage_tiles[3 * (size_t)stg] = nt;
-            stage_pairs[(size_t)stg] = n_stages == 1 ? total_pairs : std::min<int64_t>(total_pairs, sites_in * std::max(Wmax, 1));
-        }
-        hipLaunchKernelGGL(k_stage_plan, dim3((unsigned)n_stages), dim3(WG_PLAN_BLOCK), 0, c->sA, v, pa, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                           c->plan_cbase.as<int64_t>(), c->plan_cum0.as<uint32_t>(), tbaseA, tbaseB, tbaseM, c->plan_pairs.as<int64_t>(), c->plan_tiles.as<int64_t>());
+    if (!p.all_narrow) {
+        hipLaunchKernelGGL(k_tile_count, dim3((unsigned)nC, (unsigned)n_stages), dim3(WG_BLOCK), 0, c->sA, job.v, pa, cntA, cntB, cntM);
         HIP_TRY(hipGetLastError());
-    } else {
-        hipLaunchKernelGGL(k_tile_count, dim3((unsigned)nC, (unsigned)n_stages), dim3(WG_BLOCK), 0, c->sA, v, pa, cntA, cntB, cntM);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_stage_plan, dim3((unsigned)n_stages), dim3(WG_PLAN_BLOCK), 0, c->sA, v, pa, (const uint32_t*)cntA, (const uint32_t*)cntB, (const uint32_t*)cntM,
-                           c->plan_cbase.as<int64_t>(), c->plan_cum0.as<uint32_t>(), tbaseA, tbaseB, tbaseM, c->plan_pairs.as<int64_t>(), c->plan_tiles.as<int64_t>());
-        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_stage_plan, dim3((unsigned)n_stages), dim3(WG_PLAN_BLOCK), 0, c->sA, job.v, pa, (const uint32_t*)(p.all_narrow ? nullptr : cntA),
+                       (const uint32_t*)(p.all_narrow ? nullptr : cntB), (const uint32_t*)(p.all_narrow ? nullptr : cntM),
+                       c->plan_cbase.as<int64_t>(), c->plan_cum0.as<uint32_t>(), tbaseA, tbaseB, tbaseM, c->plan_pairs.as<int64_t>(), c->plan_tiles.as<int64_t>());
+    HIP_TRY(hipGetLastError());
+    if (!p.all_narrow) {
         // medium tiles and a pseudo count whose short division has not been tried on THEIR operand pairs yet (0 <= nmeth <= ntotal <=
         // 255 * 252: 2.1e9 pairs, ~2 ms, once per context and pseudo count, and only for a job that has windows > 60 at all)
-        check_div_m = c->divs_enabled && term_modeA == 2 && WMED > 0 && c->divs_m_pc != P->pseudo_count;
-        if (check_div_m) {
-            HIP_TRY(c->divcheck.ensure(4));
-            HIP_TRY(hipMemsetAsync(c->divcheck.p, 0, 4, c->sA));
-            const int max_total = 255 * WG_MEDIUM_WMAX;
-            hipLaunchKernelGGL(k_check_div, dim3((unsigned)max_total + 1), dim3(WG_BLOCK), 0, c->sA, P->pseudo_count, P->pseudo_count + P->pseudo_count,
-                               max_total, c->divcheck.as<unsigned int>());
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(reinterpret_cast<JobStatus*>(c->h_status.p) + 3, c->divcheck.p, 4, hipMemcpyDeviceToHost, c->sA));
-        }
-        HIP_TRY(hipMemcpyAsync(stage_pairs.data(), c->plan_pairs.p, (size_t)n_stages * 8, hipMemcpyDeviceToHost, c->sA));
-        HIP_TRY(hipMemcpyAsync(stage_tiles.data(), c->plan_tiles.p, (size_t)n_stages * 24, hipMemcpyDeviceToHost, c->sA));
+        const bool check_div_m = c->divs_enabled && p.term_mode[2] == 2 && p.WMED > 0 && c->divs_m_pc != pc;
+        int rc;
+        if (check_div_m && (rc = queue_div_check(c, pc, WG_MEDIUM_WMAX, hst + 3, err, errlen)) != WGBSSEG_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(p.stage_pairs.data(), c->plan_pairs.p, (size_t)n_stages * 8, hipMemcpyDeviceToHost, c->sA));
+        HIP_TRY(hipMemcpyAsync(p.stage_tiles.data(), c->plan_tiles.p, (size_t)n_stages * 24, hipMemcpyDeviceToHost, c->sA));
         HIP_TRY(hipStreamSynchronize(c->sA));
         if (check_div_m) {
             c->divs_m_ok = *reinterpret_cast<const unsigned int*>(&hst[3]) == 0u;
-            c->divs_m_pc = P->pseudo_count;
-            if (profiling()) fprintf(stderr, "[wgbsseg] short division core for pseudo count %g on the operand pairs of a MEDIUM tile: %s\n", (double)P->pseudo_count, c->divs_m_ok ? "verified on every pair" : "NOT exact, the full core stays");
+            c->divs_m_pc = pc;
+            if (profiling()) fprintf(stderr, "[wgbsseg] short division core for pseudo count %g on the operand pairs of a MEDIUM tile: %s\n", (double)pc, c->divs_m_ok ? "verified on every pair" : "NOT exact, the full core stays");
         }
     }
-    std::vector<int64_t> tileA0((size_t)n_stages + 1, 0), tileB0((size_t)n_stages + 1, 0), tileM0((size_t)n_stages + 1, 0);
-    for (int stg = 0; stg < n_stages; stg++) {
-        tileA0[(size_t)stg + 1] = tileA0[(size_t)stg] + stage_tiles[3 * (size_t)stg];
-        tileB0[(size_t)stg + 1] = tileB0[(size_t)stg] + stage_tiles[3 * (size_t)stg + 1];
-        tileM0[(size_t)stg + 1] = tileM0[(size_t)stg] + stage_tiles[3 * (size_t)stg + 2];
+    for (int k = 0; k < 3; k++) {
+        tile0[k].assign((size_t)n_stages + 1, 0);
+        for (int stg = 0; stg < n_stages; stg++) tile0[k][(size_t)stg + 1] = tile0[k][(size_t)stg] + p.stage_tiles[3 * (size_t)stg + k];
+        if (tile0[k][(size_t)n_stages] > 0x7fffffffLL) { set_err(err, errlen, "too many scoring tiles in one call"); return WGBSSEG_E_ARG; }
     }
-    if (tileA0[(size_t)n_stages] > 0x7fffffffLL || tileB0[(size_t)n_stages] > 0x7fffffffLL || tileM0[(size_t)n_stages] > 0x7fffffffLL) { set_err(err, errlen, "too many scoring tiles in one call"); return WGBSSEG_E_ARG; }
-    HIP_TRY(c->tilesA.ensure((size_t)std::max<int64_t>(1, tileA0[(size_t)n_stages]) * sizeof(TileDesc)));
-    HIP_TRY(c->tilesB.ensure((size_t)std::max<int64_t>(1, tileB0[(size_t)n_stages]) * sizeof(TileDesc)));
-    HIP_TRY(c->tilesM.ensure((size_t)std::max<int64_t>(1, tileM0[(size_t)n_stages]) * sizeof(TileDesc)));
+    for (int k = 0; k < 3; k++) HIP_TRY(c->tiles[k].ensure((size_t)std::max<int64_t>(1, tile0[k][(size_t)n_stages]) * sizeof(TileDesc)));
     for (int stg = 0; stg < n_stages; stg++) {
-        hipLaunchKernelGGL(k_tile_emit, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sA, v, pa, stg, tbaseA, tbaseB, tbaseM,
-                           c->tilesA.as<TileDesc>() + tileA0[(size_t)stg], c->tilesB.as<TileDesc>() + tileB0[(size_t)stg],
-                           c->tilesM.as<TileDesc>() + tileM0[(size_t)stg]);
+        hipLaunchKernelGGL(k_tile_emit, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sA, job.v, pa, stg, tbaseA, tbaseB, tbaseM,
+                           c->tiles[0].as<TileDesc>() + tile0[0][(size_t)stg], c->tiles[1].as<TileDesc>() + tile0[1][(size_t)stg],
+                           c->tiles[2].as<TileDesc>() + tile0[2][(size_t)stg]);
         HIP_TRY(hipGetLastError());
     }
-    if (gated) {
+    if (p.gated) {
         HIP_TRY(c->stage_ctr.ensure((size_t)n_stages * 4));
         HIP_TRY(hipMemsetAsync(c->stage_ctr.p, 0, (size_t)n_stages * 4, c->sA));
     }
-    HIP_TRY(hipEventRecord(c->ev[3], c->sA));
-    if (gated) HIP_TRY(hipStreamWaitEvent(c->sA2, c->ev[3], 0));
-    if (validate_late) {                                        // (WGBSSEG_SCAN_AFTER=2) k_validate behind the tile plan
-        HIP_TRY(hipStreamWaitEvent(sS, c->ev[3], 0));
-        rc = queue_validate_now();
-        if (rc != WGBSSEG_OK) return rc;
-        HIP_TRY(close_scan_stream());
-    }
-    if (host_marks) hm[4] = wall_s();
-    int64_t max_stage_pairs = 1;
-    for (auto x : stage_pairs) max_stage_pairs = std::max(max_stage_pairs, x);
-    const int nbuf = n_stages > 1 ? (gated && n_stages > 2 ? 3 : 2) : 1;      // (gated: a stage's scoring must not wait for the recurrence two stages back when its gate opens)
-    for (int b = 0; b < nbuf; b++) HIP_TRY(c->cost[b].ensure((size_t)max_stage_pairs * 8));
-    // k_dp: 64-step batches when no window of the job exceeds 64 sites; otherwise 32-step batches with a second pending
-    // register per lane and, for blocks longer than 128 sites, a ring of pending maxima per chunk in global memory
-    int dp_mode = Wmax > 512 ? 2 : (Wmax > 64 ? 1 : 0);           // 0: <3,64>  1: <3,32>  2: <15,32> (deep windows: more workers)
-    if (c->force_dp_mode > dp_mode) dp_mode = c->force_dp_mode;
-    const int ringN = dp_mode ? ceil_pow2(Wmax + 128) : 0;
-    const int64_t state_stride = round_up(WG_DP_STATE_HDR + (int64_t)ringN + (ringN + 1) / 2, 2);   // doubles per chunk
-    HIP_TRY(c->dpstate.ensure((size_t)nC * (size_t)state_stride * 8));
-    HIP_TRY(c->tmp_borders.ensure((size_t)(Jp + nC) * 4));
+    HIP_TRY(hipEventRecord(c->ev[EV_PLAN], c->sA));
+    if (p.gated) HIP_TRY(hipStreamWaitEvent(c->sA2, c->ev[EV_PLAN], 0));
+    mark(4);
+    return WGBSSEG_OK;
+}
+
+int Batch::stages(char* err, size_t errlen)
+{
+    const BatchPlan& p = plan;
+    const JobView& v = job.v;
+    const int n_stages = p.n_stages;
+    const int64_t max_stage_pairs = std::max<int64_t>(1, *std::max_element(p.stage_pairs.begin(), p.stage_pairs.end()));
+    for (int k = 0; k < p.nbuf; k++) HIP_TRY(c->cost[k].ensure((size_t)max_stage_pairs * 8));
+    HIP_TRY(c->dpstate.ensure((size_t)nC * (size_t)p.state_stride * 8));
+    HIP_TRY(c->tmp_borders.ensure((size_t)(job.sites_padded + nC) * 4));
     HIP_TRY(c->nb.ensure((size_t)nC * 4));
     // the batch's result on the device: the CSR offsets of the chunks' border lists, then the lists — one buffer, so that a small batch
     // (a follow-up batch of junction patches) comes home in ONE copy
-    const size_t out_head = (size_t)round_up((int64_t)(nC + 1) * 8, 16);
+    out_head = (size_t)round_up((int64_t)(nC + 1) * 8, 16);
     c->out_par ^= 1;                                             // (the other buffer may still be feeding k_copy_out of the previous batch)
-    DevBuf& outb = c->out_borders[c->out_par];
-    HIP_TRY(outb.ensure(out_head + (size_t)(J + nC) * 4));
-    int64_t* const d_boff = outb.as<int64_t>();
-    int32_t* const d_bord = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(outb.p) + out_head);
-    grow_events(c->ev_cost0, n_stages); grow_events(c->ev_cost1, n_stages);
-    grow_events(c->ev_dp0, n_stages); grow_events(c->ev_dp1, n_stages);
-    grow_events(c->ev_fork, n_stages); grow_events(c->ev_join, n_stages);
+    outb = &c->out_borders[c->out_par];
+    HIP_TRY(outb->ensure(out_head + (size_t)(J + nC) * 4));
+    for (auto* evs : {&c->ev_cost0, &c->ev_cost1, &c->ev_dp0, &c->ev_dp1, &c->ev_fork, &c->ev_join}) grow_events(*evs, n_stages);
     StageView sv;
-    sv.cbase = c->plan_cbase.as<int64_t>(); sv.cum0 = c->plan_cum0.as<uint32_t>(); sv.tbaseA = tbaseA; sv.tbaseB = tbaseB;
+    sv.cbase = c->plan_cbase.as<int64_t>(); sv.cum0 = c->plan_cum0.as<uint32_t>();
+    sv.tbaseA = c->plan_tbase.as<int64_t>(); sv.tbaseB = sv.tbaseA + (size_t)n_stages * (nC + 1);
     sv.sb = c->plan_sb.as<int32_t>();
-    // LDS of k_dp: two arranged batches (64 steps x 64 lanes, or 32 steps x 64 lanes x {A, B}) + M ring + fetched ring entries + flags + ring of windows / row offsets
-    const int dp_wlean_off = (getenv("WGBSSEG_DP_WLEAN") && atoi(getenv("WGBSSEG_DP_WLEAN")) == 0) ? 1 : 0;      // 0: narrow batches of a wide job on the generic step (A/B, tests; read per call)
-    DpArgs da = {ringN, {dp_wlean_off, 0, 0}};
+    DpArgs da = {p.ringN, {c->dp_wlean ? 0 : 1, 0, 0}};       // pad[0] = 1: the narrow batches of a wide job on the generic step
 #ifdef WGBSSEG_DP_TIMING
     if (const char* e = getenv("WGBSSEG_DP_DEBUG")) da.pad[1] = atoi(e);      // timing builds only: see k_dp (results are WRONG in these modes)
 #endif
-    c->last_dp_chunks = nC; c->last_dp_stride = state_stride;
+    c->last_dp_chunks = nC; c->last_dp_stride = p.state_stride;
+    // LDS of k_dp: two arranged batches (64 steps x 64 lanes, or 32 steps x 64 lanes x {A, B}) + M ring + fetched ring entries + flags + ring of windows / row offsets
     const size_t lds_dp = 2 * 4096 * 8 + 128 * 8 + 64 * 12 + 16 + 1024 * 6;
-    if (st.wide_units) HIP_TRY(hipStreamWaitEvent(c->sA, c->ev[2], 0));      // wide tiles read the carries: scoring after the scan
-    if (st.wide_units && gated) HIP_TRY(hipStreamWaitEvent(c->sA2, c->ev[2], 0));
+    double* const dps = c->dpstate.as<double>();
+    if (st.wide_units) HIP_TRY(hipStreamWaitEvent(c->sA, c->ev[EV_SCAN_END], 0));      // wide tiles read the carries: scoring after the scan
+    if (st.wide_units && p.gated) HIP_TRY(hipStreamWaitEvent(c->sA2, c->ev[EV_SCAN_END], 0));
     // Two scoring streams.  A scoring launch ends in a tail of partly filled workgroup slots (1280 on the chip), and a stage
     // with more than one tile class pays one per class: there the medium and wide tiles go to a second stream, beside the
     // narrow ones (they write disjoint rows of the cost buffer), forked off the first stream when the stage may begin
     // and joined before the stage's end is recorded (ev_fork / ev_join).  Measured, islands x32: scoring 29.49 -> 28.70 ms, x8 9.35 -> 9.14 ms.
-    // Alternating the STAGES of a staged job between the streams was measured too and is not done: the one-eighth share
-    // (8 stages) scored in 3.40 instead of 3.49 ms but its recurrences, which run beside the next stage's scoring, fell behind
-    // (step 4.56 -> 4.79 ms); x200 / x512 gained 0.1-0.5 %.
-    const bool two_cost_streams = true;
+    // The STAGES of a staged job alternate between the two streams only behind k_stage_gate (gated jobs, plan_stages): without the gate it
+    // was measured and lost — the one-eighth share (8 stages) scored in 3.40 instead of 3.49 ms but its recurrences, which run beside the
+    // next stage's scoring, fell behind (step 4.56 -> 4.79 ms); x200 / x512 gained 0.1-0.5 %.
+    const bool divsA = c->divs_enabled && c->divs_ok && c->divs_pc == P.pseudo_count;
+    const bool divsM = c->divs_enabled && c->divs_m_ok && c->divs_m_pc == P.pseudo_count;
+    const int fast[3] = {p.term_mode[0] == 2 && divsA ? 3 : p.term_mode[0], p.term_mode[1], p.term_mode[2] == 2 && divsM ? 3 : p.term_mode[2]};
     for (int stg = 0; stg < n_stages; stg++) {
-        hipStream_t const sP = gated && (stg & 1) ? c->sA2 : c->sA;
+        const int64_t* const nt = &p.stage_tiles[3 * (size_t)stg];      // the stage's tiles per class
+        hipStream_t const sP = p.gated && (stg & 1) ? c->sA2 : c->sA;
         sv.stage = stg;
-        double* cbuf = c->cost[stg % nbuf].as<double>();
-        const bool side = two_cost_streams && stage_tiles[3 * (size_t)stg] > 0 && (stage_tiles[3 * (size_t)stg + 1] > 0 || stage_tiles[3 * (size_t)stg + 2] > 0);
-        hipStream_t const sSide = side ? (gated && (stg & 1) ? c->sA : c->sA2) : sP;
-        if (stg >= nbuf) HIP_TRY(hipStreamWaitEvent(sP, c->ev_dp1[stg - nbuf], 0));   // buffer free again
-        if (gated) {
-            const int64_t before = stg > 0 ? stage_tiles[3 * (size_t)stg - 3] + stage_tiles[3 * (size_t)stg - 2] + stage_tiles[3 * (size_t)stg - 1] : 0;      // tiles of every class
+        double* cbuf = c->cost[stg % p.nbuf].as<double>();
+        const bool side = nt[0] > 0 && (nt[1] > 0 || nt[2] > 0);
+        hipStream_t const sSide = side ? (p.gated && (stg & 1) ? c->sA : c->sA2) : sP;
+        if (stg >= p.nbuf) HIP_TRY(hipStreamWaitEvent(sP, c->ev_dp1[stg - p.nbuf], 0));   // buffer free again
+        if (p.gated) {
+            const int64_t before = stg > 0 ? nt[-3] + nt[-2] + nt[-1] : 0;      // the previous stage's tiles of every class
             if (before > 0) {
                 // the wait's bound: ten times what the stage before should take at 5e11 evaluations/s (its scored blocks are an upper bound for an all-narrow job), between
                 // 5 ms and 2 s — a gate that opens early lets two stages interleave (the recurrence of the first starts late); one that waits for a launch which some other
                 // context's work holds up (a context created on this device while the batch is in flight) gives up after a time in proportion to the job
-                const double est_s = 10.0 * (double)stage_pairs[(size_t)stg - 1] * c->n_samples / 5e11;
+                const double est_s = 10.0 * (double)p.stage_pairs[(size_t)stg - 1] * c->n_samples / 5e11;
                 const long long max_ticks = (long long)(1e8 * std::min(2.0, std::max(0.005, est_s)));
                 hipLaunchKernelGGL(k_stage_gate, dim3(1), dim3(64), 0, sP, (const uint32_t*)(c->stage_ctr.as<uint32_t>() + (stg - 1)),
                                    (uint32_t)std::max<int64_t>(1, before - c->stage_gate), max_ticks);
                 HIP_TRY(hipGetLastError());
             }
-            caA.finished = caB.finished = caM.finished = c->stage_ctr.as<uint32_t>() + stg;
+            for (CostArgs& a : ca) a.finished = c->stage_ctr.as<uint32_t>() + stg;
         }
         HIP_TRY(hipEventRecord(c->ev_cost0[stg], sP));
         if (side) { HIP_TRY(hipEventRecord(c->ev_fork[stg], sP)); HIP_TRY(hipStreamWaitEvent(sSide, c->ev_fork[stg], 0)); }
-        if (stage_tiles[3 * (size_t)stg] > 0) {
-            const TileDesc* td = c->tilesA.as<TileDesc>() + tileA0[(size_t)stg];
-            const int64_t nt = stage_tiles[3 * (size_t)stg];
-            const bool divs = c->divs_enabled && c->divs_ok && c->divs_pc == P->pseudo_count;
-            hipError_t e = term_mode == 2 ? (divs ? launch_cost_ti<3>(TI, false, v, sv, caA, td, nt, cbuf, ldsA, sP)
-                                                  : launch_cost_ti<2>(TI, false, v, sv, caA, td, nt, cbuf, ldsA, sP))
-                         : (term_mode == 1 ? launch_cost_ti<1>(TI, false, v, sv, caA, td, nt, cbuf, ldsA, sP)
-                                           : launch_cost_ti<0>(TI, false, v, sv, caA, td, nt, cbuf, ldsA, sP));
-            HIP_TRY(e);
-        }
-        if (stage_tiles[3 * (size_t)stg + 2] > 0) {                  // medium tiles: the narrow tiles' arithmetic on rows of 269 entries
-            const TileDesc* td = c->tilesM.as<TileDesc>() + tileM0[(size_t)stg];
-            const int64_t nt = stage_tiles[3 * (size_t)stg + 2];
-            const bool divs = c->divs_enabled && c->divs_m_ok && c->divs_m_pc == P->pseudo_count;
-            hipError_t e = term_mode == 2 ? (divs ? launch_cost_ti<3>(-1, false, v, sv, caM, td, nt, cbuf, ldsM, sSide)
-                                                  : launch_cost_ti<2>(-1, false, v, sv, caM, td, nt, cbuf, ldsM, sSide))
-                         : (term_mode == 1 ? launch_cost_ti<1>(-1, false, v, sv, caM, td, nt, cbuf, ldsM, sSide)
-                                           : launch_cost_ti<0>(-1, false, v, sv, caM, td, nt, cbuf, ldsM, sSide));
-            HIP_TRY(e);
-        }
-        if (stage_tiles[3 * (size_t)stg + 1] > 0) {
-            const TileDesc* td = c->tilesB.as<TileDesc>() + tileB0[(size_t)stg];
-            const int64_t nt = stage_tiles[3 * (size_t)stg + 1];
-            hipError_t e = term_modeB == 2 ? launch_cost_ti<2>(TI, true, v, sv, caB, td, nt, cbuf, ldsB, sSide)
-                         : (term_modeB == 1 ? launch_cost_ti<1>(TI, true, v, sv, caB, td, nt, cbuf, ldsB, sSide)
-                                           : launch_cost_ti<0>(TI, true, v, sv, caB, td, nt, cbuf, ldsB, sSide));
-            HIP_TRY(e);
-        }
+        for (int k : {0, 2, 1})          // narrow tiles on the stage's stream; medium (the narrow tiles' arithmetic on rows of 269 entries), then wide ones beside them
+            if (nt[k] > 0)
+                HIP_TRY(launch_cost_class(k, fast[k], p.TI, v, sv, ca[k], c->tiles[k].as<TileDesc>() + tile0[k][(size_t)stg], nt[k], cbuf, p.lds[k], k == 0 ? sP : sSide));
         if (side) { HIP_TRY(hipEventRecord(c->ev_join[stg], sSide)); HIP_TRY(hipStreamWaitEvent(sP, c->ev_join[stg], 0)); }
         HIP_TRY(hipEventRecord(c->ev_cost1[stg], sP));
         HIP_TRY(hipStreamWaitEvent(c->sB, c->ev_cost1[stg], 0));
@@ -1375,26 +1371,31 @@ int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32
         // the next one: whenever the call is staged.  Windows <= 60 (no wide tile in the job): the step with the batched bookkeeping, 6.75 instead
         // of 10 VALU instructions.
         // the LAST stage's recurrence has the chip to itself: the 64-step-batch kernel is twice as fast there
-        const bool dp16 = dp_mode == 0 && n_stages > 1 && stg + 1 < n_stages;
-        if (dp16)                            hipLaunchKernelGGL((k_dp16<3>), dim3((unsigned)nC), dim3(64 * 4), (size_t)(2 * 16 * 64 * 8 + WG_DP_META_RING * 6), c->sB, v, sv, cbuf, c->dpstate.as<double>(), state_stride);
-        else if (dp_mode == 0 && Wmax <= WG_NARROW_WMAX)
-                                             hipLaunchKernelGGL((k_dp<7, 64, true>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, c->dpstate.as<double>(), state_stride);
-        else if (dp_mode == 0)               hipLaunchKernelGGL((k_dp<7, 64>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, c->dpstate.as<double>(), state_stride);
-        else if (dp_mode == 1) hipLaunchKernelGGL((k_dp<7, 32>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, c->dpstate.as<double>(), state_stride);
-        else                   hipLaunchKernelGGL((k_dp<15, 32>), dim3((unsigned)nC), dim3(64 * 16), lds_dp, c->sB, v, sv, cbuf, da, c->dpstate.as<double>(), state_stride);
+        const bool dp16 = p.dp_mode == 0 && n_stages > 1 && stg + 1 < n_stages;
+        if (dp16)                                  hipLaunchKernelGGL((k_dp16<3>), dim3((unsigned)nC), dim3(64 * 4), (size_t)(2 * 16 * 64 * 8 + WG_DP_META_RING * 6), c->sB, v, sv, cbuf, dps, p.state_stride);
+        else if (p.dp_mode == 0 && p.all_narrow)   hipLaunchKernelGGL((k_dp<7, 64, true>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, dps, p.state_stride);
+        else if (p.dp_mode == 0)                   hipLaunchKernelGGL((k_dp<7, 64>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, dps, p.state_stride);
+        else if (p.dp_mode == 1)                   hipLaunchKernelGGL((k_dp<7, 32>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, dps, p.state_stride);
+        else                                       hipLaunchKernelGGL((k_dp<15, 32>), dim3((unsigned)nC), dim3(64 * 16), lds_dp, c->sB, v, sv, cbuf, da, dps, p.state_stride);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->ev_dp1[stg], c->sB));
     }
-    // ---- traceback, compaction, copy out ---------------------------------------------------------------------
-    HIP_TRY(hipEventRecord(c->ev[4], c->sB));
-    hipLaunchKernelGGL(k_trace, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sB, v, c->tmp_borders.as<int32_t>(), c->nb.as<int32_t>());
+    return WGBSSEG_OK;
+}
+
+int Batch::deliver(char* err, size_t errlen)
+{
+    int64_t* const d_boff = outb->as<int64_t>();
+    int32_t* const d_bord = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(outb->p) + out_head);
+    HIP_TRY(hipEventRecord(c->ev[EV_TRACE0], c->sB));
+    hipLaunchKernelGGL(k_trace, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sB, job.v, c->tmp_borders.as<int32_t>(), c->nb.as<int32_t>());
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_border_offsets, dim3(1), dim3(WG_BLOCK), 0, c->sB, c->nb.as<int32_t>(), nC, d_boff);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_gather_borders, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sB, v, c->tmp_borders.as<int32_t>(), c->nb.as<int32_t>(),
+    hipLaunchKernelGGL(k_gather_borders, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sB, job.v, c->tmp_borders.as<int32_t>(), c->nb.as<int32_t>(),
                        (const int64_t*)d_boff, d_bord);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[5], c->sB));
+    HIP_TRY(hipEventRecord(c->ev[EV_TRACE1], c->sB));
     // A chunk has at most len + 1 borders: a batch whose upper bound is small comes home in one copy (offsets + lists, through a page-locked
     // landing area); a large one sends the offsets first and then exactly the lists — or, when the caller can use them (EarlyOut), the offsets
     // with the edges of the leading items' lists, then the other items' lists, and the leading lists by k_copy_out behind the caller's back.
@@ -1411,30 +1412,30 @@ int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32
         hipLaunchKernelGGL(k_gather_edges, dim3((unsigned)nC), dim3(WG_BLOCK), 0, c->sB, (const int64_t*)d_boff, (const int32_t*)d_bord, (int)n_lead, c->edges.as<int32_t>(),
                            c->edges.as<int32_t>() + edge_bytes / 4);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(c->ev[5], c->sB));
+        HIP_TRY(hipEventRecord(c->ev[EV_TRACE1], c->sB));
     }
     if (!c->h_out.ensure((small ? small_bytes : out_head) + edge_bytes + rest_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
-    HIP_TRY(hipMemcpyAsync(c->h_out.p, outb.p, small ? small_bytes : (size_t)(nC + 1) * 8, hipMemcpyDeviceToHost, c->sB));
+    HIP_TRY(hipMemcpyAsync(c->h_out.p, outb->p, small ? small_bytes : (size_t)(nC + 1) * 8, hipMemcpyDeviceToHost, c->sB));
     if (n_lead) HIP_TRY(hipMemcpyAsync(reinterpret_cast<char*>(c->h_out.p) + out_head, c->edges.p, edge_bytes + rest_bytes, hipMemcpyDeviceToHost, c->sB));
-    if (small || n_lead) HIP_TRY(hipEventRecord(c->ev[6], c->sB));
-    if (host_marks) hm[5] = wall_s();
+    if (small || n_lead) HIP_TRY(hipEventRecord(c->ev[EV_HOME], c->sB));
+    mark(5);
     if (J >= (1 << 20)) {
         // a large batch: when its recurrence is done, ~0.2 ms of traceback and copies remain — just the time the host threads
         // of the junction stitching need to wake up (stitch.h)
-        HIP_TRY(hipEventSynchronize(c->ev_dp1[n_stages - 1]));
+        HIP_TRY(hipEventSynchronize(c->ev_dp1[plan.n_stages - 1]));
         wgstitch::Pool::get().heat();
     }
     HIP_TRY(hipStreamSynchronize(c->sB));
     memcpy(borders_off, c->h_out.p, (size_t)(nC + 1) * 8);
     const int64_t total_b = borders_off[nC];
-    int32_t* borders_out = alloc(total_b);
+    int32_t* borders_out = (*alloc)(total_b);
     if (!borders_out) { set_err(err, errlen, "borders_out too small: need %lld ints", (long long)total_b); return WGBSSEG_E_CAPACITY; }
     if (small) memcpy(borders_out, reinterpret_cast<const char*>(c->h_out.p) + out_head, (size_t)total_b * 4);
     else if (n_lead && early->dest_device_visible && (reinterpret_cast<uintptr_t>(borders_out) & 15) == 0) {
         const int64_t lead_b = borders_off[n_lead];              // the leading items' borders: [0, lead_b) of the lists
         // on the scan stream: idle by now, the lowest priority (the follow-up batch's kernels go first) and — as the one stream of its priority — a hardware
         // queue of its own (on a stream of the scoring streams' priority k_copy_out shared a queue with them: the follow-up batch's first kernel waited for it)
-        HIP_TRY(hipStreamWaitEvent(c->sC, c->ev[5], 0));
+        HIP_TRY(hipStreamWaitEvent(c->sC, c->ev[EV_TRACE1], 0));
         hipLaunchKernelGGL(k_copy_out, dim3(512), dim3(WG_BLOCK), 0, c->sC, (const int32_t*)d_bord, borders_out, lead_b);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(c->evD, c->sC));
@@ -1444,10 +1445,10 @@ int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32
         early->pending = true;
     } else {
         HIP_TRY(hipMemcpyAsync(borders_out, d_bord, (size_t)total_b * 4, hipMemcpyDeviceToHost, c->sB));
-        HIP_TRY(hipEventRecord(c->ev[6], c->sB));
+        HIP_TRY(hipEventRecord(c->ev[EV_HOME], c->sB));
         HIP_TRY(hipStreamSynchronize(c->sB));
     }
-    if (host_marks) hm[6] = wall_s();
+    mark(6);
     // (events, not stream synchronisations: the scoring stream's work precedes the recurrence's by its events, and the scan stream ends in evS — a stream
     // synchronisation queues a marker of its own, which waited ~0.2 ms behind k_copy_out when the two streams shared a hardware queue)
     HIP_TRY(hipEventSynchronize(c->evS));
@@ -1455,55 +1456,60 @@ int segment_chunks_impl(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32
     // of the batch; every kernel downstream of the counts is safe on such data (LDS indices out of a table's range read zeros,
     // the traceback bounds its steps) and what it produced is dropped here.
     if (hst[2].first_bad != ~0ULL) return report_bad_site(c, hst[2], err, errlen);
+    return WGBSSEG_OK;
+}
 
-    // ---- timings ---------------------------------------------------------------------------------------------
-    static const bool timeline = getenv("WGBSSEG_PROFILE") && atoi(getenv("WGBSSEG_PROFILE")) >= 2;
-    if (timeline) {       // device time line of the batch, ms after its first event (scoring / recurrence: first and last stage)
-        auto at = [&](hipEvent_t e) { float x = 0; (void)hipEventElapsedTime(&x, c->ev[0], e); return (double)x; };
+int Batch::timings(char* err, size_t errlen)
+{
+    const int n_stages = plan.n_stages;
+    const int64_t total_pairs = (int64_t)st.total_pairs;
+    if (marks) {       // device time line of the batch, ms after its first event (scoring / recurrence: first and last stage)
+        auto at = [&](hipEvent_t e) { float x = 0; (void)hipEventElapsedTime(&x, c->ev[EV_BEGIN], e); return (double)x; };
         if (n_stages > 1) {
-            fprintf(stderr, "[wgbsseg] %d stages%s, bounds", n_stages, gated ? " (gated: alternating scoring streams)" : "");
-            for (int q = 0; q <= n_stages; q++) fprintf(stderr, " %d", (int)sb[(size_t)q]);
+            fprintf(stderr, "[wgbsseg] %d stages%s, bounds", n_stages, plan.gated ? " (gated: alternating scoring streams)" : "");
+            for (int q = 0; q <= n_stages; q++) fprintf(stderr, " %d", (int)plan.sb[q]);
             fprintf(stderr, "\n");
         }
         fprintf(stderr, "[wgbsseg] batch of %d chunks, %lld sites: windows done %.3f | stats copied %.3f | scan pass (its own stream) %.3f .. %.3f | plan + tiles done %.3f | "
                 "scoring %.3f .. %.3f | recurrence %.3f .. %.3f | trace %.3f .. %.3f | borders on the host %.3f\n", nC, (long long)J,
-                at(c->ev[1]), at(c->ev[7]), at(c->ev[8]), at(c->ev[2]), at(c->ev[3]), at(c->ev_cost0[0]), at(c->ev_cost1[n_stages - 1]),
-                at(c->ev_dp0[0]), at(c->ev_dp1[n_stages - 1]), at(c->ev[4]), at(c->ev[5]), at(c->ev[6]));
+                at(c->ev[EV_WINDOWS]), at(c->ev[EV_STATS]), at(c->ev[EV_VALIDATE0]), at(c->ev[EV_SCAN_END]), at(c->ev[EV_PLAN]), at(c->ev_cost0[0]), at(c->ev_cost1[n_stages - 1]),
+                at(c->ev_dp0[0]), at(c->ev_dp1[n_stages - 1]), at(c->ev[EV_TRACE0]), at(c->ev[EV_TRACE1]), at(c->ev[EV_HOME]));
     }
     wgbsseg_timings& T = c->tim;
     if (!c->accumulate) memset(&T, 0, sizeof(T));
     float ms = 0;
     // the scan pass = k_scan for a job with wide tiles (it reads every chunk row of the batch, after k_validate has read the same bytes), k_validate otherwise
-    if (st.wide_units) HIP_TRY(hipEventElapsedTime(&ms, c->ev[10], c->ev[11])); else HIP_TRY(hipEventElapsedTime(&ms, c->ev[8], c->ev[9]));
+    if (st.wide_units) HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_SCAN0], c->ev[EV_SCAN1])); else HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_VALIDATE0], c->ev[EV_VALIDATE1]));
     T.scan_ms += ms;
     // algorithmic bytes of the pass: with wide units k_scan reads every chunk row of the batch; without, k_validate reads the
     // batch's not-yet-validated sites once
     const int64_t scan_bytes = 2 * (st.wide_units ? J : job.val_sites) * c->n_samples;
     if (scan_bytes > T.scan_main_bytes) { T.scan_main_bytes = scan_bytes; T.scan_main_ms = ms; }
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1])); T.window_ms += ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_BEGIN], c->ev[EV_WINDOWS])); T.window_ms += ms;
     float cost_end = 0;      // scoring time = the union of the stages' intervals (neighbouring stages overlap on the two scoring streams)
     for (int stg = 0; stg < n_stages; stg++) {
         float t0 = 0, t1 = 0;
-        HIP_TRY(hipEventElapsedTime(&t0, c->ev[0], c->ev_cost0[stg])); HIP_TRY(hipEventElapsedTime(&t1, c->ev[0], c->ev_cost1[stg]));
+        HIP_TRY(hipEventElapsedTime(&t0, c->ev[EV_BEGIN], c->ev_cost0[stg])); HIP_TRY(hipEventElapsedTime(&t1, c->ev[EV_BEGIN], c->ev_cost1[stg]));
         if (t1 > std::max(t0, cost_end)) T.cost_ms += t1 - std::max(t0, cost_end);
         cost_end = std::max(cost_end, t1);
         HIP_TRY(hipEventElapsedTime(&ms, c->ev_dp0[stg], c->ev_dp1[stg])); T.dp_ms += ms;
     }
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[4], c->ev[5])); T.trace_ms += ms;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[6])); T.total_ms += ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_TRACE0], c->ev[EV_TRACE1])); T.trace_ms += ms;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[EV_BEGIN], c->ev[EV_HOME])); T.total_ms += ms;
     T.sites += J; T.pairs += total_pairs; T.evals += total_pairs * c->n_samples;
-    T.scan_bytes += scan_bytes; T.max_window = std::max<int32_t>(T.max_window, Wmax);
+    T.scan_bytes += scan_bytes; T.max_window = std::max<int32_t>(T.max_window, plan.Wmax);
     T.n_stages = std::max<int32_t>(T.n_stages, n_stages); T.scan_launches += 1;
-    if (term_mode == 2 && c->divs_enabled && c->divs_ok && c->divs_pc == P->pseudo_count) T.div_short = 1;
+    if (plan.term_mode[0] == 2 && c->divs_enabled && c->divs_ok && c->divs_pc == P.pseudo_count) T.div_short = 1;
     c->last_sites = J; c->last_pairs = total_pairs; c->last_stages = n_stages; c->last_valid = true;
     c->batch_open = false;
-    if (host_marks) {
+    if (marks) {
         hm[7] = wall_s();
         fprintf(stderr, "[wgbsseg]   host clock of the batch, us after entry: tables up %.0f | windows queued %.0f | statistics here %.0f | scoring's tiles queued %.0f | everything queued %.0f | results here %.0f | return %.0f\n",
                 (hm[1] - hm[0]) * 1e6, (hm[2] - hm[0]) * 1e6, (hm[3] - hm[0]) * 1e6, (hm[4] - hm[0]) * 1e6, (hm[5] - hm[0]) * 1e6, (hm[6] - hm[0]) * 1e6, (hm[7] - hm[0]) * 1e6);
     }
     return WGBSSEG_OK;
 }
+
 }  // namespace
 
 extern "C" {
@@ -1569,11 +1575,6 @@ int map_stitch_rc(int rc, const std::string& msg, char* err, size_t errlen)
     set_err(err, errlen, "%s", msg.c_str());
     return rc == wgstitch::E_CAPACITY ? WGBSSEG_E_CAPACITY : (rc < -1 ? rc : WGBSSEG_E_ARG);
 }
-bool speculation_on()
-{
-    static const bool on = !(getenv("WGBSSEG_NO_SPECULATION") && atoi(getenv("WGBSSEG_NO_SPECULATION")));
-    return on;
-}
 }  // namespace
 
 extern "C" {
@@ -1595,9 +1596,8 @@ int wgbsseg_segment_regions(wgbsseg_ctx* c, const int64_t* region_start, const i
         const int32_t* flat = nullptr;
         std::unique_ptr<int32_t[]> owned;
         // the stitcher can start on the edges of the chunks' lists (res.n_lead = its number of chunks): ask for early delivery
-        static const bool early_on = !(getenv("WGBSSEG_NO_EARLY") && atoi(getenv("WGBSSEG_NO_EARLY")));
         EarlyOut eo;
-        eo.n_lead = early_on ? res.n_lead : 0;
+        eo.n_lead = c->early ? res.n_lead : 0;
         const int rc = run_ctx_batch(c, st0, ln, P, n_batches, n_batches > 0, flat, off, owned, msg, eo.n_lead > 0 ? &eo : nullptr);
         if (rc != WGBSSEG_OK) return rc;
         if (owned) res.owned.push_back(std::move(owned));
@@ -1616,7 +1616,7 @@ int wgbsseg_segment_regions(wgbsseg_ctx* c, const int64_t* region_start, const i
     };
     std::string msg;
     int rc = wgstitch::segment_regions(region_start, region_end, n_regions, chunk_size, run_batch, borders_out, borders_cap,
-                                       borders_off, stats, msg, speculation_on());
+                                       borders_off, stats, msg, c->speculate);
     {   // (an error path of the stitcher may have left the first batch's lists on their way: nothing may write into the context's buffers after this call)
         char e[256] = {0};
         const int r2 = wait_pending_output(c, e, sizeof e);
@@ -2262,7 +2262,7 @@ int wgbsseg_group_segment_region_range(wgbsseg_group* g, int64_t first_region, i
     };
     std::string msg;
     const int rc = wgstitch::segment_regions(g->rs.data() + first_region, g->re.data() + first_region, end_region - first_region, g->chunk_size, run_batch, borders_out,
-                                             borders_cap, borders_off, stats, msg, speculation_on());
+                                             borders_cap, borders_off, stats, msg, g->shares[0]->speculate);
     if (g->streaming && (end_region == (int64_t)g->rs.size() || rc != 0)) {      // every byte has been consumed by now; collect the uploaders
         char eb[512] = {0};
         const int lrc = wgbsseg_group_load_wait(g, eb, sizeof(eb));
