@@ -625,3 +625,203 @@ def test_dump_result_csr_reports_before_a_failing_writer(synth_world, tmp_path):
         with pytest.raises(RuntimeError):
             sbc.dump_result_csr(np.array([1, 9, 5, 12], dtype=np.int32), np.array([0, 4], dtype=np.int64))
     assert 'found' not in err.getvalue() and sbc.report == {}
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the driver's host logic behind S.RegionEngine — borders as one CSR or as slices of it, the one BED writer, the rerun on one GPU — with
+# engines that need no device
+# ------------------------------------------------------------------------------------------------------------
+HALO_OUTGROWN = 'junction patch 5 .. 9 is not resident on any single share (halo 10)'
+
+
+class OracleRegionEngine(S.RegionEngine):
+    """Test-only engine with the driver's own interface over the oracle chunk engine above and the library's stitching tree
+    (_lib.stitch_regions, no speculation).  Slices are cut by region count.  Regions never interact (segment.py:84-86), so the list of a
+    region is computed once per parameter set and kept for the other runs of the module.  `outgrown`: the call (its second slice, when
+    there is one) fails the way a share group does when a junction patch outgrows the halo between two shares."""
+    lists = {}
+
+    def __init__(self, betas, loci, outgrown=False):
+        self.chunks, self.outgrown, self.closed = OracleEngine(betas, loci), outgrown, 0
+
+    def _csr(self, regions, chunk_size, params):
+        from wgbs_tools_amd import _lib
+        key = lambda r: (tuple(r), chunk_size, params['pcount'], params['max_cpg'], params['max_bp'])
+        todo = [r for r in regions if key(r) not in self.lists]
+        if todo:
+            res, _ = _lib.stitch_regions(todo, chunk_size, lambda sites: self.chunks.segment_many(sites, params), speculate=False)
+            self.lists.update(zip(map(key, todo), res))
+        got = [self.lists[key(r)] for r in regions]
+        return np.concatenate(got).astype(np.int32), np.concatenate([[0], np.cumsum([len(b) for b in got])]).astype(np.int64)
+
+    def segment_regions_csr(self, regions, chunk_size, params):
+        from wgbs_tools_amd import _lib
+        if self.outgrown:
+            raise _lib.SegmentorError(-7, HALO_OUTGROWN)
+        self.last_stats = {}
+        return self._csr(regions, chunk_size, params)
+
+    def segment_region_slices(self, regions, chunk_size, params, n_slices):
+        from wgbs_tools_amd import _lib
+        cuts = np.unique(np.linspace(0, len(regions), n_slices + 1).astype(int)).tolist()
+        for k, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
+            if self.outgrown and k == min(1, len(cuts) - 2):
+                raise _lib.SegmentorError(-7, HALO_OUTGROWN)
+            yield self._csr(regions[a:b], chunk_size, params)
+        self.last_stats = {'slices': len(cuts) - 1}
+
+    def close(self):
+        self.closed += 1
+
+
+def _case_args(name, driver_golden, synth_world, tmp_path, out_path, **more):
+    g = driver_golden['cases'][name]
+    kw = dict(g['args'], **more)
+    if g['bed_rows'] is not None:
+        kw['bed_file'] = str(tmp_path / 'regions.bed')
+        with open(kw['bed_file'], 'w') as f:
+            f.write('#chr\tstart\tend\tstartCpG\tendCpG\n' + ''.join('chrN\t0\t1\t%d\t%d\n' % (s, e) for s, e in g['bed_rows']))
+    return make_args(synth_world, out_path, **kw)
+
+
+def _drive(args, synth_world, engine):
+    """SegmentByChunks.run with `engine` -> (BED bytes, stderr, --stats report, the driver)"""
+    err = io.StringIO()
+    with contextlib.redirect_stderr(err):
+        sbc = S.SegmentByChunks(args, synth_world['paths'], engine=engine)
+        sbc.run()
+    return open(args.out_path, 'rb').read(), err.getvalue(), json.load(open(args.stats)), sbc
+
+
+@pytest.fixture(scope='module')
+def one_piece(driver_golden, synth_world, tmp_path_factory):
+    """(BED bytes, stderr, report) of a golden case through the `segment_many` engine — the path test_driver_matches_reference_driver compares
+    with the reference driver's goldens — once per case."""
+    seen = {}
+
+    def get(name):
+        if name not in seen:
+            d = tmp_path_factory.mktemp('one_piece')
+            args = _case_args(name, driver_golden, synth_world, d, str(d / 'out.bed'), stats=str(d / 'run.json'))
+            seen[name] = _drive(args, synth_world, OracleEngine(synth_world['betas'], synth_world['loci']))[:3]
+            assert seen[name][0].count(b'\n') == driver_golden['cases'][name]['n_blocks']
+        return seen[name]
+    return get
+
+
+@pytest.mark.parametrize('slices', [1, 2, 3, 8])
+@pytest.mark.parametrize('name', CASES)
+def test_driver_through_csr_and_slices_writes_the_same_file(name, slices, driver_golden, synth_world, one_piece, tmp_path, monkeypatch):
+    """An engine of the driver's own interface, its result as one CSR and in 2, 3 and 8 slices (slice k's rows appended by the writer while
+    slice k + 1 is segmented): the file, the stderr text and the --stats counts of the `segment_many` path."""
+    want_bed, want_err, want_rep = one_piece(name)
+    monkeypatch.setattr(S.SegmentByChunks, 'SLICE_MIN_SITES', 1)
+    if slices > 1:
+        monkeypatch.setenv('WGBSSEG_BED_SLICES', str(slices))
+    args = _case_args(name, driver_golden, synth_world, tmp_path, str(tmp_path / 'out.bed'), stats=str(tmp_path / 'run.json'))
+    bed, err, rep, sbc = _drive(args, synth_world, OracleRegionEngine(synth_world['betas'], synth_world['loci']))
+    assert bed == want_bed and err == want_err
+    assert (rep['blocks_found'], rep['blocks_dropped']) == (want_rep['blocks_found'], want_rep['blocks_dropped'])
+    assert rep['blocks_found'] == driver_golden['cases'][name]['n_blocks'] and rep['engine'] == 'OracleRegionEngine'
+    sliced = slices > 1 and len(sbc.regions()) >= 2
+    if sliced:
+        assert rep['stitching']['slices'] >= 2
+    assert set(rep['phases_s']) == ({'segmentation (device + stitching; BED rows of the earlier slices beside it)', 'blocks to BED (last slice)'} if sliced
+                                    else {'segmentation (device + stitching)', 'blocks to BED'})
+
+
+@pytest.mark.parametrize('make', [OracleEngine, OracleRegionEngine])
+def test_unsorted_bed_file_comes_out_sorted(make, driver_golden, synth_world, one_piece, tmp_path, monkeypatch):
+    """-L rows in descending order (is_block_file_nice only refuses duplicates and overlaps): the engine gets the regions as the file has
+    them, the BED comes out sorted by startCpG (segment.py:169) — the file of the sorted case; slices are not cut over such a list."""
+    monkeypatch.setattr(S.SegmentByChunks, 'SLICE_MIN_SITES', 1)
+    monkeypatch.setenv('WGBSSEG_BED_SLICES', '3')
+    args = _case_args('bed_regions', driver_golden, synth_world, tmp_path, str(tmp_path / 'out.bed'), stats=str(tmp_path / 'run.json'))
+    rows = [l for l in open(args.bed_file)]
+    with open(args.bed_file, 'w') as f:
+        f.write(rows[0] + ''.join(rows[:0:-1]))
+    bed, err, rep, sbc = _drive(args, synth_world, make(synth_world['betas'], synth_world['loci']))
+    assert [a for a, _ in sbc.regions()] == sorted((a for a, _ in sbc.regions()), reverse=True)
+    assert bed == one_piece('bed_regions')[0] and err == one_piece('bed_regions')[1]
+    assert 'blocks to BED' in rep['phases_s']
+
+
+class FixedEngine(S.RegionEngine):
+    """Hands out the CSRs it was given."""
+
+    def __init__(self, csrs):
+        self.csrs = csrs
+
+    def segment_regions_csr(self, regions, chunk_size, params):
+        (csr,) = self.csrs
+        return csr
+
+    def segment_region_slices(self, regions, chunk_size, params, n_slices):
+        assert n_slices == max(1, len(self.csrs))
+        yield from self.csrs
+
+
+@pytest.mark.parametrize('to_file', [True, False])
+def test_failing_row_in_a_later_slice_reports_like_the_one_piece_run(to_file, synth_world, tmp_path, monkeypatch, capfd):
+    """The lists of test_dump_result_csr_reports_before_a_failing_writer, the writer refusing a row of the SECOND slice: the summary carries
+    the counts of the one-piece run — over all lists, the reference says them before it writes (segment.py:180) —, the row number in the
+    error counts the rows of the first slice, and the rows before the failing one are written."""
+    c0 = int(synth_world['sizes'][0])
+    flat = np.array([1, 5, 7, 12, 20, 21, 30, c0 - 2, c0 + 6], dtype=np.int32)
+    off = np.array([0, 4, 4, 9], dtype=np.int64)
+    whole = [(flat, off)]
+    halves = [(flat[:4], off[:2]), (flat[4:], off[1:] - 4)]
+    third = whole[0][0][:0], np.zeros(1, dtype=np.int64)          # (a last slice after the failing one: not written, still counted)
+    monkeypatch.setattr(S.SegmentByChunks, 'SLICE_MIN_SITES', 1)
+    seen = []
+    for csrs in (whole, halves, halves + [third]):
+        monkeypatch.setenv('WGBSSEG_BED_SLICES', str(len(csrs)))
+        out_path = str(tmp_path / ('out%d.bed' % len(csrs)))
+        args = make_args(synth_world, out_path if to_file else None, min_cpg=3, stats=str(tmp_path / 'run.json'))
+        err = io.StringIO()
+        capfd.readouterr()
+        with contextlib.redirect_stderr(err):
+            sbc = S.SegmentByChunks(args, synth_world['paths'], engine=FixedEngine(csrs))
+            with pytest.raises(RuntimeError, match='Cross chromosomes') as ei:
+                sbc.run()
+        rows = open(out_path).read() if to_file else capfd.readouterr().out
+        seen.append((err.getvalue(), str(ei.value), rows, sbc.report['blocks_found'], sbc.report['blocks_dropped']))
+        assert not op.exists(args.stats)
+    assert '[wt segment] found 5 blocks\n             (dropped 2 short blocks)\n' == seen[0][0]
+    assert seen[0][1] == '[wt add_loci] line 4: Cross chromosomes' and seen[0][2].count('\n') == 4 and seen[0][3:] == (5, 2)
+    assert seen[1] == seen[0] and seen[2] == seen[0]
+
+
+@pytest.mark.parametrize('slices', [1, 3])
+def test_halo_outgrown_reruns_once_on_one_gpu(slices, driver_golden, synth_world, one_piece, tmp_path, monkeypatch, capfd):
+    """A share group whose junction patch outgrows the halo (SegmentorError -7, '... not resident on any single share ...'; with slices: after
+    the rows of the first one are in the file): the driver closes it, makes an engine on ONE GPU and writes the complete file once.  Rows that
+    have already gone to stdout cannot be taken back: there the error stands."""
+    from wgbs_tools_amd import _lib
+    want_bed, want_err, want_rep = one_piece('wg_c20000')
+    monkeypatch.setattr(S.SegmentByChunks, 'SLICE_MIN_SITES', 1)
+    monkeypatch.setenv('WGBSSEG_BED_SLICES', str(slices))
+    made = []
+
+    def make_engine(self, starts, ends, gpus=None):
+        made.append((gpus, OracleRegionEngine(synth_world['betas'], synth_world['loci'], outgrown=gpus is None)))
+        return made[-1][1]
+    monkeypatch.setattr(S.SegmentByChunks, 'make_engine', make_engine)
+    args = _case_args('wg_c20000', driver_golden, synth_world, tmp_path, str(tmp_path / 'out.bed'), stats=str(tmp_path / 'run.json'))
+    bed, err, rep, sbc = _drive(args, synth_world, None)
+    assert [g for g, _ in made] == [None, 1] and [e.closed for _, e in made] == [1, 1] and sbc.param_dict['engine'] is None
+    assert bed == want_bed and rep['blocks_found'] == want_rep['blocks_found']
+    assert err == '[wt segment] a junction patch outgrew the share halo; rerunning on one GPU\n' + want_err
+    # the same to stdout
+    del made[:]
+    args.out_path = None
+    capfd.readouterr()
+    with contextlib.redirect_stderr(io.StringIO()):
+        sbc = S.SegmentByChunks(args, synth_world['paths'])
+        if slices == 1:
+            sbc.run()
+            assert capfd.readouterr().out.encode() == want_bed and [g for g, _ in made] == [None, 1]
+        else:
+            with pytest.raises(_lib.SegmentorError, match='not resident on any single share'):
+                sbc.run()
+            assert want_bed.startswith(capfd.readouterr().out.encode()) and [g for g, _ in made] == [None] and made[0][1].closed == 1

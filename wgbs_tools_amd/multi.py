@@ -10,10 +10,12 @@ the borders do not depend on the number of shares.
 import numpy as np
 
 from . import _lib
+from .segment import RegionEngine
 
 
-class GroupEngine:
-    """Chunk engine of SegmentByChunks over a group of shares; same `segment_regions` interface as HipEngine."""
+class GroupEngine(RegionEngine):
+    """SegmentByChunks' engine over a group of shares.  regions: [(startCpG, endCpG)] 1-based half-open, ascending and disjoint (whole
+    chromosomes, a -s/-r range or the rows of a sorted -L file)."""
 
     def __init__(self, betas, genome, devices):
         self.betas = list(betas)
@@ -22,40 +24,30 @@ class GroupEngine:
         self.group = _lib.SegmenterGroup(self.devices)
         self._maps = None
         self.base = 0
-        self.last_stats = None
         self.windows = None
 
-    def _run(self, regions, chunk_size, params, copy):
-        loci = self.genome.loci()
-        self.windows = self.group.plan(loci, regions, chunk_size, params['pcount'], params['max_cpg'], params['max_bp'])
+    def _plan_and_load(self, regions, chunk_size, params):
+        self.windows = self.group.plan(self.genome.loci(), regions, chunk_size, params['pcount'], params['max_cpg'], params['max_bp'])
         if self._maps is None:
             self._maps = [np.memmap(b, dtype=np.uint8, mode='r') for b in self.betas]
         self.group.load_host(self._maps, wait=False)        # the shares segment what has arrived while the rest is uploading
-        res, self.last_stats = self.group.segment_regions(copy=copy)
-        return res
-
-    def segment_regions(self, regions, chunk_size, params):
-        """regions: [(startCpG, endCpG)] 1-based half-open, ascending and disjoint (whole chromosomes, a -s/-r range or the
-        rows of a sorted -L file).  -> merged absolute border list of each region."""
-        return self._run(regions, chunk_size, params, True)
 
     def segment_regions_csr(self, regions, chunk_size, params):
-        """The same call, the result left as ONE CSR: (flat int32 absolute 1-based borders, off int64 [regions + 1]) — views into the
-        group's result buffer, valid until its next call; what wgbsseg_add_loci_borders prints the BED from without any (start, end)
-        arrays in between."""
-        self._run(regions, chunk_size, params, False)
+        """The result left as ONE CSR: (flat int32 absolute 1-based borders, off int64 [regions + 1]) — views into the group's result
+        buffer, valid until its next call; what wgbsseg_add_loci_borders prints the BED from without any (start, end) arrays in between."""
+        self._plan_and_load(regions, chunk_size, params)
+        _, self.last_stats = self.group.segment_regions(copy=False)
         return self.group.last_csr
 
-    def segment_region_slices(self, regions, chunk_size, params, n_slices=4):
-        """Generator over slices of the regions, cut where the cumulative sites pass k / n_slices of the total: yields (first, end, flat, off)
-        — regions [first, end) as one CSR of absolute borders in a buffer of its own — as soon as the slice is segmented, while the beta bytes
-        of the later slices are still uploading (the upload streams site-major) and before the next slice is computed: the caller's BED
-        writer works on slice k during slice k + 1 (round 6; regions never interact: segment.py:84-86,129-134)."""
-        loci = self.genome.loci()
-        self.windows = self.group.plan(loci, regions, chunk_size, params['pcount'], params['max_cpg'], params['max_bp'])
-        if self._maps is None:
-            self._maps = [np.memmap(b, dtype=np.uint8, mode='r') for b in self.betas]
-        self.group.load_host(self._maps, wait=False)
+    def segment_region_slices(self, regions, chunk_size, params, n_slices):
+        """Generator over n_slices > 1 slices of the regions, cut where the cumulative sites pass k / n_slices of the total: yields each slice as one
+        CSR of absolute borders in a buffer of its own as soon as it is segmented, while the beta bytes of the later slices are still uploading
+        (the upload streams site-major) and before the next slice is computed: the caller's BED writer works on slice k during slice k + 1
+        (round 6; regions never interact: segment.py:84-86,129-134)."""
+        if n_slices < 2:
+            yield self.segment_regions_csr(regions, chunk_size, params)
+            return
+        self._plan_and_load(regions, chunk_size, params)
         sizes = np.array([b - a for a, b in regions], dtype=np.int64)
         cum = np.cumsum(sizes)
         cuts = sorted(set([0, len(regions)] + [int(np.searchsorted(cum, cum[-1] * k / n_slices, side='left')) + 1 for k in range(1, n_slices)]))
@@ -64,7 +56,7 @@ class GroupEngine:
         for first, end in zip(cuts[:-1], cuts[1:]):
             flat, off, st = self.group.segment_region_range(first, end, int(sizes[first:end].sum()) + (end - first))
             stats.append(st)
-            yield first, end, flat, off
+            yield flat, off
         self.last_stats = {k: (sum(s[k] for s in stats)) for k in stats[0]} if stats else None
         if self.last_stats:
             self.last_stats['slices'] = len(stats)

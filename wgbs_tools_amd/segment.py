@@ -12,6 +12,7 @@ There is no CPU fallback: without the HIP library and a gfx950 device `segment` 
 """
 import argparse
 import os
+import re
 import sys
 import threading
 import time
@@ -26,9 +27,78 @@ MAX_BLOCK_SITES = 65535       # WGBSSEG_MAX_CPG (include/wgbsseg.h): longest blo
 
 
 # ------------------------------------------------------------------------------------------------------------
-# chunk engine: (start, end) 1-based half-open CpG ranges -> absolute border arrays
+# engines: what SegmentByChunks calls, and the chunk engines under it
 # ------------------------------------------------------------------------------------------------------------
-class HipEngine:
+def _csr_of(lists):
+    """Border lists -> one CSR (flat int32, off int64 [len(lists) + 1]): list r is flat[off[r]:off[r + 1]]."""
+    off = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in lists], out=off[1:])
+    return (np.concatenate(lists).astype(np.int32, copy=False) if lists else np.zeros(0, dtype=np.int32)), off
+
+
+def _ascending_csr(regs, lists):
+    """_csr_of(lists), lists[r] being the borders of regs[r], in ascending order of the regions: the BED rows come out sorted by startCpG
+    (segment.py:169; is_block_file_nice has refused overlaps)."""
+    return _csr_of([lists[i] for i in sorted(range(len(regs)), key=regs.__getitem__)])
+
+
+class RegionEngine:
+    """What SegmentByChunks calls on an engine.  HipEngine and multi.GroupEngine are such engines; a chunk engine that only has
+    `segment_many` becomes one through ChunkEngineAdapter."""
+
+    last_stats = None            # the stitcher's counters of the last call (_lib._stats_dict), for --stats
+
+    def segment_regions_csr(self, regions, chunk_size, params):
+        """The chunk fan-out + merge_df_list of SegmentByChunks.run (segment.py:137-165) over regions = [(startCpG, endCpG), ...] 1-based
+        half-open -> the merged border list of every region, in the order given, as one CSR (flat, off) of absolute 1-based borders."""
+        raise NotImplementedError
+
+    def segment_region_slices(self, regions, chunk_size, params, n_slices):
+        """Generator of such CSRs over consecutive runs of the (ascending) regions; here the whole result as one slice."""
+        yield self.segment_regions_csr(regions, chunk_size, params)
+
+    def timings(self):
+        """Device timings (_lib.Timings.as_dict) of every GPU that took part."""
+        return []
+
+    def close(self):
+        pass
+
+
+class ChunkEngineAdapter(RegionEngine):
+    """A chunk engine without the library's driver loop — anything with `segment_many(sites_list, params)`: the CPU engines of the
+    test-suite, GatherEngine — as a RegionEngine: the library's chunk grid and stitching tree (wgbsseg_stitch_regions, csrc/stitch.h)
+    around its segment_many, asking for exactly the patches the reference would (no speculation)."""
+
+    def __init__(self, chunk_engine):
+        self.chunk_engine = chunk_engine
+
+    def segment_regions_csr(self, regions, chunk_size, params):
+        from . import _lib
+        res, self.last_stats = _lib.stitch_regions(regions, chunk_size, lambda sites: self.chunk_engine.segment_many(sites, params),
+                                                   speculate=False)
+        return _csr_of(res)
+
+
+def _segment_many(sites_list, chunks):
+    """segment_process (segment.py:41-59) over a batch of 1-based half-open ranges: a range of one site is its own two borders
+    (segment.py:45-46); `chunks(sites)` gets the others in one call and returns their border lists relative to each start.
+    -> [np.int64 array of absolute borders, ...]"""
+    out = [None] * len(sites_list)
+    idx = []
+    for i, (start, end) in enumerate(sites_list):
+        assert end - start > 0, f'trying to segment an empty interval {(start, end)}'
+        if end - start == 1:
+            out[i] = np.array([start, end])
+        else:
+            idx.append(i)
+    if idx:
+        for i, r in zip(idx, chunks([sites_list[i] for i in idx])):
+            out[i] = r.astype(np.int64) + sites_list[i][0]
+    return out
+
+
+class HipEngine(RegionEngine):
     """Resident betas + loci on one GPU; `segment_many` is the batched form of segment_process (segment.py:41-59)."""
 
     def __init__(self, betas, genome, device=0, site_range=None):
@@ -44,25 +114,14 @@ class HipEngine:
 
     def segment_many(self, sites_list, params):
         """sites_list: [(start, end), ...] 1-based half-open; returns [np.int64 array of absolute borders, ...]."""
-        out = [None] * len(sites_list)
-        idx, st0, ln = [], [], []
-        for i, (start, end) in enumerate(sites_list):
-            assert end - start > 0, f'trying to segment an empty interval {(start, end)}'
-            if end - start == 1:                                 # segment.py:45-46
-                out[i] = np.array([start, end])
-            else:
-                idx.append(i)
-                st0.append(start - 1 - self.base)
-                ln.append(end - start)
-        if idx:
+        def chunks(sites):
             try:
-                res = self._seg.segment_chunks(st0, ln, params['pcount'], params['max_cpg'], params['max_bp'])
+                return self._seg.segment_chunks([a - 1 - self.base for a, _ in sites], [b - a for a, b in sites],
+                                                params['pcount'], params['max_cpg'], params['max_bp'])
             except Exception as e:
-                eprint(f'Failed in sites {sites_list[idx[0]]} .. {sites_list[idx[-1]]}')   # segment.py:57-59
+                eprint(f'Failed in sites {sites[0]} .. {sites[-1]}')   # segment.py:57-59
                 raise e
-            for i, r in zip(idx, res):
-                out[i] = r.astype(np.int64) + sites_list[i][0]
-        return out
+        return _segment_many(sites_list, chunks)
 
     def segment_csr(self, starts, ends, params, off=None, out=None):
         """Array form of segment_many: 1-based half-open ranges -> (offsets int64 [n + 1], int32 borders RELATIVE to each start),
@@ -72,21 +131,21 @@ class HipEngine:
         flat, off = self._seg.segment_chunks_csr(st0, ln, params['pcount'], params['max_cpg'], params['max_bp'], out=out, off=off)
         return off, flat
 
-    def segment_regions(self, regions, chunk_size, params):
-        """The whole of SegmentByChunks.run's chunk fan-out + merge_df_list, native (wgbsseg_segment_regions):
-        regions = [(startCpG, endCpG), ...] 1-based half-open; returns the merged absolute border list of each."""
+    def segment_regions_csr(self, regions, chunk_size, params):
+        """Native chunk grid + batched patches + stitching around the GPU batches (wgbsseg_segment_regions, csrc/stitch.h)."""
         st = np.array([r[0] for r in regions], dtype=np.int64) - self.base
         en = np.array([r[1] for r in regions], dtype=np.int64) - self.base
         try:
             res, self.last_stats = self._seg.segment_regions(st, en, chunk_size, params['pcount'], params['max_cpg'],
-                                                             params['max_bp'])
+                                                             params['max_bp'], copy=False)
         except Exception as e:
             eprint(f'Failed in sites {regions[0]} .. {regions[-1]}')
             raise e
-        return [r + self.base for r in res]
+        flat, off = _csr_of(res)
+        return flat + np.int32(self.base), off
 
     def timings(self):
-        return self._seg.timings()
+        return [self._seg.timings()]
 
     def close(self):
         self._seg.close()
@@ -105,44 +164,33 @@ class GatherEngine:
         self._loci = genome.loci()
 
     def segment_many(self, sites_list, params):
-        out = [None] * len(sites_list)
-        idx = [i for i, (a, b) in enumerate(sites_list) if b - a > 1]
-        for i, (a, b) in enumerate(sites_list):
-            assert b - a > 0, f'trying to segment an empty interval {(a, b)}'
-            if b - a == 1:                                       # segment.py:45-46
-                out[i] = np.array([a, b])
-        if idx:
-            lens = np.array([sites_list[i][1] - sites_list[i][0] for i in idx], dtype=np.int64)
+        def chunks(sites):
+            lens = np.array([b - a for a, b in sites], dtype=np.int64)
             offs = np.concatenate([[0], np.cumsum((lens + 7) // 8 * 8)])      # ranges start on 16-byte boundaries
             total = int(offs[-1])
             buf = np.zeros((len(self._maps), 2 * total), dtype=np.uint8)
             loci = np.zeros(total, dtype=np.uint32)
-            for k, i in enumerate(idx):
-                a, b = sites_list[i]
-                o = int(offs[k])
+            for o, (a, b) in zip(offs.tolist(), sites):
                 for s, m in enumerate(self._maps):
                     buf[s, 2 * o:2 * (o + b - a)] = m[2 * (a - 1):2 * (b - 1)]
                 loci[o:o + b - a] = self._loci[a - 1:b - 1]
             self._seg.set_betas(list(buf))
             self._seg.set_loci(loci)
-            res = self._seg.segment_chunks(offs[:-1], lens, params['pcount'], params['max_cpg'], params['max_bp'])
-            for i, r in zip(idx, res):
-                out[i] = r.astype(np.int64) + sites_list[i][0]
-        return out
+            return self._seg.segment_chunks(offs[:-1], lens, params['pcount'], params['max_cpg'], params['max_bp'])
+        return _segment_many(sites_list, chunks)
 
     def segment_csr(self, starts, ends, params, off=None, out=None):
-        res = self.segment_many(list(zip(np.asarray(starts).tolist(), np.asarray(ends).tolist())), params)
-        n = len(res)
-        off = np.empty(n + 1, dtype=np.int64) if off is None else off
-        off[0] = 0
-        np.cumsum([len(r) for r in res], out=off[1:n + 1])
-        out = np.empty(max(1, int(off[n])), dtype=np.int32) if out is None else out
-        for i, r in enumerate(res):
-            out[off[i]:off[i + 1]] = r - int(starts[i])
+        starts = np.asarray(starts).tolist()
+        res = self.segment_many(list(zip(starts, np.asarray(ends).tolist())), params)
+        flat, o = _csr_of([r - a for r, a in zip(res, starts)])
+        if off is None:
+            return o, flat
+        off[:o.size], out[:flat.size] = o, flat
         return off, out
 
     def close(self):
         self._seg.close()
+
 
 
 SMALL_CHUNK_WARNING = ('[wt segment] WARNING: chunk_size is small compared to max_cpg and/or max_bp.\n'
@@ -168,13 +216,14 @@ class SegmentByChunks:
             raise IllegalArgumentError(f'[wt segment] ERROR: blocks of up to min(max_cpg, max_bp/2, chunk_size) = {min(max_cpg, args.chunk_size)} sites '
                                        f'requested; at most {MAX_BLOCK_SITES} are supported (default max_cpg 1000).')
         self._regions = None
+        self.report = {}                                         # what --stats writes (write_stats)
         self.genome = GenomeRefPaths(args.genome)
         self.param_dict = {'betas': betas,
                            'pcount': args.pcount,
                            'max_cpg': max_cpg,
                            'max_bp': args.max_bp,
                            'genome': self.genome,
-                           'engine': engine}
+                           'engine': engine if engine is None or isinstance(engine, RegionEngine) else ChunkEngineAdapter(engine)}
         self.args = args
         self.validate_genome()
 
@@ -233,88 +282,64 @@ class SegmentByChunks:
         tags, starts, ends = self.break_to_chunks()
         from . import parallel
         rank, world, local = parallel.env_rank_world()
-        own_engine = self.param_dict['engine'] is None
-        csr = None
         if world > 1:
             return self.run_sharded(rank, world, local)
         want_stats = bool(getattr(self.args, 'stats', None))
         prof = [('start', time.perf_counter())] if (os.environ.get('WGBSSEG_PROFILE') or want_stats) else None
         self.report = {'regions': len(self.regions()), 'chunks': len(starts), 'sites': int(sum(e - s for s, e in zip(starts, ends)))}
         if not starts:                                           # nothing to segment (e.g. an -L file of empty rows)
-            self.dump_result(np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
+            self.dump_result_csr(*_csr_of([]))
             self.write_stats(prof)
             return
+        own_engine = self.param_dict['engine'] is None
         if own_engine:
             self.param_dict['engine'] = self.make_engine(starts, ends)
             if prof: prof.append(('engine (one GPU: loci + betas to the device)', time.perf_counter()))
+        bed = _BedWriter(self.genome, self.args.out_path, self.args.min_cpg)
+        n_slices, closer = self._n_slices(self.regions()), None
         try:
-            eng = self.param_dict['engine']
-            if hasattr(eng, 'segment_regions'):
-                # native chunk grid + batched patches + stitching around the GPU batches (csrc/stitch.h)
-                regs = self.regions()
-                # an engine that can leave its result as one CSR of absolute borders (the share groups: every whole-genome / -r / -s run and
-                # sorted -L files) hands it to the BED writer as it is (wgbsseg_add_loci_borders): no per-region copies, no (start, end) arrays
-                as_csr = lambda e: getattr(e, 'segment_regions_csr', None) if all(regs[i][0] >= regs[i - 1][1] for i in range(1, len(regs))) else None
-                try:
-                    if own_engine and as_csr(eng) and self._slices_pay(eng, regs):
-                        # round 6: the regions in slices, the BED rows of one slice written while the next is segmented (and while the beta
-                        # bytes of the later ones are still uploading): the 20 ms of BED text leave the run's critical path
-                        sliced = self._run_sliced(eng, regs, prof, want_stats)
-                        if sliced:
-                            return
-                    res = (as_csr(eng) or eng.segment_regions)(regs, self.args.chunk_size, self.param_dict)
-                except Exception as e:
-                    if not (own_engine and getattr(e, 'code', 0) == -7 and 'not resident on any single share' in str(e)):
-                        raise _as_reference_error(e)
-                    # a junction patch outgrew the halo between two shares (patch doubling past a chunk): one GPU, whole range
-                    eprint('[wt segment] a junction patch outgrew the share halo; rerunning on one GPU')
-                    eng.close()
-                    eng = self.param_dict['engine'] = self.make_engine(starts, ends, gpus=1)
-                    res = (as_csr(eng) or eng.segment_regions)(regs, self.args.chunk_size, self.param_dict)
-                if as_csr(eng):
-                    csr, merged = res, None
-                else:
-                    merged = dict(zip([f'{a}-{b}' for a, b in regs], res))
-                if want_stats:                                   # (before the engine goes away)
-                    self.report['engine'] = type(eng).__name__
-                    self.report['stitching'] = getattr(eng, 'last_stats', None)
-                    tm = eng.timings() if hasattr(eng, 'timings') else None
-                    self.report['device'] = tm if isinstance(tm, list) else ([tm] if tm else None)
-            else:
-                # a chunk engine without the library's driver loop (the CPU engines of the test-suite): the library's chunk grid and
-                # stitching tree (wgbsseg_stitch_regions, csrc/stitch.h) around its segment_many, asking for exactly the patches the
-                # reference would (no speculation)
-                from . import _lib
-                regs = self.regions()
-                try:
-                    res, self.last_stats = _lib.stitch_regions(regs, self.args.chunk_size, lambda sites: eng.segment_many(sites, self.param_dict),
-                                                               speculate=False)
-                except _lib.SegmentorError as e:
-                    raise _as_reference_error(e)
-                merged = dict(zip([f'{a}-{b}' for a, b in regs], res))
+            eng = self._segment(bed, n_slices, starts, ends, own_engine)
+            self.last_stats = eng.last_stats
+            if want_stats:                                       # (before the engine goes away)
+                self.report['engine'] = type(eng).__name__
+                self.report['stitching'] = eng.last_stats
+                self.report['device'] = eng.timings() or None
         finally:
-            closer = None
-            if own_engine and self.param_dict['engine'] is not None:      # (None: the sliced form has closed it already)
-                # releasing ~10 GB of device buffers takes as long as writing the BED: do both at once
+            if own_engine:
+                # releasing ~10 GB of device buffers takes as long as writing the BED (of the last slice): do both at once
                 closer = threading.Thread(target=self.param_dict['engine'].close)
                 closer.start()
                 self.param_dict['engine'] = None
         try:
-            if prof: prof.append(('segmentation (device + stitching)', time.perf_counter()))
-            if csr is not None:
-                self.dump_result_csr(*csr)
-            else:
-                s = np.concatenate([m[:-1] for m in merged.values()]) if merged else np.zeros(0, dtype=np.int64)
-                e = np.concatenate([m[1:] for m in merged.values()]) if merged else np.zeros(0, dtype=np.int64)
-                self.dump_result(s, e)
+            if prof: prof.append(('segmentation (device + stitching; BED rows of the earlier slices beside it)' if n_slices > 1 else
+                                  'segmentation (device + stitching)', time.perf_counter()))
+            bed.finish(self.report)
         finally:
             if closer is not None:
                 closer.join()
         if prof:
-            prof.append(('blocks to BED', time.perf_counter()))
+            prof.append(('blocks to BED (last slice)' if n_slices > 1 else 'blocks to BED', time.perf_counter()))
             if os.environ.get('WGBSSEG_PROFILE'):
                 eprint('[wt segment] phases: ' + ', '.join('%s %.3f s' % (n, t - prof[i][1]) for i, (n, t) in enumerate(prof[1:])))
         self.write_stats(prof)
+
+    def _segment(self, bed, n_slices, starts, ends, may_retry):
+        """The borders of every region from the engine into `bed`, slice by slice; -> the engine that gave them."""
+        eng = self.param_dict['engine']
+        try:
+            for flat, off in self._border_slices(eng, self.regions(), n_slices):
+                bed.put(flat, off)
+        except Exception as err:
+            bed.wait()
+            halo_outgrown = getattr(err, 'code', 0) == -7 and 'not resident on any single share' in str(err)
+            if not (may_retry and halo_outgrown and bed.take_back()):      # (rows already on stdout cannot be taken back)
+                raise _as_reference_error(err)
+            # a junction patch outgrew the halo between two shares (patch doubling past a chunk): one GPU, whole range
+            eprint('[wt segment] a junction patch outgrew the share halo; rerunning on one GPU')
+            eng.close()
+            self.param_dict['engine'] = self.make_engine(starts, ends, gpus=1)
+            return self._segment(bed, n_slices, starts, ends, False)
+        return eng
 
     def write_stats(self, prof):
         """--stats PATH: one JSON object about the run (the reference only has its stderr lines)."""
@@ -329,7 +354,7 @@ class SegmentByChunks:
                               'min_cpg': a.min_cpg, 'max_cpg': self.param_dict['max_cpg'], 'max_bp': a.max_bp,
                               'region': a.region, 'sites': a.sites, 'bed_file': a.bed_file},
                'out_path': None if a.out_path is sys.stdout else str(a.out_path)}
-        rep.update(getattr(self, 'report', {}))
+        rep.update(self.report)
         if prof and len(prof) > 1:
             rep['phases_s'] = {n: round(t - prof[i][1], 6) for i, (n, t) in enumerate(prof[1:])}
             rep['wall_s'] = round(prof[-1][1] - prof[0][1], 6)
@@ -354,6 +379,7 @@ class SegmentByChunks:
             return multi.GroupEngine(self.betas, self.genome, [(first + d) % have for d in range(n)])
         return HipEngine(self.betas, self.genome, device=first, site_range=(min(starts) - 1, max(ends) - 1))
 
+
     def run_sharded(self, rank, world, local, engine_factory=None, patch_engine_factory=None):
         """One process per GPU (python -m torch.distributed.run ... wgbstools segment ...): the chunk grid is cut into
         `world` contiguous, work-balanced runs of chunks (the planner of the share groups, include/wgbsseg.h); every rank
@@ -375,7 +401,7 @@ class SegmentByChunks:
                 return GatherEngine(self.betas, self.genome, device=local % max(1, _lib.device_count()))
         if not regs:
             if rank == 0:
-                self.dump_result(np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64))
+                self.dump_result_csr(*_csr_of([]))
             dist.barrier()
             return
         run = parallel.ShardedRun(dist, regs, self.args.chunk_size, self.genome.loci(), pd, rank, world)
@@ -391,9 +417,7 @@ class SegmentByChunks:
             merged = run.step(parallel.csr_engine(eng, pd), patches)
             self.last_stats = run.last_stats
             if rank == 0:
-                s_ = np.concatenate([m[:-1] for m in merged])
-                e_ = np.concatenate([m[1:] for m in merged])
-                self.dump_result(s_, e_)
+                self.dump_result_csr(*_ascending_csr(regs, merged))
         finally:
             for e in [eng] + peng:
                 if e is not None and hasattr(e, 'close'):
@@ -409,155 +433,126 @@ class SegmentByChunks:
     SLICES = 1
     SLICE_MIN_SITES = 4000000   # below that a run is over before a second slice could help
 
-    def _slices_pay(self, eng, regs):
+    def _n_slices(self, regs):
+        from . import multi
         n = int(os.environ.get('WGBSSEG_BED_SLICES', self.SLICES))
-        return (n > 1 and hasattr(eng, 'segment_region_slices') and len(regs) >= 2 and sum(b - a for a, b in regs) >= self.SLICE_MIN_SITES)
+        pays = len(regs) >= 2 and sum(b - a for a, b in regs) >= self.SLICE_MIN_SITES
+        return n if n > 1 and pays and multi.regions_fit_a_group(regs) else 1
 
-    def _run_sliced(self, eng, regs, prof, want_stats):
-        """run()'s segmentation + dump_result for an engine that can take the regions in slices (multi.GroupEngine): slice k's BED rows
-        (wgbsseg_add_loci_borders, append mode) are written by a second thread while slice k + 1 is segmented.  Same rows, same summary line,
-        same errors as the one-piece form; False (nothing written) when a junction patch outgrew a share's halo — the caller then reruns on
-        one GPU as before."""
-        import queue
-        import re
-        from . import _lib
-        names, sizes = self.genome.get_chrom_cpg_sizes()
-        cum = np.cumsum(sizes)
-        loci = self.genome.loci()
-        out_path = self.args.out_path
-        to_stdout = out_path is None or out_path is sys.stdout
-        if to_stdout:
-            sys.stdout.flush()
-        todo = queue.Queue()
-        state = dict(written=0, dropped=0, error=None, slices=0)
-
-        def writer():
-            while True:
-                item = todo.get()
-                if item is None:
-                    return
-                if state['error'] is not None:
-                    continue                                     # (drain: nothing is written behind a failed slice)
-                flat, off = item
-                try:
-                    w, d = _lib.add_loci_borders(loci, names, cum, flat, off, self.args.min_cpg, None if to_stdout else out_path, append=state['slices'] > 0)
-                    state['written'] += w; state['dropped'] += d; state['slices'] += 1
-                except _lib.SegmentorError as e:
-                    msg = e.msg or ''
-                    m = re.match(r'(\[wt add_loci\] line )(\d+)(: .*)', msg, re.S)
-                    if m:                                        # the row's number counts the rows of the earlier slices too
-                        msg = m.group(1) + str(int(m.group(2)) + state['written']) + m.group(3)
-                    state['error'] = msg
-        th = threading.Thread(target=writer)
-        th.start()
-        n_blocks = 0
-        try:
-            n = int(os.environ.get('WGBSSEG_BED_SLICES', self.SLICES))
-            for first, end, flat, off in eng.segment_region_slices(regs, self.args.chunk_size, self.param_dict, n):
-                n_blocks += int(np.maximum(np.diff(off) - 1, 0).sum())
-                todo.put((flat, off))
-                if state['error'] is not None:
-                    break
-        except Exception as e:
-            todo.put(None); th.join()
-            if getattr(e, 'code', 0) == -7 and 'not resident on any single share' in str(e):
-                if not to_stdout and state['slices'] > 0:
-                    os.remove(out_path)                          # (rows of the earlier slices: the rerun writes the file afresh)
-                if to_stdout and state['slices'] > 0:
-                    raise _as_reference_error(e)                 # (rows already on stdout cannot be taken back)
-                return False
-            raise _as_reference_error(e)
-        if want_stats:                                           # (before the engine goes away)
-            self.report['engine'] = type(eng).__name__
-            self.report['stitching'] = getattr(eng, 'last_stats', None)
-            tm = eng.timings() if hasattr(eng, 'timings') else None
-            self.report['device'] = tm if isinstance(tm, list) else ([tm] if tm else None)
-        # releasing ~10 GB of device buffers takes as long as writing the last slice: do both at once
-        closer = threading.Thread(target=eng.close)
-        closer.start()
-        self.param_dict['engine'] = None
-        if prof: prof.append(('segmentation (device + stitching; BED rows of the earlier slices beside it)', time.perf_counter()))
-        todo.put(None)
-        th.join()
-        closer.join()
-        if n_blocks == 0:
-            eprint('Empty blocks array')
-        elif state['error'] is not None:
-            if '[wt add_loci] line' in state['error']:
-                # the reference says the counts BEFORE it writes (segment.py:180): a run whose writer fails on a row has still said them
-                eprint(f"[wt segment] found {n_blocks - state['dropped']:,} blocks\n             (dropped {state['dropped']:,} short blocks)")
-            raise RuntimeError(state['error'])
-        else:
-            eprint(f"[wt segment] found {state['written']:,} blocks\n             (dropped {state['dropped']:,} short blocks)")
-            self.report.update(blocks_found=int(state['written']), blocks_dropped=int(state['dropped']))
-        if prof:
-            prof.append(('blocks to BED (last slice)', time.perf_counter()))
-            if os.environ.get('WGBSSEG_PROFILE'):
-                eprint('[wt segment] phases: ' + ', '.join('%s %.3f s' % (n, t - prof[i][1]) for i, (n, t) in enumerate(prof[1:])))
-        self.write_stats(prof)
-        return True
+    def _border_slices(self, eng, regs, n_slices):
+        """The merged border lists of all regions as CSRs, the regions ascending across them: the engine's slices — one, or WGBSSEG_BED_SLICES of them, slice k's
+        BED rows then being written while slice k + 1 is segmented (and while the beta bytes of the later ones are still uploading)."""
+        from . import multi
+        if multi.regions_fit_a_group(regs):                      # every whole-genome / -r / -s run and sorted -L files
+            return eng.segment_region_slices(regs, self.args.chunk_size, self.param_dict, n_slices)
+        # an unsorted -L file (is_block_file_nice has refused overlaps): the rows come out sorted by startCpG (segment.py:169)
+        flat, off = eng.segment_regions_csr(regs, self.args.chunk_size, self.param_dict)
+        return [_ascending_csr(regs, [flat[off[i]:off[i + 1]] for i in range(len(regs))])]
 
     def dump_result_csr(self, flat, off):
-        """dump_result (segment.py:167-190) straight from the merged border lists (CSR of absolute 1-based borders, regions ascending): the
-        blocks are the pairs of consecutive borders (segment.py:154), the `min_cpg` filter and the BED rows happen in the library
-        (wgbsseg_add_loci_borders) — same rows, same stderr summary (also when the writer fails on a row).  `flat` / `off` may be the engine's
-        `last_csr` views: they are numpy-owned buffers of the binding (not device or library memory) and stay valid after the engine is closed,
-        until its next segment_regions_csr call."""
+        """dump_result (segment.py:167-190) straight from the merged border lists (CSR of absolute 1-based borders, regions ascending): see _BedWriter."""
+        bed = _BedWriter(self.genome, self.args.out_path, self.args.min_cpg)
+        bed.put(flat, off)
+        bed.finish(self.report)
+
+    def dump_result(self, start_cpg, end_cpg):
+        """segment.py:167-190 for blocks given as (start, end) arrays (disjoint, as a segmentation's are): every block a region of two borders."""
+        order = np.argsort(start_cpg, kind='stable')
+        self.dump_result_csr(np.stack([start_cpg[order], end_cpg[order]], axis=1).ravel(), 2 * np.arange(start_cpg.size + 1))
+
+
+class _BedWriter:
+    """The one way borders reach the BED (dump_result, segment.py:167-190): `put` takes CSRs (flat, off) of absolute 1-based borders, region r's being
+    flat[off[r]:off[r + 1]], regions ascending across all of them; the blocks are the pairs of consecutive borders (segment.py:154), the `min_cpg`
+    filter and the BED rows happen in the library (wgbsseg_add_loci_borders), on a thread of their own, each CSR appended behind the one before;
+    `finish` waits for the rows and says the reference's summary.  `flat` / `off` may be views of an engine's result buffer: those are numpy-owned
+    buffers of the binding (not device or library memory) and stay valid after the engine is closed."""
+
+    def __init__(self, genome, out_path, min_cpg):
+        self.names, sizes = genome.get_chrom_cpg_sizes()
+        self.cum, self.loci, self.min_cpg = np.cumsum(sizes), genome.loci(), min_cpg
+        self.path = None if out_path is None or out_path is sys.stdout else out_path
+        if self.path is None:
+            sys.stdout.flush()
+        self.thread = None
+        self._reset()
+
+    def _reset(self):
+        self.csrs, self.written, self.dropped, self.begun, self.error = [], 0, 0, False, None
+
+    def take_back(self):
+        """Forget everything put so far, for a second attempt; a file begun is removed.  False when rows have already gone to stdout."""
+        self.wait()
+        if self.begun and self.path is None:
+            return False
+        if self.begun:
+            os.remove(self.path)
+        self._reset()
+        return True
+
+    def put(self, flat, off):
+        self.csrs.append((flat, off))
+        before = self.thread
+
+        def work():
+            if before is not None:
+                before.join()
+            self._write(flat, off)
+        self.thread = threading.Thread(target=work)
+        self.thread.start()
+
+    def wait(self):
+        if self.thread is not None:
+            self.thread.join()
+
+    def _write(self, flat, off):
         from . import _lib
-        nr_blocks = int(np.maximum(np.diff(off) - 1, 0).sum())
+        if self.error is not None or not _n_blocks(off):         # nothing is written behind a failed slice; nothing at all for no blocks (segment.py:168-170)
+            return
+        try:
+            w, d = _lib.add_loci_borders(self.loci, self.names, self.cum, flat, off, self.min_cpg, self.path, append=self.begun)
+            self.written += w; self.dropped += d; self.begun = True
+        except _lib.SegmentorError as e:
+            m = re.match(r'(\[wt add_loci\] line )(\d+)(: .*)', e.msg or '', re.S)
+            # the row's number counts the rows of the earlier slices too
+            self.error = m.group(1) + str(int(m.group(2)) + self.written) + m.group(3) if m else e.msg
+
+    def finish(self, report):
+        self.wait()
+        nr_blocks = sum(_n_blocks(off) for _, off in self.csrs)
         if nr_blocks == 0:
             eprint('Empty blocks array')
             return
-        names, sizes = self.genome.get_chrom_cpg_sizes()
-        out_path = self.args.out_path
-        to_stdout = out_path is None or out_path is sys.stdout
-        if to_stdout:
-            sys.stdout.flush()
-        def summary(found, short):
-            eprint(f'[wt segment] found {found:,} blocks\n'
-                   f'             (dropped {short:,} short blocks)')
-            if hasattr(self, 'report'):
-                self.report.update(blocks_found=int(found), blocks_dropped=int(short))
-        try:
-            written, dropped = _lib.add_loci_borders(self.genome.loci(), names, np.cumsum(sizes), flat, off, self.args.min_cpg,
-                                                     None if to_stdout else out_path)
-        except _lib.SegmentorError as e:
+        found, short = self.written, self.dropped
+        if self.error is not None:
             # the reference reports the counts BEFORE it writes (segment.py:180), so a run whose writer fails has still said them: on this
-            # path the counts come from one numpy pass over the lists (the library's counts exist only for a completed file)
+            # path the counts come from one numpy pass over ALL the lists (the library's counts exist only for a completed file)
             # — for a failing ROW only ('[wt add_loci] line N: ...', add_loci.cpp:42-49): an argument the library refused (descending borders, regions
             # out of order, a NULL path) is no list of blocks at all, and counts made of it would mean nothing (ADVICE r05)
-            if '[wt add_loci] line' not in (e.msg or ''):
-                raise RuntimeError(e.msg)
-            flat_, off_ = np.asarray(flat, dtype=np.int64), np.asarray(off, dtype=np.int64)
-            d = np.diff(flat_)
-            inner = np.ones(d.size, dtype=bool)
-            cut = off_[1:-1] - 1                                  # the pair that straddles two regions is not a block
-            inner[cut[(cut >= 0) & (cut < d.size)]] = False
-            short = int((d[inner] < self.args.min_cpg).sum())
-            summary(nr_blocks - short, short)
-            raise RuntimeError(e.msg)
-        summary(written, dropped)
+            if '[wt add_loci] line' not in self.error:
+                raise RuntimeError(self.error)
+            short = sum(_n_short(flat, off, self.min_cpg) for flat, off in self.csrs)
+            found = nr_blocks - short
+        eprint(f'[wt segment] found {found:,} blocks\n'
+               f'             (dropped {short:,} short blocks)')
+        report.update(blocks_found=int(found), blocks_dropped=int(short))
+        if self.error is not None:
+            raise RuntimeError(self.error)
 
-    def dump_result(self, start_cpg, end_cpg):
-        """segment.py:167-190"""
-        if start_cpg.size == 0:
-            eprint('Empty blocks array')
-            return
-        nr_blocks = start_cpg.size
-        s, e = start_cpg, end_cpg
-        if not (s[1:] >= s[:-1]).all():                          # (chromosome by chromosome they already come sorted)
-            order = np.argsort(s, kind='stable')
-            s, e = s[order], e[order]
-        keep = (e - s) > self.args.min_cpg - 1
-        if not keep.all():
-            s, e = s[keep], e[keep]
-        nr_blocks_filt = s.size
-        nr_dropped = nr_blocks - nr_blocks_filt
-        eprint(f'[wt segment] found {nr_blocks_filt:,} blocks\n'
-               f'             (dropped {nr_dropped:,} short blocks)')
-        if hasattr(self, 'report'):
-            self.report.update(blocks_found=int(nr_blocks_filt), blocks_dropped=int(nr_dropped))
-        write_bed(self.genome, s, e, self.args.out_path)
+
+def _n_blocks(off):
+    return int(np.maximum(np.diff(off) - 1, 0).sum())
+
+
+def _n_short(flat, off, min_cpg):
+    """Blocks of a border CSR with fewer than min_cpg sites."""
+    flat, off = np.asarray(flat, dtype=np.int64), np.asarray(off, dtype=np.int64)
+    d = np.diff(flat)
+    inner = np.ones(d.size, dtype=bool)
+    cut = off[1:-1] - 1                                           # the pair that straddles two regions is not a block
+    inner[cut[(cut >= 0) & (cut < d.size)]] = False
+    return int((d[inner] < min_cpg).sum())
+
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -674,3 +669,4 @@ def main(argv=None):
 
 if __name__ == '__main__':
     main()
+
