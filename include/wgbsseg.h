@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 240            /* 0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 241            /* 0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -453,6 +453,9 @@ int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_tot
  * finish() returns WGBSSEG_E_ARG naming the byte offset of the first malformed line, else of the first negative count, else of
  * the first read that starts before the read before it; WGBSSEG_E_CAPACITY for a block of 2^31 rows or more.
  * wgbsseg_bimodal_kernel_ms: device time (HIP events) of all launches so far; waits for them.
+ * wgbsseg_debug_bimodal_terms (test hook, device 0): the arithmetic the EM kernel applies to a pair of column counts, for `count`
+ * pairs (a[q], b[q]) (count <= 2^28).  With pa = 1e-3 + a, pb = 1e-3 + b, n = pa + pb: out holds six rows of `count` double bit
+ * patterns, out[k * count + q] = pa / n, pb / n, log2(pa / n), log2(pb / n), n, a * log2(pa / n) + b * log2(pb / n) for k = 0 .. 5.
  */
 typedef struct wgbsseg_bimodal wgbsseg_bimodal;
 int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, int32_t strict, int32_t min_len,
@@ -461,6 +464,7 @@ int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, 
 int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char* err, size_t errlen);
 void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b);
 double wgbsseg_bimodal_kernel_ms(wgbsseg_bimodal* b);
+int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t count, uint64_t* out);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

@@ -8,6 +8,7 @@
  * exhaustively over the path's whole input domain:
  *     log2f(p)              for every float p in (0, 1]
  *     log2(1.0 - (double)p) for every float p in (0, 1)
+ * and over arrays of doubles (probe_log2_bits_fill): the quotients of the test_bimodal EM's column counts.
  */
 #include <math.h>
 #include <stdint.h>
@@ -113,4 +114,28 @@ uint64_t probe_log2_1mp_maxulp(uint32_t first, uint64_t count, const uint64_t *c
     uint64_t mx = 0;
     for (int t = 0; t < threads; t++) { pthread_join(th[t], NULL); if (jb[t].maxulp > mx) mx = jb[t].maxulp; }
     return mx;
+}
+
+/* out[q] = bits(log2(x)) for the doubles x given by their bit patterns in[q] */
+typedef struct { const uint64_t *in; uint64_t *out; uint64_t a, b; } bits_job;
+static void *bits_worker(void *arg)
+{
+    bits_job *jb = (bits_job *)arg;
+    for (uint64_t q = jb->a; q < jb->b; q++) {
+        double x; memcpy(&x, &jb->in[q], 8);
+        jb->out[q] = bits_of_d(log2(x));
+    }
+    return NULL;
+}
+void probe_log2_bits_fill(const uint64_t *in, uint64_t count, uint64_t *out, int threads)
+{
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    pthread_t th[256]; bits_job jb[256];
+    for (int t = 0; t < threads; t++) {
+        jb[t].in = in; jb[t].out = out;
+        jb[t].a = count * (uint64_t)t / (uint64_t)threads; jb[t].b = count * (uint64_t)(t + 1) / (uint64_t)threads;
+        pthread_create(&th[t], NULL, bits_worker, &jb[t]);
+    }
+    for (int t = 0; t < threads; t++) pthread_join(th[t], NULL);
 }

@@ -3,7 +3,13 @@ product never imports it.  It fixes what the reference leaves to its host: log2 
 a row's likelihood sums its columns left to right from 0.0 with the C and T sums kept apart and combined as (-1.0 + sum_C) + sum_T
 (the reference uses BLAS dgemv, whose order is not defined), a tie goes to cluster 0, and ll0 / new_ll are added in the
 reference's sequential Python order, one addition per row copy.  The device must give the same bits (tests/test_gpu_bimodal.py);
-the reference's own output pins this restatement (tests/golden/bimodal_cases.json)."""
+the reference's own output pins this restatement (tests/golden/bimodal_cases.json).
+
+The contract has two halves of different strength.  Device == this restatement, bit for bit: both take log2 from libm (math.log2
+here, its restatement wg_log2 on the device; tests/test_bimodal_arith_cpu.py ties the two on the EM's own arguments).  This
+restatement == the reference only at print precision (rel 1e-12 and a near-tie allowance, tests/test_bimodal_cpu.py): the
+reference's EM calls np.log2, which is not libm's log2 to the last bit (numpy 2.2.6 against glibc 2.35: 3,337 of 2,000,000 lattice
+arguments differ in the last place), and sums its rows in BLAS's order."""
 import bisect
 import math
 
@@ -51,8 +57,10 @@ def block_reads(starts, reads, s1, s2, strict, min_len):
     return out, first, max_ind - first
 
 
-def em_block(lines, first, ncols):
-    """-> (ll0, ll_em, sum of n_per_col, rows, iterations); rows == 0: (0, 0, 0, 0, 0)"""
+def em_block(lines, first, ncols, trace=None):
+    """-> (ll0, ll_em, sum of n_per_col, rows, iterations); rows == 0: (0, 0, 0, 0, 0).  trace (a list): one dict per pass is
+    appended, rows = the row copies of each cluster, ties = per exact tie l0 == l1 of a line with count > 0 its number of observations,
+    order = per cluster the lines with count > 0 whose likelihood would differ as -1.0 + (sum_C + sum_T)"""
     rows = sum(c for _, _, c in lines)
     if rows == 0:
         return 0.0, 0.0, 0.0, 0, 0
@@ -84,6 +92,7 @@ def em_block(lines, first, ncols):
         cc = [[0] * ncols, [0] * ncols]
         ct = [[0] * ncols, [0] * ncols]
         S = [0.0, 0.0]
+        seen = dict(rows=[0, 0], ties=[], order=[0, 0])
         for o, (_, _, cnt) in zip(obs, lines):
             sc = [0.0, 0.0]
             stt = [0.0, 0.0]
@@ -97,6 +106,11 @@ def em_block(lines, first, ncols):
             l1 = (-1.0 + sc[1]) + stt[1]
             z = 1 if l1 > l0 else 0
             v = l1 if z else l0
+            seen['rows'][z] += cnt
+            if l1 == l0 and cnt:
+                seen['ties'].append(len(o))
+            if cnt and -1.0 + (sc[z] + stt[z]) != v:
+                seen['order'][z] += 1
             s = S[z]
             for _ in range(cnt):
                 s = s + v
@@ -106,6 +120,8 @@ def em_block(lines, first, ncols):
                     cc[z][col] += cnt
                 else:
                     ct[z][col] += cnt
+        if trace is not None:
+            trace.append(seen)
         new_ll = S[0] + S[1]
         more = new_ll - ll > 0
         ll = new_ll

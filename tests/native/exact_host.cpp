@@ -181,6 +181,30 @@ uint64_t lookup_rows_violations(float pc, uint32_t t_lo, uint32_t t_hi)
     }
     return bad;
 }
+// The host twin of bimodal_kernels.h's wg_bim_pair / wg_bim_ll0_term (what k_bim_em computes from a pair of column counts), for
+// `count` pairs: out = six rows of `count` bit patterns, pa / n, pb / n, their log2, n and the ll0 term a * la + b * lb.
+void bimodal_terms_fill(const uint32_t* a, const uint32_t* b, int64_t count, uint64_t* out, int threads)
+{
+    par_for((uint64_t)count, threads, [=](uint64_t q0, uint64_t q1) {
+        for (uint64_t q = q0; q < q1; q++) {
+            const double pa = 1e-3 + (double)a[q], pb = 1e-3 + (double)b[q];
+            const double n = pa + pb;
+            const double qa = pa / n, qb = pb / n;
+            const double la = wg_log2(qa, g_tab.d_tab, g_tab.d_tab2), lb = wg_log2(qb, g_tab.d_tab, g_tab.d_tab2);
+            out[q] = wg_d2u(qa);
+            out[count + q] = wg_d2u(qb);
+            out[2 * count + q] = wg_d2u(la);
+            out[3 * count + q] = wg_d2u(lb);
+            out[4 * count + q] = wg_d2u(n);
+            out[5 * count + q] = wg_d2u((double)a[q] * la + (double)b[q] * lb);
+        }
+    });
+}
+// wg_log2 on arbitrary doubles (bit patterns in and out): the EM's first-pass constants
+void exact_log2_bits_fill(const uint64_t* x, int64_t count, uint64_t* out)
+{
+    for (int64_t q = 0; q < count; q++) out[q] = wg_d2u(wg_log2(wg_u2d(x[q]), g_tab.d_tab, g_tab.d_tab2));
+}
 void exact_sample_terms(const float* nmeth, const float* ntotal, int64_t count, float pc, float* out)
 {
     float pc2 = pc + pc;

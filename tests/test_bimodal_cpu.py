@@ -1,6 +1,7 @@
 """`wgbstools test_bimodal` without a GPU: the golden cases (written by the reference itself, tests/golden/make_golden_bimodal.py)
-against the test restatement tests/bimodal_ref.py, the Benjamini-Hochberg step on hand-worked cases, the command line's checks
-and messages, and the dispatcher."""
+against the test restatement tests/bimodal_ref.py, the census of the hand-built corner cases (tests/bimodal_corners.py: each case
+reaches the corners it is named for), the Benjamini-Hochberg step on hand-worked cases, the command line's checks and messages, and
+the dispatcher."""
 import json
 import os.path as op
 
@@ -8,6 +9,7 @@ import numpy as np
 import pytest
 
 import bimodal_cases as BC
+import bimodal_corners as BK
 import bimodal_ref as BR
 from wgbs_tools_amd import test_bimodal as tb
 from wgbs_tools_amd import wgbs_tools
@@ -82,6 +84,31 @@ def test_cases_reach_their_corners():
     assert any(r[4] == 0 for r in res) and max(r[3] for r in res) > 256
     p = np.array([BR.pvalue(r[0], r[1], r[3], r[4]) for r in res])
     assert (p < 1e-6).any() and (p > 0.5).any()                                              # bimodal and unimodal blocks
+
+
+@pytest.mark.parametrize('name', sorted(BK.cases()))
+def test_corner_case_reaches_its_corners(name):
+    """a case that stops reaching a corner it is named for must not go on passing"""
+    case = BK.cases()[name]
+    got = BK.census(name)
+    assert case['corners'] and case['corners'] <= set(BK.CORNERS)
+    assert not case['corners'] - got, sorted(case['corners'] - got)
+    assert len(case['text']) < 16384                              # a few KB of pat text each
+    assert sum(r[4] for r in BK.want(name)) <= 10 * 200000        # and a restatement that stays in seconds
+
+
+def test_corner_cases_cover_every_corner():
+    named = set().union(*(c['corners'] for c in BK.cases().values()))
+    assert named == set(BK.CORNERS), sorted(set(BK.CORNERS) ^ named)
+    # the numbers behind some of the names
+    deep = BK.want('deep')[0]
+    assert deep[4] <= 200000 and deep[2] > 100000                 # rows; the sum of the columns' counts
+    assert BK.want('slow')[0][5] >= 8
+    zero = BK.want('zero_counts')
+    assert zero[1][3:] == (6, 0, 0) and zero[1][:3] == (0.0, 0.0, 0.0)      # counts all 0: the columns, nothing else
+    lock = BK.cases()['lockstep']
+    assert BK.want('blocks_descending') == BK.want('lockstep')[::-1]
+    assert len(BK.cases()['blocks_shuffled']['s']) > len(lock['s'])
 
 
 def test_fdr_bh_hand_worked():

@@ -1,7 +1,9 @@
 """`wgbstools test_bimodal` on the GPU (k_bim_em and the streaming read table behind wgbsseg_bimodal_*): every golden case of the
 reference through the command line, byte for byte; the device's raw per-block numbers bit for bit against the restatement
-tests/bimodal_ref.py (every case, then a time-boxed seeded random sweep); chunk sizes from a few hundred bytes to the whole file;
-the LDS and the global-memory table paths; the refusals with their byte offsets."""
+tests/bimodal_ref.py (every case, the hand-built corner cases of tests/bimodal_corners.py on both table paths and three chunk
+sizes, a sweep over fixed seeds, then a time-boxed random sweep); the kernel's column-count arithmetic through
+wgbsseg_debug_bimodal_terms against its host twin on the whole lattice of tests/bimodal_lattice.py; chunk sizes from a few hundred
+bytes to the whole file; the LDS and the global-memory table paths; the refusals with their byte offsets."""
 import gzip
 import json
 import os
@@ -12,6 +14,8 @@ import numpy as np
 import pytest
 
 import bimodal_cases as BC
+import bimodal_corners as BK
+import bimodal_lattice as BL
 import bimodal_ref as BR
 from wgbs_tools_amd import _lib, test_bimodal, wgbs_tools
 
@@ -183,6 +187,91 @@ def test_output_file_and_verbose(genome, tmp_path, capsys):
     assert cap.out == ''
     assert cap.err.count('[wt bimodal] finished processesing') == len(BC.CHROMS)
     assert out.read_text().count('\n') == 6
+
+
+def _feed_in_chunks(b, text, size):
+    pos = 0
+    while pos < len(text):
+        cut = text.find(b'\n', min(len(text) - 1, pos + size - 1)) + 1
+        b.feed(text[pos:cut])
+        pos = cut
+
+
+def test_column_terms_match_the_host_twin():
+    """wg_bim_pair / wg_bim_ll0_term as the device evaluates them (fp64 IEEE division, wg_log2 on full-mantissa quotients, both of
+    its branches) against the host build of the same expressions, all six outputs bit for bit on every pair of the lattice.  The
+    host twin, not this machine's libm, is the yardstick: tests/test_bimodal_arith_cpu.py ties the twin to libm."""
+    host = BL.load_host()
+    names = ('pa / n', 'pb / n', 'log2(pa / n)', 'log2(pb / n)', 'n', 'll0 term')
+    bad = dict.fromkeys(names, 0)
+    first = {}
+    pairs = 0
+    t_dev = 0.0
+    for name, a, b in BL.batches():
+        t0 = time.time()
+        got = _lib.debug_bimodal_terms(a, b)
+        t_dev += time.time() - t0
+        want = BL.host_terms(host, a, b)
+        pairs += a.size
+        for k, nm in enumerate(names):
+            d = np.flatnonzero(got[k] != want[k])
+            bad[nm] += d.size
+            if d.size:
+                first.setdefault(nm, (name, int(a[d[0]]), int(b[d[0]]), hex(int(got[k][d[0]])), hex(int(want[k][d[0]]))))
+    print('bimodal column terms: %d pairs, %.2f s in the hook, mismatches %s' % (pairs, t_dev, bad))
+    assert pairs == 8394753 + BL.N_RANDOM + 5 * 2001
+    assert not any(bad.values()), (bad, first)
+
+
+@pytest.mark.parametrize('chunk', ['whole', 4096, 300])
+@pytest.mark.parametrize('cols', [-1, 0, 16])
+@pytest.mark.parametrize('name', sorted(BK.cases()))
+def test_corner_cases_match_restatement(name, cols, chunk):
+    """each hand-built corner (tests/test_bimodal_cpu.py checks that the case reaches it), on the default tables, with every block
+    on global memory and with LDS tables of 16 columns; the text fed whole and in chunks of about 4 KB and 300 B"""
+    c = BK.cases()[name]
+    s, e = np.array(c['s']), np.array(c['e'])
+    with _lib.Bimodal(s, e, c['strict'], c['min_len'], max_lds_cols=cols) as b:
+        _feed_in_chunks(b, c['text'], len(c['text']) if chunk == 'whole' else chunk)
+        ll, cnt = b.finish()
+    want = BK.want(name)
+    _same_bits(ll, cnt, want)
+    for j, w in enumerate(want):                                  # (without rows _same_bits looks at the columns only)
+        if w[4] == 0:
+            assert ll[j].tolist() == [0.0, 0.0, 0.0] and int(cnt[j, 2]) == 0, (j, ll[j], cnt[j])
+
+
+FIXED_SEEDS = tuple(range(20261016, 20261016 + 24))
+
+
+def _fixed_draw(seed):
+    """the draw of test_random_against_restatement from a fixed seed; every third seed is deep: 30 - 200 sites, a few blocks,
+    hundreds of reads with counts up to a few thousand"""
+    rng = np.random.default_rng(seed)
+    deep = seed % 3 == 0
+    n_sites = int(rng.integers(30, 200 if deep else 1500))
+    nb = int(rng.integers(1, 5 if deep else 60))
+    s = rng.integers(1, n_sites, nb)
+    e = s + rng.integers(1, rng.choice([4, 30, 400]), nb)
+    nr = int(rng.integers(100, 400)) if deep else int(rng.integers(1, 1500))
+    st = np.sort(rng.integers(1, n_sites + 5, nr))
+    ln = rng.integers(0, rng.choice([6, 30, 200]), nr)
+    max_count = int(rng.choice([300, 3000])) if deep else 12
+    alphabet = np.array(list('CCTT.H'))
+    lines = ['chr1\t%d\t%s\t%d\n' % (st[i], ''.join(rng.choice(alphabet, ln[i])), rng.integers(0, max_count)) for i in range(nr)]
+    text = ''.join(lines).encode()
+    strict, min_len = bool(rng.integers(0, 2)), int(rng.integers(1, 4))
+    return text, s, e, strict, min_len, int(rng.choice([-1, 0, 8])), int(rng.choice([200, 5000, len(text)]))
+
+
+@pytest.mark.parametrize('seed', FIXED_SEEDS)
+def test_fixed_seeds_against_restatement(seed):
+    """the random comparison below on inputs that are the same for every run of a commit"""
+    text, s, e, strict, min_len, cols, step = _fixed_draw(seed)
+    with _lib.Bimodal(s, e, strict, min_len, max_lds_cols=cols) as b:
+        _feed_in_chunks(b, text, step)
+        ll, cnt = b.finish()
+    _same_bits(ll, cnt, _want(text, s, e, strict, min_len))
 
 
 def test_random_against_restatement():

@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 240          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 241          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -39,7 +39,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_first_batch_items', 'wgbsseg_plan_shares_weighted',
            'wgbsseg_homog_create', 'wgbsseg_homog_feed', 'wgbsseg_homog_finish', 'wgbsseg_homog_destroy', 'wgbsseg_homog_kernel_ms',
            'wgbsseg_debug_homog_bins',
-           'wgbsseg_bimodal_create', 'wgbsseg_bimodal_feed', 'wgbsseg_bimodal_finish', 'wgbsseg_bimodal_destroy', 'wgbsseg_bimodal_kernel_ms']
+           'wgbsseg_bimodal_create', 'wgbsseg_bimodal_feed', 'wgbsseg_bimodal_finish', 'wgbsseg_bimodal_destroy', 'wgbsseg_bimodal_kernel_ms',
+           'wgbsseg_debug_bimodal_terms']
 
 
 class NativeLibraryError(RuntimeError):
@@ -224,6 +225,8 @@ def load():
     L.wgbsseg_homog_kernel_ms.argtypes = [vp]
     L.wgbsseg_debug_homog_bins.restype = i32
     L.wgbsseg_debug_homog_bins.argtypes = [vp, i32, i32, vp]
+    L.wgbsseg_debug_bimodal_terms.restype = i32
+    L.wgbsseg_debug_bimodal_terms.argtypes = [vp, vp, i64, vp]
     L.wgbsseg_bimodal_create.restype = i32
     L.wgbsseg_bimodal_create.argtypes = [i32, vp, vp, i64, i32, i32, i32, C.POINTER(vp), C.c_char_p, C.c_size_t]
     L.wgbsseg_bimodal_feed.restype = i32
@@ -604,6 +607,21 @@ def debug_homog_bins(edges, max_total):
     rc = L.wgbsseg_debug_homog_bins(r.ctypes.data, r.size - 1, int(max_total), out.ctypes.data)
     if rc != OK:
         raise SegmentorError(rc, 'debug_homog_bins failed')
+    return out
+
+
+def debug_bimodal_terms(a, b):
+    """wgbsseg_debug_bimodal_terms: uint64 [6][n] bit patterns of pa / n, pb / n, their log2, n and the ll0 term of the column
+    counts (a[q], b[q]) (uint32), as k_bim_em computes them"""
+    L = load()
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    b = np.ascontiguousarray(b, dtype=np.uint32)
+    if a.shape != b.shape or a.ndim != 1:
+        raise ValueError('a / b: one value per pair')
+    out = np.empty((6, a.size), dtype=np.uint64)
+    rc = L.wgbsseg_debug_bimodal_terms(a.ctypes.data, b.ctypes.data, a.size, out.ctypes.data)
+    if rc != OK:
+        raise SegmentorError(rc, 'debug_bimodal_terms failed')
     return out
 
 

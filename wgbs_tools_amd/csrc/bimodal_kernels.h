@@ -77,6 +77,23 @@ __device__ __forceinline__ long long wg_bim_lower(const int32_t* a, long long lo
 
 __device__ __forceinline__ uint32_t wg_bim_code(char c) { return c == 'C' ? 1u : (c == 'T' ? 2u : 0u); }
 
+// What k_bim_em computes from a pair of column counts (a, b) = (#C, #T): pa = 1e-3 + a, pb = 1e-3 + b, n = pa + pb, the IEEE
+// quotients pa / n and pb / n and their log2 (the between-pass tables l_p_c / l_p_t), and the column's ll0 term a * la + b * lb.
+// k_bim_debug_terms (the test hook) evaluates the same function; tests/native/exact_host.cpp carries its host twin.
+struct wg_bim_terms { double n, qa, qb, la, lb; };
+__device__ __forceinline__ wg_bim_terms wg_bim_pair(uint32_t a, uint32_t b, const wg_d2* __restrict__ dt, const wg_d2* __restrict__ dt2)
+{
+    wg_bim_terms r;
+    const double pa = 1e-3 + (double)a, pb = 1e-3 + (double)b;
+    r.n = pa + pb;
+    r.qa = pa / r.n;
+    r.qb = pb / r.n;
+    r.la = wg_log2(r.qa, dt, dt2);
+    r.lb = wg_log2(r.qb, dt, dt2);
+    return r;
+}
+__device__ __forceinline__ double wg_bim_ll0_term(uint32_t a, uint32_t b, const wg_bim_terms& r) { return (double)a * r.la + (double)b * r.lb; }
+
 // Pass 1 over a chunk: per tile, the number of good lines and of their pattern words.  Malformed lines and negative counts
 // are reported (lowest byte offset) and left out of the table (both kernels skip the same lines).
 __global__ __launch_bounds__(WG_BLOCK) void k_bim_tile_count(const char* __restrict__ text, int64_t n, uint32_t* __restrict__ tile_cnt,
@@ -283,10 +300,10 @@ __global__ __launch_bounds__(WG_BIM_WAVE) void k_bim_em(const int32_t* __restric
     }
     __syncthreads();
     for (long long j = lane; j < nc; j += WG_BIM_WAVE) {
-        const double C = (double)cn[j], Tn = (double)cn[2 * nc + j];
-        const double c = 1e-3 + C, t = 1e-3 + Tn, nn = c + t;
-        lp[j] = C * wg_log2(c / nn, dt, dt2) + Tn * wg_log2(t / nn, dt, dt2);
-        lp[nc + j] = nn;
+        const uint32_t C = cn[j], Tn = cn[2 * nc + j];
+        const wg_bim_terms r = wg_bim_pair(C, Tn, dt, dt2);
+        lp[j] = wg_bim_ll0_term(C, Tn, r);
+        lp[nc + j] = r.n;
         cn[j] = 0u; cn[2 * nc + j] = 0u;
     }
     __syncthreads();
@@ -349,10 +366,9 @@ __global__ __launch_bounds__(WG_BIM_WAVE) void k_bim_em(const int32_t* __restric
         ll = nll;
         for (long long j = lane; j < nc; j += WG_BIM_WAVE) {
             for (int z = 0; z < 2; z++) {
-                const double pc = 1e-3 + (double)cn[z * nc + j], pt = 1e-3 + (double)cn[(2 + z) * nc + j];
-                const double tot = pc + pt;
-                lp[z * nc + j] = wg_log2(pc / tot, dt, dt2);
-                lp[(2 + z) * nc + j] = wg_log2(pt / tot, dt, dt2);
+                const wg_bim_terms r = wg_bim_pair(cn[z * nc + j], cn[(2 + z) * nc + j], dt, dt2);
+                lp[z * nc + j] = r.la;
+                lp[(2 + z) * nc + j] = r.lb;
                 cn[z * nc + j] = 0u; cn[(2 + z) * nc + j] = 0u;
             }
         }
@@ -365,6 +381,21 @@ __global__ __launch_bounds__(WG_BIM_WAVE) void k_bim_em(const int32_t* __restric
     if (lane == 0) {
         res_f[3 * b] = ll0; res_f[3 * b + 1] = ll; res_f[3 * b + 2] = sum_n;
         res_i[3 * b] = nc; res_i[3 * b + 1] = rows; res_i[3 * b + 2] = iters;
+    }
+}
+
+// test hook: wg_bim_pair / wg_bim_ll0_term on arrays of (a, b); out = six rows of `count` bit patterns: qa, qb, la, lb, n, the ll0 term
+__global__ __launch_bounds__(WG_BLOCK) void k_bim_debug_terms(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, int64_t count,
+                                                              uint64_t* __restrict__ out)
+{
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < count; q += (int64_t)gridDim.x * blockDim.x) {
+        const wg_bim_terms r = wg_bim_pair(a[q], b[q], g_wg_tables.d_tab, g_wg_tables.d_tab2);
+        out[q] = wg_d2u(r.qa);
+        out[count + q] = wg_d2u(r.qb);
+        out[2 * count + q] = wg_d2u(r.la);
+        out[3 * count + q] = wg_d2u(r.lb);
+        out[4 * count + q] = wg_d2u(r.n);
+        out[5 * count + q] = wg_d2u(wg_bim_ll0_term(a[q], b[q], r));
     }
 }
 

@@ -3049,6 +3049,28 @@ int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_tot
     return e == hipSuccess ? WGBSSEG_OK : WGBSSEG_E_HIP;
 }
 
+int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t count, uint64_t* out)
+{
+    if (!a || !b || !out || count < 1 || count > (1ll << 28)) return WGBSSEG_E_ARG;
+    char err[256];
+    const size_t errlen = sizeof(err);
+    uint32_t* d_ab = nullptr;
+    uint64_t* d_out = nullptr;
+    HIP_TRY(hipMalloc(&d_ab, 2 * sizeof(uint32_t) * (size_t)count));
+    if (hipMalloc(&d_out, 6 * sizeof(uint64_t) * (size_t)count) != hipSuccess) { (void)hipFree(d_ab); return WGBSSEG_E_HIP; }
+    hipError_t e = hipMemcpy(d_ab, a, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_ab + count, b, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const unsigned blocks = (unsigned)std::min<int64_t>((count + WG_BLOCK - 1) / WG_BLOCK, 16384);
+        hipLaunchKernelGGL(k_bim_debug_terms, dim3(blocks), dim3(WG_BLOCK), 0, 0, d_ab, d_ab + count, count, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out, d_out, 6 * sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost);
+    (void)hipFree(d_ab);
+    (void)hipFree(d_out);
+    return e == hipSuccess ? WGBSSEG_OK : WGBSSEG_E_HIP;
+}
+
 }  // extern "C"
 
 // `wgbstools test_bimodal` accumulator on one device: the blocks, the read table of the live window (two copies: dropping moves
