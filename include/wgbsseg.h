@@ -235,7 +235,8 @@ int wgbsseg_group_segment_regions(wgbsseg_group* g, int32_t* borders_out, int64_
 /*
  * The same over a SLICE of the planned regions, [first_region, end_region): regions never interact (segment.py:84-86,129-134), so a caller may
  * take them in slices and do something with one slice's blocks — write their BED rows — while the next slice is segmented and the beta bytes of
- * the later regions are still on their way up (wgbsseg_group_load_host_async streams site-major): `wgbstools segment` does (round 6).  borders_off has
+ * the later regions are still on their way up (wgbsseg_group_load_host_async streams site-major): `wgbstools segment` does when WGBSSEG_BED_SLICES asks
+ * for more than one slice (opt-in; by default it takes all regions as one).  borders_off has
  * end_region - first_region + 1 entries.  The slices of one pass must be taken in ascending order; the uploaders are collected with the last one.
  */
 int wgbsseg_group_segment_region_range(wgbsseg_group* g, int64_t first_region, int64_t end_region, int32_t* borders_out, int64_t borders_cap,

@@ -25,6 +25,7 @@
 #include <utility>
 #include <vector>
 #include <unistd.h>
+#include "env.h"
 
 namespace wgstitch {
 
@@ -258,8 +259,7 @@ public:
 private:
     Pool()
     {
-        int t = (int)std::min<unsigned>(8, std::max<unsigned>(1, std::thread::hardware_concurrency() / 2));
-        if (const char* e = getenv("WGBSSEG_STITCH_THREADS")) t = std::max(1, atoi(e));
+        const int t = (int)env_int("WGBSSEG_STITCH_THREADS", std::min<unsigned>(8, std::thread::hardware_concurrency() / 2), 1);
         for (int i = 1; i < t; i++) { workers_.emplace_back([this] { loop(); }); workers_.back().detach(); }
     }
     static int64_t now_us() { return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -416,7 +416,7 @@ inline int segment_regions(const int64_t* region_start, const int64_t* region_en
     typedef std::chrono::steady_clock Clock;
     const Clock::time_point t_begin = Clock::now();
     int64_t us_batches = 0;
-    const bool prof = getenv("WGBSSEG_PROFILE_STITCH") != nullptr;
+    const bool prof = env_flag("WGBSSEG_PROFILE_STITCH", false);
     std::vector<std::pair<const char*, Clock::time_point>> marks;
     auto mark = [&](const char* what) { if (prof) marks.emplace_back(what, Clock::now()); };
     mark("begin");

@@ -28,6 +28,7 @@
 #endif
 
 #include "../../include/wgbsseg.h"
+#include "owners.h"
 #include "seg_kernels.h"
 #include "pat_kernels.h"
 #include "homog_kernels.h"
@@ -38,30 +39,6 @@
 #include "table_io.h"
 
 namespace {
-
-inline double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// WGBSSEG_PROFILE=1: where the host time of a call goes (allocations, upload), on stderr
-inline bool profiling() { static const bool on = getenv("WGBSSEG_PROFILE") && atoi(getenv("WGBSSEG_PROFILE")); return on; }
-std::atomic<long long> g_alloc_us(0), g_alloc_bytes(0), g_alloc_calls(0);
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= cap) return hipSuccess;
-        const double t0 = profiling() ? wall_s() : 0.0;
-        if (p) { hipError_t e = hipFree(p); p = nullptr; cap = 0; if (e != hipSuccess) return e; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { e = hipMalloc(&p, bytes); want = bytes; }
-        if (e == hipSuccess) cap = want;
-        if (profiling()) { g_alloc_us += (long long)((wall_s() - t0) * 1e6); g_alloc_bytes += (long long)want; g_alloc_calls += 1; }
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 void set_err(char* err, size_t errlen, const char* fmt, ...)
 {
@@ -85,35 +62,8 @@ void set_err(char* err, size_t errlen, const char* fmt, ...)
 hipError_t set_kernel_attributes();      // defined below, next to the kernel launchers
 inline int ceil_pow2(int v) { int r = 1; while (r < v) r <<= 1; return r; }
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-// a switch of the environment, as an integer (`def` when it is not set): read when a context is created
-inline int env_int(const char* name, int def) { const char* e = getenv(name); return e ? atoi(e) : def; }
 
 }  // namespace
-
-struct PinnedBuf {          // grow-only page-locked host buffer (fast, truly asynchronous D2H)
-    void* p = nullptr;
-    size_t cap = 0;
-    bool ensure(size_t bytes)
-    {
-        if (bytes <= cap) return true;
-        const double t0 = profiling() ? wall_s() : 0.0;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        const size_t want = bytes + bytes / 4 + 4096;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-        cap = want;
-        if (profiling()) { g_alloc_us += (long long)((wall_s() - t0) * 1e6); g_alloc_bytes += (long long)want; g_alloc_calls += 1; }
-        return true;
-    }
-    bool ensure_exact(size_t bytes)
-    {
-        if (bytes <= cap) return true;
-        if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
-        if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-        cap = bytes;
-        return true;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
 
 #define WG_MAX_CPUS 8192
 struct NearCpus { std::vector<unsigned long> bits; bool valid = false; };      // affinity mask of the CPUs next to a device
@@ -125,8 +75,8 @@ enum BatchEvent { EV_BEGIN, EV_WINDOWS, EV_SCAN_END, EV_PLAN, EV_TRACE0, EV_TRAC
 struct wgbsseg_ctx {
     int device = 0;
     NearCpus near_cpus;          // the upload threads run there (worked out once, at create)
-    hipStream_t sA = nullptr, sB = nullptr, sC = nullptr;     // scoring (+ everything else) | recurrence, traceback | the scan pass
-    hipStream_t sA2 = nullptr;                                // second scoring stream: medium / wide tiles beside the narrow ones (stage loop)
+    Stream sA, sB, sC;     // scoring (+ everything else) | recurrence, traceback | the scan pass
+    Stream sA2;                                // second scoring stream: medium / wide tiles beside the narrow ones (stage loop)
     // inputs
     DevBuf betas_own, loci_own;
     const uint8_t* betas = nullptr;
@@ -140,22 +90,22 @@ struct wgbsseg_ctx {
     DevBuf chunks, wtile, carry, W16, cum32, back16, chunk_pairs, status, tile_tot, tile_base, tile_chunk;
     DevBuf plan_cbase, plan_cum0, plan_tbase, plan_pairs, plan_tiles, plan_cnt, umax16;
     std::vector<PinnedBuf> pinned;
-    std::vector<PinnedBuf> up_stage;   // two page-locked staging pieces per upload thread (set_betas_host)
+    std::vector<PinnedBuf> up_stage;   // the page-locked staging pieces of the uploads, `depth` per upload thread (run_upload); kept until destroy
     DevBuf tiles[3], cost[3], stage_ctr, dpstate, tmp_borders, nb, boff, out_borders[2], edges, dbg_a, dbg_b, dbg_c, lookup;
     int out_par = 0;              // which of the two result buffers the batch in flight writes: the lists of the previous batch may still be on their way home (below)
     // early delivery (segment_regions' first batch): k_copy_out (on the scan stream) writes the chunks' border lists into the page-locked result ...
-    hipEvent_t evS = nullptr;     // the scan stream's last command of the batch in flight (the copy of its verdict)
-    hipEvent_t evD = nullptr;     // ... while the host already rehearses the junctions on the lists' edges and runs the follow-up batch; evD: the lists are home
+    Event evS;     // the scan stream's last command of the batch in flight (the copy of its verdict)
+    Event evD;     // ... while the host already rehearses the junctions on the lists' edges and runs the follow-up batch; evD: the lists are home
     bool out_pending = false;
     bool batch_open = false;      // a batch is between its first launch and its clean end (an error return leaves it set: the next batch drains the device first)
     std::vector<wg_d2> h_lookup;   // host copy of the k-scaled log tables of the call in flight (source of an async upload)
     float lookup_pc = -1.0f;       // what the device copy `lookup` was built for: pseudo count and exponent rows of the narrow / wide / medium class
     int lookup_rows[3] = {-1, -1, -1};
-    hipEvent_t ev[EV_COUNT] = {};   // a batch's events (BatchEvent); the context's other calls time themselves between ev[0] and ev[1]
+    Event ev[EV_COUNT];   // a batch's events (BatchEvent); the context's other calls time themselves between ev[0] and ev[1]
     PinnedBuf h_status;      // page-locked landing area of the status words: D2H copies that really are asynchronous
     PinnedBuf h_job, h_pieces, h_sb;   // ... the staging areas of a job's tables on their way up (chunk table, window tiles, cleared status | k_validate's pieces)
     PinnedBuf h_out;         // ... and of a batch's CSR offsets (a small batch: of its border lists too)
-    std::vector<hipEvent_t> ev_cost0, ev_cost1, ev_dp0, ev_dp1, ev_fork, ev_join;     // per stage
+    std::vector<Event> ev_cost0, ev_cost1, ev_dp0, ev_dp1, ev_fork, ev_join;     // per stage
     // last-call info
     wgbsseg_timings tim = {};
     int64_t last_sites = 0, last_pairs = 0;
@@ -164,14 +114,11 @@ struct wgbsseg_ctx {
     long long cost_budget_bytes = 0;
     int force_stages = 0;
     bool counted_live = false;
-    double stage_gate_wide_evals = 100000.0;                  // jobs with medium / wide tiles are gated from this many evaluations per step on
-    bool stage_gate_shared = false;                           // (tests) gate even when other contexts live on the device, and whatever the job's tiles
-    int stage_gate = 768;                                     // > 0: the stages of a staged all-narrow job alternate between the two scoring streams behind k_stage_gate; the value = tiles of slack
-    double stage_min_evals_per_step = 21000.0;                // staging for few chunks only from this many evaluations per step of the longest chunk
-    int last_stage_pct = -1;                                  // length of a staged job's LAST stage (whose recurrence nothing hides) in percent of the other stages'
-    int force_dp_mode = 0;   // WGBSSEG_DP_MODE: 1 = 32-step batches (wide-window path), 2 = the same with 15 worker waves
-    int force_ns = 0;
-    int force_ti = 0;
+    // staging and tiling as the environment asks (env.h: WGBSSEG_STAGE_GATE_WIDE_EVALS, _STAGE_MIN_EVALS, _STAGE_GATE_SHARED, _STAGE_GATE, _LAST_STAGE_PCT, _DP_MODE, _NS, _TI).
+    // stage_gate > 0: the stages of a staged job alternate between the two scoring streams behind k_stage_gate; last_stage_pct -1: chosen per job
+    double stage_gate_wide_evals = 100000.0, stage_min_evals_per_step = 21000.0;
+    bool stage_gate_shared = false;
+    int stage_gate = 768, last_stage_pct = -1, force_dp_mode = 0, force_ns = 0, force_ti = 0;
     double last_block_sums_ms = 0.0;
     int64_t table_blocks = 0;  // > 0: dbg_b still holds the [n_samples][table_blocks] ratio table of the last mode-3 block reduction
     bool accumulate = false;   // add to `tim` instead of resetting it (region-level calls span several batches)
@@ -187,76 +134,227 @@ struct wgbsseg_ctx {
     int64_t last_dp_chunks = 0, last_dp_stride = 0;
     float divs_m_pc = -1.0f;   // the same for the operand pairs of a medium tile (ntotal <= 255 * WG_MEDIUM_WMAX)
     bool divs_m_ok = false;
-    bool divs_enabled = true;  // WGBSSEG_DIV_SHORT=0: always the 8-instruction core
-    bool bs_general = false;   // WGBSSEG_BLOCK_SUMS_GENERAL=1: never the streaming block-sums kernel
-    int64_t scan_piece_sites = 4096;    // WGBSSEG_SCAN_PIECE_SITES: sites per wave task of k_validate (multiple of 1024)
-    int medium_wmax = WG_MEDIUM_WMAX;   // WGBSSEG_MEDIUM_WMAX: widest window of a medium tile (0: no medium class)
-    bool dp_wlean = true;      // WGBSSEG_DP_WLEAN=0: the narrow batches of a wide job on k_dp's generic step
-    bool early = true;         // WGBSSEG_NO_EARLY=1: the first batch of a region-level call delivers everything at once
-    bool speculate = true;     // WGBSSEG_NO_SPECULATION=1: junction patches only when the reference would ask for them
-    bool batch_marks = false;  // WGBSSEG_PROFILE >= 2: every batch's device time line and host clock on stderr
+    // the switches of the environment as create_ctx read them (env.h has the table): WGBSSEG_DIV_SHORT, _BLOCK_SUMS_GENERAL, _SCAN_PIECE_SITES,
+    // _MEDIUM_WMAX (0: no medium class), _DP_WLEAN, not _NO_EARLY, not _NO_SPECULATION, _PROFILE >= 2
+    bool divs_enabled = true, bs_general = false;
+    int64_t scan_piece_sites = 4096;
+    int medium_wmax = WG_MEDIUM_WMAX;
+    bool dp_wlean = true, early = true, speculate = true, batch_marks = false;
+    // Everything above frees itself, in reverse order of declaration — the streams last; by then nothing runs on the device any more.
+    ~wgbsseg_ctx() { (void)hipSetDevice(device); (void)hipDeviceSynchronize(); }
 };
 
 namespace {
 
-bool device_local_cpus(int device, NearCpus* out);      // (below, with the streaming upload)
-inline void pin_to(const NearCpus& n);
+// The CPUs next to a device: /sys/bus/pci/devices/<bus id>/local_cpulist (e.g. "0-63,128-191"), cut to the CPUs this process may run on, as an
+// affinity mask of up to WG_MAX_CPUS CPUs (a fixed cpu_set_t stops at 1024 and sched_getaffinity then FAILS on a larger host: ADVICE r05).  Worked out
+// once per context (create).  An upload thread that runs on the OTHER socket of a two-socket host fills page-locked pieces over there and the DMA then crosses the
+// socket link: measured on an MI355X box (round 5, x200 = 11.3 GB): the same upload at 9 .. 35 GB/s from run to run with free-running
+// threads.  false: unknown (no sysfs, every CPU listed, WGBSSEG_UPLOAD_PIN=0) — the threads then run where the scheduler puts them.
+bool device_local_cpus(int device, NearCpus* out)
+{
+    out->valid = false;
+    if (!env_flag("WGBSSEG_UPLOAD_PIN", true)) return false;
+    char bus[64] = {0};
+    if (hipDeviceGetPCIBusId(bus, (int)sizeof bus, device) != hipSuccess) { (void)hipGetLastError(); return false; }
+    for (char* q = bus; *q; q++) if (*q >= 'A' && *q <= 'F') *q = (char)(*q - 'A' + 'a');       // sysfs names are lower case
+    char path[160];
+    snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/local_cpulist", bus);
+    FILE* f = fopen(path, "r");
+    if (!f) return false;
+    char line[8192] = {0};
+    const bool got = fgets(line, (int)sizeof line, f) != nullptr;
+    fclose(f);
+    if (!got) return false;
+    const size_t bytes = CPU_ALLOC_SIZE(WG_MAX_CPUS);
+    std::vector<unsigned long> allowed(bytes / sizeof(unsigned long), 0ul);
+    out->bits.assign(bytes / sizeof(unsigned long), 0ul);
+    cpu_set_t* A = reinterpret_cast<cpu_set_t*>(allowed.data());
+    cpu_set_t* L = reinterpret_cast<cpu_set_t*>(out->bits.data());
+    if (sched_getaffinity(0, bytes, A) != 0) return false;
+    int n_local = 0;
+    for (const char* q = line; *q;) {
+        while (*q == ',' || *q == ' ' || *q == '\n') q++;
+        if (*q < '0' || *q > '9') break;
+        char* end = nullptr;
+        long a = strtol(q, &end, 10), b = a;
+        if (*end == '-') b = strtol(end + 1, &end, 10);
+        for (long x = a; x <= b && x < WG_MAX_CPUS; x++) if (CPU_ISSET_S((int)x, bytes, A)) { CPU_SET_S((int)x, bytes, L); n_local++; }
+        q = end;
+    }
+    if (n_local == 0 || n_local == CPU_COUNT_S(bytes, A)) return false;      // nothing to choose from
+    out->valid = true;
+    return true;
+}
+inline void pin_to(const NearCpus& n)
+{
+    if (n.valid) (void)pthread_setaffinity_np(pthread_self(), n.bits.size() * sizeof(unsigned long), reinterpret_cast<const cpu_set_t*>(n.bits.data()));
+}
+// Page-cached file bytes -> a page-locked staging piece (round 6, profiles/r06_upload_ab.txt):
+//   * the piece's pages are mapped in ONE call (madvise MADV_POPULATE_READ, Linux >= 5.14) instead of a minor fault per 4 KB page as the copy touches them;
+//   * non-temporal stores: the staging piece is written once and read by the DMA engine — no read-for-ownership, no cache pollution.
+// WGBSSEG_UPLOAD_POPULATE=0 / WGBSSEG_UPLOAD_NT=0 switch either off (A/B).  x200 (11.3 GB) end to end on one box: 0.38-0.45 s -> 0.32 s with both and
+// 8 x 2 MB pieces; x32 0.107-0.114 -> 0.098-0.110.  The rate of ONE setting still swings between 30 and 47 GB/s from run to run on the same box.
+struct FillMode { bool populate = true, nt = true; };
+inline void fill_piece(void* dst, const uint8_t* src, size_t n, const FillMode& m)
+{
+#ifdef MADV_POPULATE_READ
+    if (m.populate) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(src) & ~(uintptr_t)4095, b = (reinterpret_cast<uintptr_t>(src) + n + 4095) & ~(uintptr_t)4095;
+        (void)madvise(reinterpret_cast<void*>(a), b - a, MADV_POPULATE_READ);      // (an error — an old kernel, not a mapping — just leaves the faults to the copy)
+    }
+#endif
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+    if (m.nt && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        __m128i* d = reinterpret_cast<__m128i*>(dst);
+        const __m128i* s = reinterpret_cast<const __m128i*>(src);
+        size_t v = n >> 6;
+        for (; v > 0; v--, s += 4, d += 4) {
+            const __m128i x0 = _mm_loadu_si128(s), x1 = _mm_loadu_si128(s + 1), x2 = _mm_loadu_si128(s + 2), x3 = _mm_loadu_si128(s + 3);
+            _mm_stream_si128(d, x0); _mm_stream_si128(d + 1, x1); _mm_stream_si128(d + 2, x2); _mm_stream_si128(d + 3, x3);
+        }
+        _mm_sfence();
+        const size_t done = n & ~(size_t)63;
+        if (n > done) memcpy(static_cast<char*>(dst) + done, src + done, n - done);
+        return;
+    }
+#endif
+    memcpy(dst, src, n);
+}
+// What one upload call does: the five WGBSSEG_UPLOAD_* switches are read here and nowhere else, per call.  The two forms:
+//   blocking (set_betas_host, set_lbetas_host, set_loci_host, group_load_host): 4 MB pieces, 4 threads (small inputs fewer: below two, the plain copy of
+//     upload_rows), two pieces per thread, filled by memcpy, rows one after the other.  One thread drives ~33 GB/s (page faults + the copy into page-locked
+//     staging); a few threads, each with its own stream, fill the link (measured 46 GB/s with 4; more threads only contend).
+//   streaming (group_load_host_async): 4 threads x 1 MB, from 4 GB up 8 x 2 MB, WGBSSEG_UPLOAD_DEPTH pieces per thread, filled by fill_piece, piece-major:
+//     piece p of EVERY row before piece p + 1 of any, which is what makes a prefix of the sites ready for the segmenter while the rest is on its way.
+//     (Measured, free-running threads: 4 threads x 1 MB 33.5 GB/s, x 2 MB 26-29, 8-16 threads 17-30: profiles/r02_upload_sweep.txt.  Round 5, threads on the
+//     device's CPUs: 8 threads x 4 MB 37-42 GB/s on 11.3 GB (x200: 0.35-0.38 s end to end against 0.43-0.50 with 4 x 1 MB); x32's 1.8 GB the same either
+//     way: profiles/r05_upload_pinned_ab.txt.  Round 6: 8 x 2 MB with the pieces' pages mapped per call and a non-temporal fill: x200 0.32 s end to end on
+//     both runs of the A/B against 0.33-0.45 for 8 x 4 MB, profiles/r06_upload_ab.txt.)
+struct UploadPlan {
+    int64_t piece = 0, ppr = 0, n_tasks = 0;     // bytes of a staging piece; pieces per row; pieces in all
+    int T = 1, depth = 2;                        // upload threads; staging pieces (copies in flight) per thread
+    bool piece_major = false;                    // task it = p * n_rows + r, not r * ppr + p
+    FillMode fill = {false, false};
+};
+UploadPlan plan_upload(bool streaming, int64_t n_rows, int64_t row_bytes)
+{
+    UploadPlan u;
+    const int64_t bytes = row_bytes * n_rows;
+    const bool big = streaming && bytes >= (4LL << 30);
+    const long long kb = env_int("WGBSSEG_UPLOAD_PIECE_KB", 0), threads = env_int("WGBSSEG_UPLOAD_THREADS", 0);
+    u.piece = kb >= 64 ? (int64_t)kb << 10 : streaming ? (big ? 2 << 20 : 1 << 20) : 4 << 20;
+    u.ppr = (row_bytes + u.piece - 1) / u.piece;
+    u.n_tasks = u.ppr * n_rows;
+    const int64_t T = std::min<int64_t>(threads > 0 ? threads : big ? 8 : 4, 64);
+    u.T = (int)std::max<int64_t>(1, std::min<int64_t>(T, streaming ? u.n_tasks : std::min<int64_t>(u.n_tasks / 2, bytes >> 24)));
+    u.piece_major = streaming;
+    if (streaming) {
+        const long long depth = env_int("WGBSSEG_UPLOAD_DEPTH", 2);
+        if (depth >= 2 && depth <= 8) u.depth = (int)depth;
+        u.fill.populate = env_flag("WGBSSEG_UPLOAD_POPULATE", true);
+        u.fill.nt = env_flag("WGBSSEG_UPLOAD_NT", true);
+    }
+    return u;
+}
 
-// Pageable host rows (typically memory-mapped .beta files) -> HBM: dst + r * dst_pitch <- rows[r][0 .. row_bytes).
-// One thread drives ~33 GB/s of that (page faults + the copy into page-locked staging); a few threads, each with its
-// own stream and two 4 MB staging pieces, fill the link (measured 46 GB/s with 4; more threads only contend).
+// The upload loop: pageable host rows (typically memory-mapped .beta files) -> HBM, dst + r * dst_pitch <- rows[r][0 .. row_bytes), in pieces that
+// u.T threads claim one after the other.  A thread runs on the device's CPUs with a stream of its own and u.depth staging pieces of the context
+// (c->up_stage; allocated — and so first touched — by the thread itself, after pin_to: they sit on that socket), and calls landed(it) when piece `it`
+// is on the device.  Returns every thread's verdict.
+template <class Landed>
+std::vector<hipError_t> run_upload(wgbsseg_ctx* c, const UploadPlan& u, uint8_t* dst, int64_t dst_pitch, const uint8_t* const* rows, int64_t n_rows,
+                                   int64_t row_bytes, Landed landed)
+{
+    const int depth = u.depth;
+    if (c->up_stage.size() < (size_t)(depth * u.T)) c->up_stage.resize((size_t)(depth * u.T));
+    std::atomic<int64_t> next(0);
+    std::vector<hipError_t> terr((size_t)u.T, hipSuccess);
+    auto worker = [&](int t) {
+        pin_to(c->near_cpus);
+        hipError_t e = hipSetDevice(c->device);
+        PinnedBuf* const stg = &c->up_stage[(size_t)(depth * t)];
+        for (int k = 0; k < depth && e == hipSuccess; k++) if (!stg[k].ensure_exact((size_t)u.piece)) e = hipErrorOutOfMemory;
+        Stream st;
+        Event ev[8];
+        int64_t task_of[8] = {-1, -1, -1, -1, -1, -1, -1, -1};      // the piece whose copy was queued last from slot k (-1: none in flight)
+        if (e == hipSuccess) e = st.create();
+        for (int k = 0; k < depth && e == hipSuccess; k++) e = ev[k].create(false);
+        auto settle = [&](int k) {                                  // slot k's previous copy has left the piece
+            if (task_of[k] < 0) return;
+            e = hipEventSynchronize(ev[k]);
+            if (e == hipSuccess) landed(task_of[k]);
+            task_of[k] = -1;
+        };
+        int k = 0;
+        while (e == hipSuccess) {
+            const int64_t it = next.fetch_add(1);
+            if (it >= u.n_tasks) break;
+            const int64_t p = u.piece_major ? it / n_rows : it % u.ppr, r = u.piece_major ? it % n_rows : it / u.ppr;
+            const int64_t o = p * u.piece, b = std::min<int64_t>(u.piece, row_bytes - o);
+            settle(k);
+            if (e != hipSuccess) break;
+            fill_piece(stg[k].p, rows[r] + o, (size_t)b, u.fill);
+            e = hipMemcpyAsync(dst + r * dst_pitch + o, stg[k].p, (size_t)b, hipMemcpyHostToDevice, st);
+            if (e == hipSuccess) e = hipEventRecord(ev[k], st);
+            task_of[k] = it;
+            k = (k + 1) % depth;
+        }
+        for (int q = 0; q < depth && e == hipSuccess; q++, k = (k + 1) % depth) settle(k);
+        if (st) { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; }      // (after an error too: no copy may outlive the call, the pieces stay)
+        terr[(size_t)t] = e;
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < u.T; t++) th.emplace_back(worker, t);
+    for (auto& x : th) x.join();
+    return terr;
+}
+
 int upload_rows(wgbsseg_ctx* c, uint8_t* dst, int64_t dst_pitch, const uint8_t* const* rows, int64_t n_rows, int64_t row_bytes,
                 const char* what, char* err, size_t errlen)
 {
     const double t0 = wall_s();
-    int64_t piece = 4 << 20;
-    { const char* e = getenv("WGBSSEG_UPLOAD_PIECE_KB"); if (e && atoi(e) >= 64) piece = (int64_t)atoi(e) << 10; }
-    const int64_t pieces_per_row = (row_bytes + piece - 1) / piece, n_pieces = pieces_per_row * n_rows;
-    int T = 4;
-    { const char* e = getenv("WGBSSEG_UPLOAD_THREADS"); if (e && atoi(e) > 0) T = atoi(e); }
-    T = (int)std::min<int64_t>(std::min<int64_t>(T, 64), std::max<int64_t>(1, std::min<int64_t>(n_pieces / 2, (row_bytes * n_rows) >> 24)));   // small inputs: the plain copy
-    if (T <= 1) {
+    const UploadPlan u = plan_upload(false, n_rows, row_bytes);
+    if (u.T <= 1) {      // small inputs: the plain copy
         for (int64_t r = 0; r < n_rows; r++)
             HIP_TRY(hipMemcpyAsync(dst + r * dst_pitch, rows[r], (size_t)row_bytes, hipMemcpyHostToDevice, c->sA));
         HIP_TRY(hipStreamSynchronize(c->sA));
     } else {
-        if (c->up_stage.size() < (size_t)(2 * T)) c->up_stage.resize((size_t)(2 * T));
-        std::atomic<int64_t> next(0);
-        std::vector<hipError_t> terr((size_t)T, hipSuccess);
-        auto worker = [&](int t) {
-            pin_to(c->near_cpus);
-            hipError_t e = hipSetDevice(c->device);
-            // (its two staging pieces are allocated — first touched — by the worker itself, on the device's CPUs: they sit on that socket)
-            for (int k = 0; k < 2 && e == hipSuccess; k++) if (!c->up_stage[(size_t)(2 * t + k)].ensure_exact((size_t)piece)) e = hipErrorOutOfMemory;
-            hipStream_t st = nullptr;
-            hipEvent_t ev[2] = {nullptr, nullptr};
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-            for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-            bool busy[2] = {false, false};
-            int k = 0;
-            while (e == hipSuccess) {
-                const int64_t it = next.fetch_add(1);
-                if (it >= n_pieces) break;
-                const int64_t r = it / pieces_per_row, o = (it % pieces_per_row) * piece, b = std::min<int64_t>(piece, row_bytes - o);
-                void* stg = c->up_stage[(size_t)(2 * t + k)].p;
-                if (busy[k]) { e = hipEventSynchronize(ev[k]); if (e != hipSuccess) break; }      // its previous copy has left the piece
-                memcpy(stg, rows[r] + o, (size_t)b);
-                e = hipMemcpyAsync(dst + r * dst_pitch + o, stg, (size_t)b, hipMemcpyHostToDevice, st);
-                if (e == hipSuccess) e = hipEventRecord(ev[k], st);
-                busy[k] = true;
-                k ^= 1;
-            }
-            if (st) { const hipError_t e2 = hipStreamSynchronize(st); if (e == hipSuccess) e = e2; (void)hipStreamDestroy(st); }
-            for (auto& x : ev) if (x) (void)hipEventDestroy(x);
-            terr[(size_t)t] = e;
-        };
-        std::vector<std::thread> th;
-        for (int t = 0; t < T; t++) th.emplace_back(worker, t);
-        for (auto& x : th) x.join();
-        for (int t = 0; t < T; t++) HIP_TRY(terr[(size_t)t]);
+        const std::vector<hipError_t> terr = run_upload(c, u, dst, dst_pitch, rows, n_rows, row_bytes, [](int64_t) {});
+        for (int t = 0; t < u.T; t++) HIP_TRY(terr[(size_t)t]);
     }
     if (profiling()) fprintf(stderr, "[wgbsseg] %s to the device: %.1f ms, %.1f GB/s (%d upload threads)\n", what, (wall_s() - t0) * 1e3,
-                             (double)row_bytes * n_rows / (wall_s() - t0) * 1e-9, T);
+                             (double)row_bytes * n_rows / (wall_s() - t0) * 1e-9, u.T);
+    return WGBSSEG_OK;
+}
+
+// ready_sites: the sites that are resident for EVERY row, counted from the front (what the streaming segmenter waits on)
+int upload_rows_streaming(wgbsseg_ctx* c, uint8_t* dst, int64_t dst_pitch, const uint8_t* const* rows, int64_t n_rows, int64_t row_bytes,
+                          std::atomic<int64_t>& ready_sites, std::string& msg)
+{
+    const double t0 = wall_s();
+    const UploadPlan u = plan_upload(true, n_rows, row_bytes);
+    std::vector<std::atomic<int>> rows_done((size_t)u.ppr);
+    for (auto& x : rows_done) x.store(0);
+    std::atomic<int64_t> pieces_done(0);
+    std::mutex mu;
+    auto complete = [&](int64_t task) {                          // task = p * n_rows + r: row r's piece p is on the device
+        const int64_t p = task / n_rows;
+        if (rows_done[(size_t)p].fetch_add(1) + 1 == (int)n_rows) {
+            std::lock_guard<std::mutex> lk(mu);
+            int64_t d = pieces_done.load();
+            while (d < u.ppr && rows_done[(size_t)d].load() == (int)n_rows) d++;
+            pieces_done.store(d);
+            ready_sites.store(std::min<int64_t>(d * u.piece, row_bytes) / 2);
+        }
+    };
+    const std::vector<hipError_t> terr = run_upload(c, u, dst, dst_pitch, rows, n_rows, row_bytes, complete);
+    for (int t = 0; t < u.T; t++)
+        if (terr[(size_t)t] != hipSuccess) { msg = std::string("HIP error during the upload: ") + hipGetErrorString(terr[(size_t)t]); return WGBSSEG_E_HIP; }
+    ready_sites.store(row_bytes / 2);
+    if (profiling()) fprintf(stderr, "[wgbsseg] betas to the device (streaming): %.1f ms, %.1f GB/s (%d upload threads x %d pieces of %lld KB%s%s%s)\n", (wall_s() - t0) * 1e3,
+                             (double)row_bytes * n_rows / (wall_s() - t0) * 1e-9, u.T, u.depth, (long long)(u.piece >> 10), c->near_cpus.valid ? ", on the device's CPUs" : "",
+                             u.fill.populate ? ", pages mapped per piece" : "", u.fill.nt ? ", non-temporal fill" : "");
     return WGBSSEG_OK;
 }
 
@@ -275,7 +373,6 @@ int wgbsseg_device_count(void)
 
 }  // extern "C"
 namespace {
-int create_ctx(int device, bool scan_low_priority, wgbsseg_ctx** out, char* err, size_t errlen);
 std::atomic<int> g_live_ctx[64];      // contexts alive per device (gated stages want theirs alone on its device)
 
 // what every context and engine asks of its device: it exists and is a gfx950 (it is made the current device)
@@ -297,16 +394,7 @@ int check_device(int device, char* err, size_t errlen)
     }
     return WGBSSEG_OK;
 }
-}
-extern "C" {
 
-int wgbsseg_create(int device, wgbsseg_ctx** out, char* err, size_t errlen)
-{
-    return create_ctx(device, true, out, err, errlen);
-}
-
-}  // extern "C"
-namespace {
 // scan_low_priority: the scan stream below the scoring streams (right where k_validate competes with the kernels of its OWN batch only; the shares of a group that
 // double up on a device get it at the scoring streams' priority: wgbsseg_group_create)
 int create_ctx(int device, bool scan_low_priority, wgbsseg_ctx** out, char* err, size_t errlen)
@@ -316,98 +404,85 @@ int create_ctx(int device, bool scan_low_priority, wgbsseg_ctx** out, char* err,
     const int rc = check_device(device, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     HIP_TRY(set_kernel_attributes());        // per device, checked: k_dp / k_cost ask for more than 64 KB of dynamic LDS
-    wgbsseg_ctx* c = new (std::nothrow) wgbsseg_ctx();
+    std::unique_ptr<wgbsseg_ctx> c(new (std::nothrow) wgbsseg_ctx());      // (a failing call below frees what has been made)
     if (!c) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
     c->device = device;
     (void)device_local_cpus(device, &c->near_cpus);
-    HIP_TRY(hipStreamCreateWithFlags(&c->sA, hipStreamNonBlocking));
+    HIP_TRY(c->sA.create());
     {   // the recurrence stream outranks the scoring stream: its 483 latency-bound workgroups should never queue behind
         // the hundreds of thousands of throughput-bound scoring tiles
         int lo_p = 0, hi_p = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);
-        HIP_TRY(hipStreamCreateWithPriority(&c->sB, hipStreamNonBlocking, hi_p));
+        HIP_TRY(c->sB.create(hi_p));
         // ... and the scan stream ranks below it: k_validate starts with the batch, beside the windows pass, and must not take the wavefront
         // slots of the kernels that are on the way to the first scoring tile (measured, hg19 x 32: scoring begins 0.36 ms into the batch
         // instead of 0.46, profiles/r06_front_ab.txt)
-        HIP_TRY(scan_low_priority ? hipStreamCreateWithPriority(&c->sC, hipStreamNonBlocking, lo_p) : hipStreamCreateWithFlags(&c->sC, hipStreamNonBlocking));
+        HIP_TRY(scan_low_priority ? c->sC.create(lo_p) : c->sC.create());
     }
-    HIP_TRY(hipStreamCreateWithFlags(&c->sA2, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&c->evD, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&c->evS, hipEventDisableTiming));
-    for (auto& v : c->ev) HIP_TRY(hipEventCreate(&v));
-    const char* b = getenv("WGBSSEG_COST_BUDGET_MB");
-    c->cost_budget_bytes = (b && atoll(b) > 0 ? atoll(b) : 6144LL) << 20;
-    c->force_stages = env_int("WGBSSEG_FORCE_STAGES", 0);
-    { const char* e = getenv("WGBSSEG_STAGE_GATE"); if (e) c->stage_gate = std::max(0, atoi(e)); }
-    { const char* e = getenv("WGBSSEG_STAGE_GATE_SHARED"); c->stage_gate_shared = e && atoi(e) != 0; }
-    { const char* e = getenv("WGBSSEG_STAGE_GATE_WIDE_EVALS"); if (e) c->stage_gate_wide_evals = atof(e); }
-    { const char* e = getenv("WGBSSEG_STAGE_MIN_EVALS"); if (e) c->stage_min_evals_per_step = atof(e); }
-    { const char* e = getenv("WGBSSEG_LAST_STAGE_PCT"); if (e) c->last_stage_pct = std::min(800, std::max(5, atoi(e))); }      // (A/B, tests; default: chosen per job)
-    { const char* e = getenv("WGBSSEG_DP_MODE"); c->force_dp_mode = e ? std::min(2, std::max(0, atoi(e))) : 0; }
-    c->force_ns = env_int("WGBSSEG_NS", 0);
-    c->force_ti = env_int("WGBSSEG_TI", 0);
-    c->bs_general = env_int("WGBSSEG_BLOCK_SUMS_GENERAL", 0) != 0;
-    c->divs_enabled = env_int("WGBSSEG_DIV_SHORT", 1) != 0;
-    { const int sp = env_int("WGBSSEG_SCAN_PIECE_SITES", 0); if (sp >= 1024) c->scan_piece_sites = (int64_t)(sp & ~1023); }
-    const int wm = std::max(0, std::min(WG_MEDIUM_WMAX, env_int("WGBSSEG_MEDIUM_WMAX", WG_MEDIUM_WMAX)));
+    HIP_TRY(c->sA2.create());
+    HIP_TRY(c->evD.create(false));
+    HIP_TRY(c->evS.create(false));
+    for (auto& v : c->ev) HIP_TRY(v.create());
+    const long long budget_mb = env_int("WGBSSEG_COST_BUDGET_MB", 0);
+    c->cost_budget_bytes = (budget_mb > 0 ? budget_mb : 6144LL) << 20;
+    c->force_stages = (int)env_int("WGBSSEG_FORCE_STAGES", 0);
+    c->stage_gate = (int)env_int("WGBSSEG_STAGE_GATE", c->stage_gate, 0);
+    c->stage_gate_shared = env_flag("WGBSSEG_STAGE_GATE_SHARED", false);
+    c->stage_gate_wide_evals = env_double("WGBSSEG_STAGE_GATE_WIDE_EVALS", c->stage_gate_wide_evals);
+    c->stage_min_evals_per_step = env_double("WGBSSEG_STAGE_MIN_EVALS", c->stage_min_evals_per_step);
+    if (env_int("WGBSSEG_LAST_STAGE_PCT", -1) != -1) c->last_stage_pct = (int)env_int("WGBSSEG_LAST_STAGE_PCT", -1, 5, 800);      // (unset: chosen per job)
+    c->force_dp_mode = (int)env_int("WGBSSEG_DP_MODE", 0, 0, 2);
+    c->force_ns = (int)env_int("WGBSSEG_NS", 0);
+    c->force_ti = (int)env_int("WGBSSEG_TI", 0);
+    c->bs_general = env_flag("WGBSSEG_BLOCK_SUMS_GENERAL", false);
+    c->divs_enabled = env_flag("WGBSSEG_DIV_SHORT", true);
+    { const long long sp = env_int("WGBSSEG_SCAN_PIECE_SITES", 0); if (sp >= 1024) c->scan_piece_sites = sp & ~1023LL; }
+    const int wm = (int)env_int("WGBSSEG_MEDIUM_WMAX", WG_MEDIUM_WMAX, 0, WG_MEDIUM_WMAX);
     c->medium_wmax = wm > WG_NARROW_WMAX ? wm : 0;
-    c->dp_wlean = env_int("WGBSSEG_DP_WLEAN", 1) != 0;
-    c->early = env_int("WGBSSEG_NO_EARLY", 0) == 0;
-    c->speculate = env_int("WGBSSEG_NO_SPECULATION", 0) == 0;
+    c->dp_wlean = env_flag("WGBSSEG_DP_WLEAN", true);
+    c->early = !env_flag("WGBSSEG_NO_EARLY", false);
+    c->speculate = !env_flag("WGBSSEG_NO_SPECULATION", false);
     c->batch_marks = env_int("WGBSSEG_PROFILE", 0) >= 2;
     g_live_ctx[device & 63].fetch_add(1, std::memory_order_relaxed);
     c->counted_live = true;
-    *out = c;
+    *out = c.release();
     return WGBSSEG_OK;
 }
 }  // namespace
 extern "C" {
+
+int wgbsseg_create(int device, wgbsseg_ctx** out, char* err, size_t errlen) { return create_ctx(device, true, out, err, errlen); }
 
 void wgbsseg_destroy(wgbsseg_ctx* c)
 {
     if (!c) return;
     if (c->counted_live) g_live_ctx[c->device & 63].fetch_sub(1, std::memory_order_relaxed);
     const double t0 = wall_s();
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    DevBuf* all[] = {&c->betas_own, &c->loci_own, &c->chunks, &c->wtile, &c->carry, &c->W16, &c->cum32, &c->back16, &c->chunk_pairs, &c->tile_tot, &c->tile_base, &c->tile_chunk,
-                     &c->status, &c->plan_cbase, &c->plan_cum0, &c->plan_tbase, &c->plan_pairs, &c->plan_tiles, &c->plan_cnt, &c->tiles[0], &c->tiles[1], &c->tiles[2], &c->umax16,
-                     &c->cost[0], &c->cost[1], &c->cost[2], &c->stage_ctr, &c->dpstate, &c->tmp_borders, &c->nb, &c->boff, &c->out_borders[0], &c->out_borders[1], &c->edges,
-                     &c->dbg_a, &c->dbg_b, &c->dbg_c, &c->lookup, &c->scan_pieces, &c->divcheck, &c->plan_sb, &c->bs_desc};
-    for (auto* b : all) b->release();
-    for (auto& pb : c->pinned) pb.release();
-    for (auto& pb : c->up_stage) pb.release();
-    c->h_status.release();
-    c->h_out.release();
-    c->h_job.release();
-    c->h_pieces.release();
-    c->h_sb.release();
-    for (auto& v : c->ev) if (v) (void)hipEventDestroy(v);
-    for (auto* vec : {&c->ev_cost0, &c->ev_cost1, &c->ev_dp0, &c->ev_dp1, &c->ev_fork, &c->ev_join}) for (auto v : *vec) (void)hipEventDestroy(v);
-    if (c->sA) (void)hipStreamDestroy(c->sA);
-    if (c->sB) (void)hipStreamDestroy(c->sB);
-    if (c->sC) (void)hipStreamDestroy(c->sC);
-    if (c->sA2) (void)hipStreamDestroy(c->sA2);
-    if (c->evD) (void)hipEventDestroy(c->evD);
-    if (c->evS) (void)hipEventDestroy(c->evS);
     delete c;
     if (profiling()) fprintf(stderr, "[wgbsseg] destroy: %.1f ms\n", (wall_s() - t0) * 1e3);
+}
+
+// The context's own device rows for n_samples x n_sites count pairs of `elem` bytes: they exist, the context points at them (the device is current),
+// and what the last call left behind is no longer valid.  The bytes are still to come.
+static hipError_t own_rows(wgbsseg_ctx* c, int64_t n_samples, int64_t n_sites, int elem)
+{
+    const int64_t pitch = round_up(2 * elem * n_sites, 256) + 256;      // slack: vector loads may run past the last site
+    const hipError_t e = c->betas_own.ensure((size_t)pitch * (size_t)n_samples);
+    if (e != hipSuccess) return e;
+    c->betas = c->betas_own.as<uint8_t>();
+    c->pitch = pitch; c->n_total = n_sites; c->n_samples = (int32_t)n_samples; c->elem = elem;
+    c->last_valid = false;
+    return hipSuccess;
 }
 
 static int set_rows_host(wgbsseg_ctx* c, const uint8_t* const* samples, int64_t n_samples, int64_t n_sites, int elem, char* err, size_t errlen)
 {
     if (!c || !samples || n_samples < 1 || n_sites < 1) { set_err(err, errlen, "bad arguments to set_betas_host"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(c->device));
-    const int64_t pitch = round_up(2 * elem * n_sites, 256) + 256;      // slack: vector loads may run past the last site
-    HIP_TRY(c->betas_own.ensure((size_t)pitch * (size_t)n_samples));
     for (int64_t s = 0; s < n_samples; s++)
         if (!samples[s]) { set_err(err, errlen, "samples[%lld] is NULL", (long long)s); return WGBSSEG_E_ARG; }
-    const int rc = upload_rows(c, c->betas_own.as<uint8_t>(), pitch, samples, n_samples, 2 * elem * n_sites, "betas", err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    c->betas = c->betas_own.as<uint8_t>();
-    c->pitch = pitch; c->n_total = n_sites; c->n_samples = (int32_t)n_samples; c->elem = elem;
-    c->last_valid = false;
-    return WGBSSEG_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(own_rows(c, n_samples, n_sites, elem));
+    return upload_rows(c, c->betas_own.as<uint8_t>(), c->pitch, samples, n_samples, 2 * elem * n_sites, "betas", err, errlen);
 }
 
 int wgbsseg_set_betas_host(wgbsseg_ctx* c, const uint8_t* const* samples, int64_t n_samples, int64_t n_sites,
@@ -693,9 +768,9 @@ hipError_t set_kernel_attributes()
     return e;
 }
 
-void grow_events(std::vector<hipEvent_t>& v, size_t n)
+void grow_events(std::vector<Event>& v, size_t n)
 {
-    while (v.size() < n) { hipEvent_t e; (void)hipEventCreate(&e); v.push_back(e); }
+    while (v.size() < n) { v.emplace_back(); (void)v.back().create(); }
 }
 
 typedef std::function<int32_t*(int64_t)> BorderAlloc;       // total border count -> destination (NULL: too small)
@@ -728,14 +803,11 @@ int plain_segment_chunk(wgbsseg_ctx* c, int64_t start0, int32_t n, const wgbsseg
     // bytes (28.8 GB for max_cpg >= chunk = 60,000 — within an MI355X's 288 GB; E_NOMEM below when the device cannot give it).
     // WGBSSEG_PLAIN_RING_ROWS caps the rows (tests: the banded ring with R < n on chunks small enough for the suite).
     int64_t budget_rows = std::max<int64_t>((int64_t)W + 255, (1LL << 30) / ((int64_t)W * 8));
-    if (const char* e = getenv("WGBSSEG_PLAIN_RING_ROWS")) {
-        const long long v = atoll(e);
-        if (v > 0) budget_rows = std::max<int64_t>((int64_t)W, (int64_t)v);     // R >= W keeps the band >= 1 row
-    }
+    const long long cap_rows = env_int("WGBSSEG_PLAIN_RING_ROWS", 0);      // (read per batch: a test sets it on a live context)
+    if (cap_rows > 0) budget_rows = std::max<int64_t>((int64_t)W, (int64_t)cap_rows);     // R >= W keeps the band >= 1 row
     const int32_t R = (int32_t)std::min<int64_t>(n, budget_rows);
     const int32_t band = R >= n ? n : R - (W - 1);
-    DevBuf buf, M, T, bad;
-    struct Free { DevBuf& a; DevBuf& b; DevBuf& c; DevBuf& d; ~Free() { a.release(); b.release(); c.release(); d.release(); } } fr{buf, M, T, bad};
+    DevBuf buf, M, T, bad;      // (this call's alone: they go when it returns)
     if (buf.ensure((size_t)W * (size_t)R * 8) != hipSuccess || M.ensure((size_t)(n + 1) * 8) != hipSuccess || T.ensure((size_t)(n + 1) * 4) != hipSuccess ||
         bad.ensure(8) != hipSuccess) {
         (void)hipGetLastError();
@@ -1155,7 +1227,6 @@ int Batch::disorder_exit(char* err, size_t errlen)
     // the plain path (csrc/plain_dp.h: the reference's loops as written), the rest of the batch runs again without them, and the border
     // lists are put back in the caller's order.
     DevBuf flags;
-    struct Free { DevBuf& a; ~Free() { a.release(); } } fr{flags};
     HIP_TRY(flags.ensure((size_t)n_chunks * 4));
     HIP_TRY(hipMemsetAsync(flags.p, 0, (size_t)n_chunks * 4, c->sA));
     hipLaunchKernelGGL(k_find_disorder, dim3((unsigned)n_chunks), dim3(WG_BLOCK), 0, c->sA, job.v, flags.as<uint32_t>());
@@ -1315,7 +1386,7 @@ int Batch::stages(char* err, size_t errlen)
     sv.sb = c->plan_sb.as<int32_t>();
     DpArgs da = {p.ringN, {c->dp_wlean ? 0 : 1, 0, 0}};       // pad[0] = 1: the narrow batches of a wide job on the generic step
 #ifdef WGBSSEG_DP_TIMING
-    if (const char* e = getenv("WGBSSEG_DP_DEBUG")) da.pad[1] = atoi(e);      // timing builds only: see k_dp (results are WRONG in these modes)
+    da.pad[1] = (int)env_int("WGBSSEG_DP_DEBUG", 0);      // timing builds only: see k_dp (results are WRONG in these modes)
 #endif
     c->last_dp_chunks = nC; c->last_dp_stride = p.state_stride;
     // LDS of k_dp: two arranged batches (64 steps x 64 lanes, or 32 steps x 64 lanes x {A, B}) + M ring + fetched ring entries + flags + ring of windows / row offsets
@@ -1742,170 +1813,6 @@ void parallel_for(int64_t n, int max_threads, F f)
 
 }  // namespace
 
-namespace {
-
-// The CPUs next to a device: /sys/bus/pci/devices/<bus id>/local_cpulist (e.g. "0-63,128-191"), cut to the CPUs this process may use.
-// An upload thread that runs on the OTHER socket of a two-socket host fills page-locked pieces over there and the DMA then crosses the
-// socket link: measured on an MI355X box (round 5, x200 = 11.3 GB): the same upload at 9 .. 35 GB/s from run to run with free-running
-// threads.  false: unknown (no sysfs, every CPU listed, WGBSSEG_UPLOAD_PIN=0) — the threads then run where the scheduler puts them.
-// The CPUs next to a device (/sys/bus/pci/devices/<bus id>/local_cpulist) that this process may run on, as an affinity mask of up to WG_MAX_CPUS
-// CPUs (a fixed cpu_set_t stops at 1024 and sched_getaffinity then FAILS on a larger host: ADVICE r05).  Worked out once per context (create).
-bool device_local_cpus(int device, NearCpus* out)
-{
-    out->valid = false;
-    { const char* e = getenv("WGBSSEG_UPLOAD_PIN"); if (e && atoi(e) == 0) return false; }
-    char bus[64] = {0};
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof bus, device) != hipSuccess) { (void)hipGetLastError(); return false; }
-    for (char* q = bus; *q; q++) if (*q >= 'A' && *q <= 'F') *q = (char)(*q - 'A' + 'a');       // sysfs names are lower case
-    char path[160];
-    snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/local_cpulist", bus);
-    FILE* f = fopen(path, "r");
-    if (!f) return false;
-    char line[8192] = {0};
-    const bool got = fgets(line, (int)sizeof line, f) != nullptr;
-    fclose(f);
-    if (!got) return false;
-    const size_t bytes = CPU_ALLOC_SIZE(WG_MAX_CPUS);
-    std::vector<unsigned long> allowed(bytes / sizeof(unsigned long), 0ul);
-    out->bits.assign(bytes / sizeof(unsigned long), 0ul);
-    cpu_set_t* A = reinterpret_cast<cpu_set_t*>(allowed.data());
-    cpu_set_t* L = reinterpret_cast<cpu_set_t*>(out->bits.data());
-    if (sched_getaffinity(0, bytes, A) != 0) return false;
-    int n_local = 0;
-    for (const char* q = line; *q;) {
-        while (*q == ',' || *q == ' ' || *q == '\n') q++;
-        if (*q < '0' || *q > '9') break;
-        char* end = nullptr;
-        long a = strtol(q, &end, 10), b = a;
-        if (*end == '-') b = strtol(end + 1, &end, 10);
-        for (long x = a; x <= b && x < WG_MAX_CPUS; x++) if (CPU_ISSET_S((int)x, bytes, A)) { CPU_SET_S((int)x, bytes, L); n_local++; }
-        q = end;
-    }
-    if (n_local == 0 || n_local == CPU_COUNT_S(bytes, A)) return false;      // nothing to choose from
-    out->valid = true;
-    return true;
-}
-inline void pin_to(const NearCpus& n)
-{
-    if (n.valid) (void)pthread_setaffinity_np(pthread_self(), n.bits.size() * sizeof(unsigned long), reinterpret_cast<const cpu_set_t*>(n.bits.data()));
-}
-// Page-cached file bytes -> a page-locked staging piece (round 6, profiles/r06_upload_ab.txt):
-//   * the piece's pages are mapped in ONE call (madvise MADV_POPULATE_READ, Linux >= 5.14) instead of a minor fault per 4 KB page as the copy touches them;
-//   * non-temporal stores: the staging piece is written once and read by the DMA engine — no read-for-ownership, no cache pollution.
-// WGBSSEG_UPLOAD_POPULATE=0 / WGBSSEG_UPLOAD_NT=0 switch either off (A/B).  x200 (11.3 GB) end to end on one box: 0.38-0.45 s -> 0.32 s with both and
-// 8 x 2 MB pieces; x32 0.107-0.114 -> 0.098-0.110.  The rate of ONE setting still swings between 30 and 47 GB/s from run to run on the same box.
-struct FillMode { bool populate = true, nt = true; };
-inline FillMode fill_mode()
-{
-    FillMode m;
-    { const char* e = getenv("WGBSSEG_UPLOAD_POPULATE"); if (e) m.populate = atoi(e) != 0; }
-    { const char* e = getenv("WGBSSEG_UPLOAD_NT"); if (e) m.nt = atoi(e) != 0; }
-    return m;
-}
-inline void fill_piece(void* dst, const uint8_t* src, size_t n, const FillMode& m)
-{
-#ifdef MADV_POPULATE_READ
-    if (m.populate) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(src) & ~(uintptr_t)4095, b = (reinterpret_cast<uintptr_t>(src) + n + 4095) & ~(uintptr_t)4095;
-        (void)madvise(reinterpret_cast<void*>(a), b - a, MADV_POPULATE_READ);      // (an error — an old kernel, not a mapping — just leaves the faults to the copy)
-    }
-#endif
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-    if (m.nt && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-        __m128i* d = reinterpret_cast<__m128i*>(dst);
-        const __m128i* s = reinterpret_cast<const __m128i*>(src);
-        size_t v = n >> 6;
-        for (; v > 0; v--, s += 4, d += 4) {
-            const __m128i x0 = _mm_loadu_si128(s), x1 = _mm_loadu_si128(s + 1), x2 = _mm_loadu_si128(s + 2), x3 = _mm_loadu_si128(s + 3);
-            _mm_stream_si128(d, x0); _mm_stream_si128(d + 1, x1); _mm_stream_si128(d + 2, x2); _mm_stream_si128(d + 3, x3);
-        }
-        _mm_sfence();
-        const size_t done = n & ~(size_t)63;
-        if (n > done) memcpy(static_cast<char*>(dst) + done, src + done, n - done);
-        return;
-    }
-#endif
-    memcpy(dst, src, n);
-}
-
-int upload_rows_streaming(wgbsseg_ctx* c, uint8_t* dst, int64_t dst_pitch, const uint8_t* const* rows, int64_t n_rows, int64_t row_bytes,
-                          std::atomic<int64_t>& ready_sites, std::string& msg)
-{
-    const double t0 = wall_s();
-    // (measured, free-running threads: 4 threads x 1 MB 33.5 GB/s, x 2 MB 26-29, 8-16 threads 17-30: profiles/r02_upload_sweep.txt.  Round 5, threads on the
-    // device's CPUs: 8 threads x 4 MB 37-42 GB/s on 11.3 GB (x200: 0.35-0.38 s end to end against 0.43-0.50 with 4 x 1 MB); x32's 1.8 GB the same either
-    // way: profiles/r05_upload_pinned_ab.txt.  Large cohorts take the wide form.  Round 6: 8 x 2 MB with the pieces' pages mapped per call and a non-temporal
-    // fill: x200 0.32 s end to end on both runs of the A/B against 0.33-0.45 for 8 x 4 MB, profiles/r06_upload_ab.txt.)
-    const bool big = row_bytes * n_rows >= (4LL << 30);
-    int64_t piece = big ? (2 << 20) : (1 << 20);
-    { const char* e = getenv("WGBSSEG_UPLOAD_PIECE_KB"); if (e && atoi(e) >= 64) piece = (int64_t)atoi(e) << 10; }
-    const int64_t ppr = (row_bytes + piece - 1) / piece, n_tasks = ppr * n_rows;
-    int T = big ? 8 : 4;
-    { const char* e = getenv("WGBSSEG_UPLOAD_THREADS"); if (e && atoi(e) > 0) T = atoi(e); }
-    T = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(T, 64), n_tasks));
-    std::vector<std::atomic<int>> rows_done((size_t)ppr);
-    for (auto& x : rows_done) x.store(0);
-    std::atomic<int64_t> next(0), pieces_done(0);
-    std::mutex mu;
-    std::vector<hipError_t> terr((size_t)T, hipSuccess);
-    const bool pin = c->near_cpus.valid;                         // upload threads (and the pieces they allocate and fill) on the device's socket
-    auto complete = [&](int64_t task) {                          // task = p * n_rows + r: row r's piece p is on the device
-        const int64_t p = task / n_rows;
-        if (rows_done[(size_t)p].fetch_add(1) + 1 == (int)n_rows) {
-            std::lock_guard<std::mutex> lk(mu);
-            int64_t d = pieces_done.load();
-            while (d < ppr && rows_done[(size_t)d].load() == (int)n_rows) d++;
-            pieces_done.store(d);
-            ready_sites.store(std::min<int64_t>(d * piece, row_bytes) / 2);
-        }
-    };
-    const FillMode fm = fill_mode();
-    int depth = 2;                                               // staging pieces (copies in flight) per upload thread
-    { const char* e = getenv("WGBSSEG_UPLOAD_DEPTH"); if (e && atoi(e) >= 2 && atoi(e) <= 8) depth = atoi(e); }
-    auto worker = [&](int t) {
-        pin_to(c->near_cpus);
-        hipError_t e = hipSetDevice(c->device);
-        hipStream_t st = nullptr;
-        hipEvent_t ev[8] = {};
-        void* stg[8] = {};
-        int64_t task_of[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        for (int k = 0; k < depth && e == hipSuccess; k++) e = hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-        // (allocated — and so first touched — by the thread that fills them, which runs on the device's CPUs: the pieces sit on that socket)
-        for (int k = 0; k < depth && e == hipSuccess; k++) e = hipHostMalloc(&stg[k], (size_t)piece, hipHostMallocDefault);
-        int k = 0;
-        while (e == hipSuccess) {
-            const int64_t it = next.fetch_add(1);
-            if (it >= n_tasks) break;
-            const int64_t p = it / n_rows, r = it % n_rows, o = p * piece, b = std::min<int64_t>(piece, row_bytes - o);
-            if (task_of[k] >= 0) { e = hipEventSynchronize(ev[k]); if (e != hipSuccess) break; complete(task_of[k]); task_of[k] = -1; }
-            fill_piece(stg[k], rows[r] + o, (size_t)b, fm);
-            e = hipMemcpyAsync(dst + r * dst_pitch + o, stg[k], (size_t)b, hipMemcpyHostToDevice, st);
-            if (e == hipSuccess) e = hipEventRecord(ev[k], st);
-            task_of[k] = it;
-            k = (k + 1) % depth;
-        }
-        for (int q = 0; q < depth && e == hipSuccess; q++, k = (k + 1) % depth)
-            if (task_of[k] >= 0) { e = hipEventSynchronize(ev[k]); if (e == hipSuccess) complete(task_of[k]); task_of[k] = -1; }
-        if (st) (void)hipStreamDestroy(st);
-        for (auto& x : ev) if (x) (void)hipEventDestroy(x);
-        for (auto& x : stg) if (x) (void)hipHostFree(x);
-        terr[(size_t)t] = e;
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; t++) th.emplace_back(worker, t);
-    for (auto& x : th) x.join();
-    for (int t = 0; t < T; t++)
-        if (terr[(size_t)t] != hipSuccess) { msg = std::string("HIP error during the upload: ") + hipGetErrorString(terr[(size_t)t]); return WGBSSEG_E_HIP; }
-    ready_sites.store(row_bytes / 2);
-    if (profiling()) fprintf(stderr, "[wgbsseg] betas to the device (streaming): %.1f ms, %.1f GB/s (%d upload threads x %d pieces of %lld KB%s%s%s)\n", (wall_s() - t0) * 1e3,
-                             (double)row_bytes * n_rows / (wall_s() - t0) * 1e-9, T, depth, (long long)(piece >> 10), pin ? ", on the device's CPUs" : "",
-                             fm.populate ? ", pages mapped per piece" : "", fm.nt ? ", non-temporal fill" : "");
-    return WGBSSEG_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int wgbsseg_group_create(const int32_t* devices, int32_t n_shares, wgbsseg_group** out, char* err, size_t errlen)
@@ -2106,12 +2013,8 @@ int wgbsseg_group_load_host_async(wgbsseg_group* g, const uint8_t* const* sample
         wgbsseg_ctx* c = g->shares[(size_t)d];
         hipError_t e = hipSetDevice(c->device);
         if (e != hipSuccess) return fail(e, "hipSetDevice");
-        const int64_t n = hi - lo, pitch = round_up(2 * n, 256) + 256;
-        e = c->betas_own.ensure((size_t)pitch * (size_t)n_samples);
+        e = own_rows(c, n_samples, hi - lo, 1);
         if (e != hipSuccess) return fail(e, "device rows of a share");
-        c->betas = c->betas_own.as<uint8_t>();
-        c->pitch = pitch; c->n_total = n; c->n_samples = (int32_t)n_samples; c->elem = 1;
-        c->last_valid = false;
     }
     std::vector<const uint8_t*> base(samples, samples + n_samples);
     for (int d = 0; d < G; d++) {
@@ -2719,40 +2622,38 @@ int wgbsseg_convert_regions(wgbsseg_ctx* c, const int64_t* chrom_lo, const int64
 // The pat-text feed of an engine (wgbsseg_patbeta / _homog / _bimodal): one device and stream; text chunks through two page-locked
 // staging buffers and two device buffers, so that the caller's decompression of chunk k+1 overlaps the copy and the kernels of
 // chunk k; the input offset of the next chunk; and the device time of the launches the engine brackets with span_begin / span_end.
+// Teardown: an engine's buffers — its own and the feed's — must not go while the stream may still use them.  Members go in reverse order of
+// declaration and an engine's `feed` comes first, so declaration order alone would free the engine's buffers before the feed had a say: every
+// engine's destructor calls drain() instead (explicit, one line each), and so does the feed's own for the buffers it holds itself.
 struct PatFeed {
     int device = 0;
-    hipStream_t st = nullptr;
+    Stream st;                                                    // (declared first: goes last)
     PinnedBuf stage[2];
     DevBuf text[2];
-    hipEvent_t ev[2] = {nullptr, nullptr};                        // after the work on slot k's text
+    Event ev[2];                                                  // after the work on slot k's text
     bool busy[2] = {false, false};
     int k = 0;                                                    // the slot of the next chunk
     unsigned long long fed = 0;                                   // bytes fed so far
     double span_ms = 0.0;                                         // the spans read so far
-    std::deque<std::pair<hipEvent_t, hipEvent_t>> spans;          // recorded, in stream order, not read yet
-    std::vector<hipEvent_t> spare;                                // the events of read spans, for the next ones
+    std::deque<std::pair<Event, Event>> spans;                    // recorded, in stream order, not read yet
+    std::vector<Event> spare;                                     // the events of read spans, for the next ones
 
     int open(int dev, char* err, size_t errlen)
     {
         const int rc = check_device(dev, err, errlen);
         if (rc != WGBSSEG_OK) return rc;
         device = dev;
-        HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        for (auto& e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIP_TRY(st.create());
+        for (auto& e : ev) HIP_TRY(e.create(false));
         return WGBSSEG_OK;
     }
-    void close()                                                  // (the engine frees its own buffers after this)
+    void drain()                                                  // the stream has passed everything queued on it, the spans are read: buffers may go
     {
         (void)hipSetDevice(device);
         if (st) (void)hipStreamSynchronize(st);
         collect();
-        for (auto& b : text) b.release();
-        for (auto& s : stage) s.release();
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-        for (auto& s : spans) { (void)hipEventDestroy(s.first); (void)hipEventDestroy(s.second); }
-        for (hipEvent_t e : spare) (void)hipEventDestroy(e);
-        if (st) (void)hipStreamDestroy(st);
     }
+    ~PatFeed() { drain(); }
     // the checks of a feed call: -1 when refused (err set), 0 for an empty chunk, else the chunk's number of tiles
     static int64_t tiles(const char* name, const void* engine, const char* text, int64_t n_bytes, char* err, size_t errlen)
     {
@@ -2785,14 +2686,14 @@ struct PatFeed {
     }
     hipError_t span_begin()
     {
-        hipEvent_t e[2] = {nullptr, nullptr};
+        Event e[2];
         for (auto& x : e) {
-            if (!spare.empty()) { x = spare.back(); spare.pop_back(); continue; }
-            const hipError_t r = hipEventCreate(&x);
-            if (r != hipSuccess) { if (e[0]) spare.push_back(e[0]); return r; }
+            if (!spare.empty()) { x = std::move(spare.back()); spare.pop_back(); continue; }
+            const hipError_t r = x.create();
+            if (r != hipSuccess) return r;
         }
-        spans.push_back({e[0], e[1]});
-        return hipEventRecord(e[0], st);
+        spans.emplace_back(std::move(e[0]), std::move(e[1]));
+        return hipEventRecord(spans.back().first, st);
     }
     hipError_t span_end() { return hipEventRecord(spans.back().second, st); }
     // adds the spans the stream has passed to span_ms (in order: the first one still running ends the walk)
@@ -2803,7 +2704,7 @@ struct PatFeed {
             const hipError_t e = hipEventElapsedTime(&ms, spans.front().first, spans.front().second);
             if (e == hipErrorNotReady) break;
             if (e == hipSuccess) span_ms += (double)ms;
-            spare.push_back(spans.front().first); spare.push_back(spans.front().second);
+            spare.push_back(std::move(spans.front().first)); spare.push_back(std::move(spans.front().second));
             spans.pop_front();
         }
     }
@@ -2832,21 +2733,17 @@ struct wgbsseg_patbeta {
     PatFeed feed;
     int64_t start = 1, end = 1;
     DevBuf meth, cov, outb, bad;
+    ~wgbsseg_patbeta() { feed.drain(); }
 };
 
 extern "C" {
-
-void wgbsseg_patbeta_destroy(wgbsseg_patbeta* p);
 
 int wgbsseg_patbeta_create(int device, int64_t start_cpg, int64_t end_cpg, wgbsseg_patbeta** out, char* err, size_t errlen)
 {
     if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
     *out = nullptr;
     if (start_cpg < 1 || end_cpg <= start_cpg || end_cpg - start_cpg > 0x7fffffff) { set_err(err, errlen, "patbeta: bad CpG range [%lld, %lld)", (long long)start_cpg, (long long)end_cpg); return WGBSSEG_E_ARG; }
-    // (the struct's members are plain handles: whatever has been created when a HIP call fails is released by the destroy
-    // function, which is what the owner calls on every early return)
-    struct Free { void operator()(wgbsseg_patbeta* q) const { wgbsseg_patbeta_destroy(q); } };
-    std::unique_ptr<wgbsseg_patbeta, Free> p(new (std::nothrow) wgbsseg_patbeta());
+    std::unique_ptr<wgbsseg_patbeta> p(new (std::nothrow) wgbsseg_patbeta());      // (a failing call below frees what has been made)
     if (!p) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
     const int rc = p->feed.open(device, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
@@ -2860,13 +2757,7 @@ int wgbsseg_patbeta_create(int device, int64_t start_cpg, int64_t end_cpg, wgbss
     return WGBSSEG_OK;
 }
 
-void wgbsseg_patbeta_destroy(wgbsseg_patbeta* p)
-{
-    if (!p) return;
-    p->feed.close();
-    for (DevBuf* b : {&p->meth, &p->cov, &p->outb, &p->bad}) b->release();
-    delete p;
-}
+void wgbsseg_patbeta_destroy(wgbsseg_patbeta* p) { delete p; }
 
 int wgbsseg_patbeta_feed(wgbsseg_patbeta* p, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
@@ -2920,11 +2811,10 @@ struct wgbsseg_homog {
     int n_bins = 0, min_cpgs = 0, inclusive = 0;
     DevBuf bstart, bend, bpmax, range, counts, bad, desc, prev;
     unsigned long long chunks = 0;
+    ~wgbsseg_homog() { feed.drain(); }
 };
 
 extern "C" {
-
-void wgbsseg_homog_destroy(wgbsseg_homog* h);
 
 int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, const float* range, int32_t n_bins,
                          int32_t min_cpgs, int32_t inclusive, wgbsseg_homog** out, char* err, size_t errlen)
@@ -2949,8 +2839,7 @@ int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* en
         run = std::max(run, (int32_t)b);
         pm[(size_t)j] = run;
     }
-    struct Free { void operator()(wgbsseg_homog* q) const { wgbsseg_homog_destroy(q); } };
-    std::unique_ptr<wgbsseg_homog, Free> h(new (std::nothrow) wgbsseg_homog());
+    std::unique_ptr<wgbsseg_homog> h(new (std::nothrow) wgbsseg_homog());      // (a failing call below frees what has been made)
     if (!h) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
     const int rc = h->feed.open(device, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
@@ -2974,13 +2863,7 @@ int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* en
     return WGBSSEG_OK;
 }
 
-void wgbsseg_homog_destroy(wgbsseg_homog* h)
-{
-    if (!h) return;
-    h->feed.close();
-    for (DevBuf* b : {&h->bstart, &h->bend, &h->bpmax, &h->range, &h->counts, &h->bad, &h->desc, &h->prev}) b->release();
-    delete h;
-}
+void wgbsseg_homog_destroy(wgbsseg_homog* h) { delete h; }
 
 int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
@@ -3034,19 +2917,14 @@ int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_tot
     char err[256];
     const size_t errlen = sizeof(err);
     const int64_t n = (int64_t)(max_total + 1) * (max_total + 2) / 2;
-    float* d_range = nullptr;
-    int8_t* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_range, sizeof(float) * (size_t)(n_bins + 1)));
-    if (hipMalloc(&d_out, (size_t)n) != hipSuccess) { (void)hipFree(d_range); return WGBSSEG_E_HIP; }
-    hipError_t e = hipMemcpy(d_range, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_homog_bins, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, 0, d_range, (int)n_bins, (int)max_total, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(d_range);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? WGBSSEG_OK : WGBSSEG_E_HIP;
+    DevBuf d_range, d_out;
+    HIP_TRY(d_range.ensure(sizeof(float) * (size_t)(n_bins + 1)));
+    HIP_TRY(d_out.ensure((size_t)n));
+    HIP_TRY(hipMemcpy(d_range.p, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_homog_bins, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, 0, d_range.as<float>(), (int)n_bins, (int)max_total, d_out.as<int8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n, hipMemcpyDeviceToHost));
+    return WGBSSEG_OK;
 }
 
 int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t count, uint64_t* out)
@@ -3054,21 +2932,17 @@ int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t co
     if (!a || !b || !out || count < 1 || count > (1ll << 28)) return WGBSSEG_E_ARG;
     char err[256];
     const size_t errlen = sizeof(err);
-    uint32_t* d_ab = nullptr;
-    uint64_t* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_ab, 2 * sizeof(uint32_t) * (size_t)count));
-    if (hipMalloc(&d_out, 6 * sizeof(uint64_t) * (size_t)count) != hipSuccess) { (void)hipFree(d_ab); return WGBSSEG_E_HIP; }
-    hipError_t e = hipMemcpy(d_ab, a, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_ab + count, b, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const unsigned blocks = (unsigned)std::min<int64_t>((count + WG_BLOCK - 1) / WG_BLOCK, 16384);
-        hipLaunchKernelGGL(k_bim_debug_terms, dim3(blocks), dim3(WG_BLOCK), 0, 0, d_ab, d_ab + count, count, d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, 6 * sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost);
-    (void)hipFree(d_ab);
-    (void)hipFree(d_out);
-    return e == hipSuccess ? WGBSSEG_OK : WGBSSEG_E_HIP;
+    DevBuf d_ab, d_out;
+    HIP_TRY(d_ab.ensure(2 * sizeof(uint32_t) * (size_t)count));
+    HIP_TRY(d_out.ensure(6 * sizeof(uint64_t) * (size_t)count));
+    uint32_t* const ab = d_ab.as<uint32_t>();
+    HIP_TRY(hipMemcpy(ab, a, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ab + count, b, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)std::min<int64_t>((count + WG_BLOCK - 1) / WG_BLOCK, 16384);
+    hipLaunchKernelGGL(k_bim_debug_terms, dim3(blocks), dim3(WG_BLOCK), 0, 0, ab, ab + count, count, d_out.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out.p, 6 * sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost));
+    return WGBSSEG_OK;
 }
 
 }  // extern "C"
@@ -3093,6 +2967,7 @@ struct wgbsseg_bimodal {
     PinnedBuf host_state, host_meta, host_off;
     bool stop = false;                            // an input error was seen: nothing more is computed
     wg_bim_state* hs() const { return reinterpret_cast<wg_bim_state*>(host_state.p); }
+    ~wgbsseg_bimodal() { feed.drain(); }
 };
 
 static int bim_sync_state(wgbsseg_bimodal* b, char* err, size_t errlen)
@@ -3123,9 +2998,7 @@ static int bim_reserve(wgbsseg_bimodal* b, size_t rows, size_t words, char* err,
             HIP_TRY(hipMemcpy(fresh.woff.p, old.woff.p, R * 8, hipMemcpyDeviceToDevice));
         }
         if (t == b->cur && W) HIP_TRY(hipMemcpy(fresh.words.p, old.words.p, W * 4, hipMemcpyDeviceToDevice));
-        for (DevBuf* d : {&old.start, &old.len, &old.cnt, &old.woff, &old.words}) d->release();
-        old = fresh;
-        fresh = wgbsseg_bimodal::Table();                       // (ownership moved: nothing to free twice)
+        old = std::move(fresh);                                 // (the old table's buffers go here)
     }
     b->cap_rows = nr; b->cap_words = nw;
     return WGBSSEG_OK;
@@ -3175,8 +3048,6 @@ static int bim_retire(wgbsseg_bimodal* b, int64_t p1, char* err, size_t errlen)
 
 extern "C" {
 
-void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b);
-
 int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, int32_t strict, int32_t min_len,
                            int32_t max_lds_cols, wgbsseg_bimodal** out, char* err, size_t errlen)
 {
@@ -3191,8 +3062,7 @@ int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* 
             return WGBSSEG_E_ARG;
         }
     }
-    struct Free { void operator()(wgbsseg_bimodal* q) const { wgbsseg_bimodal_destroy(q); } };
-    std::unique_ptr<wgbsseg_bimodal, Free> b(new (std::nothrow) wgbsseg_bimodal());
+    std::unique_ptr<wgbsseg_bimodal> b(new (std::nothrow) wgbsseg_bimodal());      // (a failing call below frees what has been made)
     if (!b) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
     const int rc = b->feed.open(device, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
@@ -3218,16 +3088,7 @@ int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* 
     return WGBSSEG_OK;
 }
 
-void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b)
-{
-    if (!b) return;
-    b->feed.close();
-    for (DevBuf* d : {&b->bs1, &b->bs2, &b->ids, &b->meta, &b->scr_off, &b->scratch, &b->res_f, &b->res_i, &b->state, &b->tile_cnt,
-                      &b->tile_base, &b->pos}) d->release();
-    for (auto& t : b->tab) for (DevBuf* d : {&t.start, &t.len, &t.cnt, &t.woff, &t.words}) d->release();
-    b->host_state.release(); b->host_meta.release(); b->host_off.release();
-    delete b;
-}
+void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b) { delete b; }
 
 int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
