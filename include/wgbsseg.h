@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 241            /* 0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 250            /* 0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -296,6 +296,30 @@ int wgbsseg_marker_stats(wgbsseg_ctx* ctx, const int32_t* tg, int32_t n_tg, cons
                          double* out, char* err, size_t errlen);
 /* HIP-event time of the kernel of the last wgbsseg_block_sums call (ms) */
 double wgbsseg_last_block_sums_ms(const wgbsseg_ctx* ctx);
+
+/*
+ * Per-sample statistics over the union of site ranges — what `wgbstools beta_cov` and `beta_stats` print per file
+ * (beta_cov.py:62-69, beta_stats.py:28-56), every field an integer:
+ *   n_sites               sum of (end0 - start0)
+ *   meth_sum, cov_sum     sums of the two columns
+ *   covered, covered_at   sites with cov > 0 / cov >= depth_at
+ *   orphans               sites with cov == 0 and meth > 0 (numpy's meth / cov is inf there)
+ *   max_cov               largest cov (0 over no sites)
+ *   ratio_hi:ratio_lo     the EXACT sum of the doubles fl(fl(meth / cov) * 100.0) over the sites with cov > 0, a 128-bit
+ *                         unsigned integer in units of 2^-62 (every such double is a multiple of 2^-62 for uint8 and uint16
+ *                         counts): independent of summation order, so of launch geometry and of how the ranges are cut
+ * Ranges are 0-based half-open [start0[i], end0[i]) inside [0, n_sites of the resident rows], ascending and disjoint
+ * (start0[i] >= end0[i - 1]); empty ranges are allowed and n_ranges == 0 gives all-zero results.  Works on uint8 rows
+ * (wgbsseg_set_betas_*) and uint16 rows (wgbsseg_set_lbetas_host).  A list that breaks the rules is refused with
+ * WGBSSEG_E_ARG and a message naming the first offending range.  out is a HOST buffer of n_samples entries.  The kernels'
+ * HIP-event time is what wgbsseg_last_block_sums_ms returns afterwards.
+ */
+typedef struct {
+    uint64_t n_sites, meth_sum, cov_sum, covered, covered_at, orphans, ratio_lo, ratio_hi;
+    uint32_t max_cov, reserved;
+} wgbsseg_sample_stat;
+int wgbsseg_sample_stats(wgbsseg_ctx* ctx, const int64_t* start0, const int64_t* end0, int64_t n_ranges, int32_t depth_at,
+                         wgbsseg_sample_stat* out, char* err, size_t errlen);
 
 /*
  * BED regions -> CpG index ranges: the join of `wgbstools convert -L` (convert.py:147-185 chr_thread, :133-145

@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 241          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 250          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -40,7 +40,7 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_homog_create', 'wgbsseg_homog_feed', 'wgbsseg_homog_finish', 'wgbsseg_homog_destroy', 'wgbsseg_homog_kernel_ms',
            'wgbsseg_debug_homog_bins',
            'wgbsseg_bimodal_create', 'wgbsseg_bimodal_feed', 'wgbsseg_bimodal_finish', 'wgbsseg_bimodal_destroy', 'wgbsseg_bimodal_kernel_ms',
-           'wgbsseg_debug_bimodal_terms']
+           'wgbsseg_debug_bimodal_terms', 'wgbsseg_sample_stats']
 
 
 class NativeLibraryError(RuntimeError):
@@ -58,6 +58,12 @@ class SegmentorError(RuntimeError):
 
 class Params(C.Structure):
     _fields_ = [('pseudo_count', C.c_float), ('max_cpg', C.c_uint32), ('max_bp', C.c_uint32)]
+
+
+# wgbsseg_sample_stat (include/wgbsseg.h): what Segmenter.sample_stats returns one of per resident sample
+SAMPLE_STAT_DTYPE = np.dtype([('n_sites', np.uint64), ('meth_sum', np.uint64), ('cov_sum', np.uint64), ('covered', np.uint64),
+                              ('covered_at', np.uint64), ('orphans', np.uint64), ('ratio_lo', np.uint64), ('ratio_hi', np.uint64),
+                              ('max_cov', np.uint32), ('reserved', np.uint32)])
 
 
 class Timings(C.Structure):
@@ -169,6 +175,8 @@ def load():
     L.wgbsseg_block_sums.argtypes = [vp, vp, vp, i64, i32, C.c_uint32, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_last_block_sums_ms.restype = C.c_double
     L.wgbsseg_last_block_sums_ms.argtypes = [vp]
+    L.wgbsseg_sample_stats.restype = i32
+    L.wgbsseg_sample_stats.argtypes = [vp, vp, vp, i64, i32, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_set_site_base.restype = i32
     L.wgbsseg_set_site_base.argtypes = [vp, i64]
     L.wgbsseg_stitch_regions.restype = i32
@@ -440,6 +448,16 @@ class Segmenter:
         bg = np.ascontiguousarray(bg, dtype=np.int32)
         out = np.empty((int(n_blocks), 8), dtype=np.float64)
         _check(self._L.wgbsseg_marker_stats(self._h, tg.ctypes.data, tg.size, bg.ctypes.data, bg.size, int(n_blocks), out.ctypes.data,
+                                            self._err, ERRLEN), self._err)
+        return out
+
+    def sample_stats(self, ranges, depth_at=10):
+        """wgbsseg_sample_stats over the resident samples: `ranges` = 0-based half-open site ranges [[start0, end0), ...], ascending
+        and disjoint (an empty list: all-zero results) -> structured array [n_samples] of SAMPLE_STAT_DTYPE."""
+        r = np.ascontiguousarray(ranges, dtype=np.int64).reshape(-1, 2)
+        s, e = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+        out = np.zeros(self.n_samples, dtype=SAMPLE_STAT_DTYPE)
+        _check(self._L.wgbsseg_sample_stats(self._h, s.ctypes.data, e.ctypes.data, s.size, int(depth_at), out.ctypes.data,
                                             self._err, ERRLEN), self._err)
         return out
 

@@ -33,6 +33,7 @@
 #include "pat_kernels.h"
 #include "homog_kernels.h"
 #include "bimodal_kernels.h"
+#include "stats_kernels.h"
 #include "plain_dp.h"
 #include "stitch.h"
 #include "add_loci.h"
@@ -127,6 +128,7 @@ struct wgbsseg_ctx {
     // API calls: device-resident betas handed over by pointer may change between them.
     std::vector<std::pair<int64_t, int64_t>> validated;
     DevBuf scan_pieces, divcheck, plan_sb, bs_desc;
+    DevBuf st_ranges, st_parts;     // wgbsseg_sample_stats: the range table | the tiles' partial results and the per-sample results
     std::vector<int32_t> h_stage_bounds;
     // the short division core of the narrow scoring tiles: verified on the device per pseudo count (k_check_div)
     float divs_pc = -1.0f;     // pseudo count the verdict below is for
@@ -2385,6 +2387,69 @@ int wgbsseg_marker_stats(wgbsseg_ctx* c, const int32_t* tg, int32_t n_tg, const 
 }
 
 double wgbsseg_last_block_sums_ms(const wgbsseg_ctx* c) { return c ? c->last_block_sums_ms : 0.0; }
+
+static_assert(sizeof(wgbsseg_sample_stat) == sizeof(wg_sample_stat) && sizeof(wg_sample_stat) == 72, "wgbsseg_sample_stat is the kernels' wg_sample_stat");
+
+int wgbsseg_sample_stats(wgbsseg_ctx* c, const int64_t* start0, const int64_t* end0, int64_t n_ranges, int32_t depth_at,
+                         wgbsseg_sample_stat* out, char* err, size_t errlen)
+{
+    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
+    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
+    if (n_ranges < 0 || !out || (n_ranges && (!start0 || !end0))) { set_err(err, errlen, "bad arguments to sample_stats"); return WGBSSEG_E_ARG; }
+    const int64_t S = 8 / c->elem;                               // sites per 16-byte vector of a row
+    std::vector<int64_t> h((size_t)n_ranges * 3 + 1);           // x0 | x1 | cumv: the 16-byte vectors of the ranges before each one
+    int64_t* hx0 = h.data();
+    int64_t* hx1 = hx0 + n_ranges;
+    int64_t* hcum = hx1 + n_ranges;
+    int64_t n_sites = 0, n_vec = 0;
+    for (int64_t i = 0; i < n_ranges; i++) {
+        const int64_t a = start0[i], b = end0[i];
+        if (a < 0 || b < a || b > c->n_total) {
+            set_err(err, errlen, "sample_stats: range %lld = sites [%lld, %lld) is outside the %lld resident sites or reversed", (long long)i, (long long)a, (long long)b, (long long)c->n_total);
+            return WGBSSEG_E_ARG;
+        }
+        if (i && a < end0[i - 1]) {
+            set_err(err, errlen, "sample_stats: range %lld = sites [%lld, %lld) begins before range %lld ends (%lld): ranges must be ascending and disjoint",
+                    (long long)i, (long long)a, (long long)b, (long long)(i - 1), (long long)end0[i - 1]);
+            return WGBSSEG_E_ARG;
+        }
+        hx0[i] = a; hx1[i] = b; hcum[i] = n_vec;
+        n_sites += b - a;
+        if (b > a) n_vec += (b + S - 1) / S - a / S;
+    }
+    hcum[n_ranges] = n_vec;
+    const int64_t n_tiles = (n_vec + WG_ST_TILE - 1) / WG_ST_TILE;
+    if (n_tiles > 0x7fffffff || c->n_samples > 65535) { set_err(err, errlen, "too many sites / samples for one sample_stats call"); return WGBSSEG_E_ARG; }
+    if (n_vec == 0) {                                            // nothing to read: no ranges, or empty ones only
+        memset(out, 0, sizeof(*out) * (size_t)c->n_samples);
+        c->last_block_sums_ms = 0.0;
+        return WGBSSEG_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t part_bytes = (size_t)n_tiles * (size_t)c->n_samples * sizeof(wg_stat_part);
+    HIP_TRY(c->st_ranges.ensure(h.size() * 8));
+    HIP_TRY(c->st_parts.ensure(part_bytes + (size_t)c->n_samples * sizeof(wg_sample_stat)));
+    HIP_TRY(hipMemcpyAsync(c->st_ranges.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->sA));
+    const int64_t* dx0 = c->st_ranges.as<int64_t>();
+    wg_stat_part* dparts = c->st_parts.as<wg_stat_part>();
+    wg_sample_stat* dout = reinterpret_cast<wg_sample_stat*>(c->st_parts.as<uint8_t>() + part_bytes);
+    const dim3 grid((unsigned)n_tiles, (unsigned)c->n_samples);
+    HIP_TRY(hipEventRecord(c->ev[0], c->sA));
+    if (c->elem == 1)
+        hipLaunchKernelGGL(k_sample_stats<1>, grid, dim3(WG_ST_BLOCK), 0, c->sA, c->betas, c->pitch, dx0, dx0 + n_ranges, dx0 + 2 * n_ranges, n_ranges, n_vec, depth_at, dparts, n_tiles);
+    else
+        hipLaunchKernelGGL(k_sample_stats<2>, grid, dim3(WG_ST_BLOCK), 0, c->sA, c->betas, c->pitch, dx0, dx0 + n_ranges, dx0 + 2 * n_ranges, n_ranges, n_vec, depth_at, dparts, n_tiles);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sample_stats_fold, dim3((unsigned)c->n_samples), dim3(WG_ST_BLOCK), 0, c->sA, dparts, n_tiles, (uint64_t)n_sites, dout);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[1], c->sA));
+    HIP_TRY(hipMemcpyAsync(out, dout, sizeof(*out) * (size_t)c->n_samples, hipMemcpyDeviceToHost, c->sA));
+    HIP_TRY(hipStreamSynchronize(c->sA));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    c->last_block_sums_ms = ms;                                  // (the shared "last auxiliary kernel" clock: wgbsseg_last_block_sums_ms)
+    return WGBSSEG_OK;
+}
 
 int wgbsseg_add_loci(const uint32_t* loci, int64_t n_sites, const int64_t* chrom_cum, const char* const* chrom_names,
                      int32_t n_chroms, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks,
