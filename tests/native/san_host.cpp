@@ -1,5 +1,5 @@
-// Sanitizer harness for the host-side C++ of the library (TEST INFRASTRUCTURE): csrc/stitch.h (chunk grid, junction rehearsal,
-// pairwise trees on the thread pool, flattening) and csrc/add_loci.h (BED rows), driven by a toy chunk engine that is a pure
+// Sanitizer harness for the host-side C++ of the library (TEST INFRASTRUCTURE): csrc/block_plan.h (the plan of a block reduction),
+// csrc/stitch.h (chunk grid, junction rehearsal, pairwise trees on the thread pool, flattening) and csrc/add_loci.h (BED rows), driven by a toy chunk engine that is a pure
 // function of the site range — as the real DP is — so that junction patches share borders with their chunks or, where the toy
 // makes them disagree, force the patch to double.  Built by tests/test_sanitizers_cpu.py three times (plain, ASan + UBSan,
 // TSan); every build must print the same checksum lines.
@@ -14,9 +14,13 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <cmath>
+#include <algorithm>
+#include <set>
+#include <utility>
 #include "stitch.h"
 #include "add_loci.h"
 #include "table_io.h"
+#include "block_plan.h"
 
 static uint64_t mix(uint64_t x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33; return x; }
 
@@ -73,10 +77,67 @@ static uint64_t run_world(int n_regions, int64_t region_len, int64_t chunk, int 
     return h;
 }
 
+// The plans of the block reduction (block_plan.h) over the tables of tests/block_tables.py, built here again: 17,413 sites, an edge at every multiple
+// of 896 and 1024 (-1, 0, +1), blocks of 1024, 1025 and 2,500 sites with blocks fanning in and out of them, empty blocks at both ends; ordered,
+// shuffled, with a nested block, one row forty times; uint8 and uint16 rows, the general kernel forced; and the refusals.  One line: a checksum.
+static void block_plan_line()
+{
+    typedef std::pair<int64_t, int64_t> Row;
+    const int64_t N = 17413, LONG[3][2] = {{1500, 2524}, {4000, 5025}, {8191, 10691}};
+    std::set<int64_t> edges, cuts{0, N};
+    for (int64_t tile : {896, 1024}) for (int64_t m = tile; m < N; m += tile) for (int64_t d = -1; d <= 1; d++) edges.insert(m + d);
+    std::vector<Row> rows{{0, 0}, {N - 1, N}, {N, N}};
+    for (int64_t x : edges) { bool in = false; for (auto& L : LONG) in |= L[0] < x && x < L[1]; if (!in) cuts.insert(x); }
+    for (auto& L : LONG) {
+        std::vector<int64_t> inside;
+        for (int64_t x : edges) if (L[0] < x && x < L[1]) inside.push_back(x);
+        const int64_t m = (int64_t)inside.size();
+        cuts.insert(L[0] - 1 - m); cuts.insert(L[0]); cuts.insert(L[1]);
+        for (int64_t j = 0; j < m; j++) { rows.push_back({L[0] - m + j, inside[(size_t)j]}); rows.push_back({inside[(size_t)j], L[1]}); }
+    }
+    for (auto it = cuts.begin(), nx = std::next(it); nx != cuts.end(); ++it, ++nx) rows.push_back({*it, *nx});
+    std::sort(rows.begin(), rows.end());
+    std::vector<std::vector<Row>> tables{rows};
+    std::vector<Row> sh = rows;                                               // a fixed shuffle (ties in the first site fall as they fall: the sort is stable)
+    for (size_t i = sh.size() - 1; i > 0; i--) std::swap(sh[i], sh[(size_t)(mix(i * 7919 + 11) % (i + 1))]);
+    tables.push_back(sh);
+    std::vector<Row> nest = rows;
+    nest.insert(std::lower_bound(nest.begin(), nest.end(), Row(100, 0)), Row(100, 9000));
+    tables.push_back(nest);
+    tables.push_back(std::vector<Row>(40, Row(700, 1900)));
+    tables.push_back({{5, 9}, {-1, 3}});                                      // the refusals: negative start, reversed, beyond the rows, too long for uint16 sums
+    tables.push_back({{5, 9}, {9, 3}});
+    tables.push_back({{5, N + 1}});
+    tables.push_back({{0, 9}, {3, 3 + 65537}});
+    uint64_t h = 1469598103934665603ULL;
+    auto fold = [&](uint64_t v) { h = (h ^ v) * 1099511628211ULL; };
+    int n_ok = 0, n_refused = 0;
+    for (size_t k = 0; k < tables.size(); k++) {
+        std::vector<int64_t> s0, e0;
+        for (auto& r : tables[k]) { s0.push_back(r.first); e0.push_back(r.second); }
+        for (int var = 0; var < 3; var++) {                                   // uint8 rows | the general kernel forced | uint16 rows, mode 0
+            BlockSumPlan p;
+            std::string msg;
+            const int rc = plan_block_sums(s0.data(), e0.data(), (int64_t)s0.size(), k == 7 ? 70000 : N, var == 2 ? 2 : 1, 0, var == 1, p, msg);
+            fold((uint64_t)(int64_t)rc); for (char ch : msg) fold((uint64_t)(unsigned char)ch);
+            if (rc != WGBSSEG_OK) { n_refused++; continue; }
+            n_ok++;
+            fold((uint64_t)p.sorted); fold((uint64_t)p.monotone); fold((uint64_t)p.n_tiles); fold((uint64_t)p.n_direct);
+            if (p.upload.size() != p.upload_words()) fold(0xbadULL);
+            const BlockSumPlan::View<const int32_t> v = p.view((const int32_t*)p.upload.data());
+            for (int64_t i = 0; i < p.n_blocks; i++) { fold((uint64_t)v.x0[i]); fold((uint64_t)v.x1[i]); if (v.perm) fold((uint64_t)v.perm[i]); }
+            for (int64_t t = 0; t <= p.n_tiles; t++) fold((uint64_t)v.tile_first[t]);
+            for (int64_t i = 0; i < p.n_direct; i++) fold((uint64_t)v.direct[i]);
+        }
+    }
+    printf("block_plan: %zu tables of up to %zu blocks, %d plans, %d refusals, checksum %016llx\n", tables.size(), nest.size(), n_ok, n_refused, (unsigned long long)h);
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 3) { fprintf(stderr, "usage: san_host <threads> <out.bed>\n"); return 2; }
     setenv("WGBSSEG_STITCH_THREADS", argv[1], 1);
+    block_plan_line();
     std::vector<int64_t> s, e;
     for (int rep = 0; rep < 3; rep++) {                                      // the pool is reused across calls
         std::vector<int64_t> s1, e1;

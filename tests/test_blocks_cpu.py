@@ -1,15 +1,18 @@
 """Block reduction (beta_to_blocks / beta_to_table) without a GPU: the oracle and the host
 logic of the mirrors against vectors captured from the reference's own Python (tests/golden/make_golden_blocks.py)."""
 import base64
+import ctypes as C
 import hashlib
 import io
 import json
 import os.path as op
+import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import block_sums as OB
+import block_tables as BT
 import cases
 from wgbs_tools_amd import beta_to_blocks as B2B, beta_to_table as B2T, synth
 
@@ -370,7 +373,7 @@ def test_comments_inside_a_line_and_pandas_missing_values(tmp_path):
 
 def test_trim_rescale_is_an_integer_division():
     """utils_wgbs.py:277-290 trim_to_uint8 rescales a saturated pair with three float64 operations, trunc(fl(fl(m / c) * 255)).  Round 5's block reduction
-    computes floor(255 m / c) in integers instead (csrc/seg_kernels.h wg_rescale_255: a float32 estimate pushed down by 1e-4, one exact correction).
+    computes floor(255 m / c) in integers instead (csrc/block_kernels.h wg_rescale_255: a float32 estimate pushed down by 1e-4, one exact correction).
     (1) the two are the same number: every exact quotient K / 255 (and K / 65535) survives the two roundings, and random / structured pairs agree;
     (2) the device's arithmetic, restated in numpy float32 with the reciprocal off by one ulp EITHER way (v_rcp_f32's accuracy), returns that floor."""
     # (1a) exact quotients: m / c = K / M as a real number => fl(m / c) = fl(K / M): 256 (65536) cases cover every such pair
@@ -400,3 +403,161 @@ def test_trim_rescale_is_an_integer_division():
         assert (r >= 0).all()
         got = q + (r >= c)
         assert np.array_equal(got, want)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the host plan of the block reduction (csrc/block_plan.h) against a restatement, block by block
+# ---------------------------------------------------------------------------------------------------------
+_ROOT = op.dirname(HERE)
+_PLAN_SRC = op.join(HERE, 'native', 'blockplan_host.cpp')
+_PLAN_LIB = op.join(HERE, 'native', 'libblockplan_host.so')
+_PLAN_HDR = op.join(_ROOT, 'wgbs_tools_amd', 'csrc', 'block_plan.h')
+E_ARG = -1
+
+
+@pytest.fixture(scope='module')
+def planlib():
+    """tests/native/libblockplan_host.so (built when missing or older than its sources)"""
+    if not op.isfile(_PLAN_LIB) or op.getmtime(_PLAN_LIB) < max(op.getmtime(_PLAN_SRC), op.getmtime(_PLAN_HDR)):
+        subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', _PLAN_SRC, '-o', _PLAN_LIB])
+    L = C.CDLL(_PLAN_LIB)
+    L.blockplan_tile_of.restype = C.c_int64
+    L.blockplan_tile_of.argtypes = [C.c_int32, C.c_int32]
+    L.blockplan_ring_reaches.restype = C.c_int32
+    L.blockplan_ring_reaches.argtypes = [C.c_int32, C.c_int32, C.c_int64]
+    L.blockplan_constants.argtypes = [C.c_void_p]
+    L.blockplan_run.restype = C.c_int
+    L.blockplan_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    k = np.zeros(5, dtype=np.int32)
+    L.blockplan_constants(k.ctypes.data)
+    assert k.tolist() == [896, 8, 16, 1024, 8]
+    return L
+
+
+def _plan(L, s0, e0, n_total=BT.N_TOTAL, elem=1, mode=0, general=False):
+    s0 = np.ascontiguousarray(s0, dtype=np.int64); e0 = np.ascontiguousarray(e0, dtype=np.int64)
+    n = s0.size
+    cap = n_total // 896 + 8
+    x0, x1, perm, direct = (np.full(max(n, 1), -7, dtype=np.int32) for _ in range(4))
+    tf = np.full(cap, -7, dtype=np.int32)
+    info = np.zeros(5, dtype=np.int64)
+    msg = C.create_string_buffer(600)
+    rc = L.blockplan_run(s0.ctypes.data, e0.ctypes.data, n, n_total, elem, mode, int(general), x0.ctypes.data, x1.ctypes.data, perm.ctypes.data,
+                         tf.ctypes.data, cap, direct.ctypes.data, info.ctypes.data, msg, 600)
+    is_sorted, monotone, n_tiles, n_direct, words = (int(v) for v in info)
+    return dict(rc=rc, msg=msg.value.decode(), sorted=bool(is_sorted), monotone=bool(monotone), n_tiles=n_tiles, words=words,
+                x0=x0[:n].tolist(), x1=x1[:n].tolist(), perm=None if is_sorted else perm[:n].tolist(), tile_first=tf[:n_tiles + 1].tolist(), direct=direct[:n_direct].tolist())
+
+
+def _restated_plan(s0, e0, n_total, elem, general):
+    """what the plan must hold, worked out one block at a time from the description of the kernels (block_kernels.h), not from the plan's code"""
+    s0, e0 = [int(v) for v in s0], [int(v) for v in e0]
+    n = len(s0)
+    is_sorted = all(s0[i] >= s0[i - 1] for i in range(1, n))
+    order = sorted(range(n), key=lambda i: (s0[i], i))                       # by first site; ties in file order
+    x0, x1 = [s0[i] for i in order], [e0[i] for i in order]
+    monotone = elem == 1 and not general and all(x1[i] >= x1[i - 1] for i in range(1, n))
+    if not monotone:                                                         # 896-site tiles: the first block that starts at or behind the tile's first site
+        n_tiles = -(-n_total // 896)
+        tf = [sum(1 for b in range(n) if x0[b] < t * 896) for t in range(n_tiles)] + [n]
+        return dict(sorted=is_sorted, monotone=False, n_tiles=n_tiles, x0=x0, x1=x1, perm=None if is_sorted else order, tile_first=tf, direct=[])
+    n_tiles = -(-n_total // 1024)
+    tile, direct = [], []
+    for b in range(n):
+        if x1[b] > x0[b]:                                                    # resolved in the tile of its last site ...
+            t = (x1[b] - 1) // 1024
+            first_in_ring = t * 1024 if t % 8 == 0 else (t - 1) * 1024 + 1   # ... from the prefixes of that tile and, inside a run, of the one before it: I(x0 - 1) must be there
+            if x0[b] < first_in_ring:
+                direct.append(b)
+        else:
+            t = min(x0[b] // 1024, n_tiles - 1)                              # an empty block: the tile of its position, the last one for a position behind it
+        tile.append(t)
+    tf = [sum(1 for b in range(n) if tile[b] < t) for t in range(n_tiles)] + [n]
+    return dict(sorted=is_sorted, monotone=True, n_tiles=n_tiles, x0=x0, x1=x1, perm=None if is_sorted else order, tile_first=tf, direct=direct)
+
+
+def _plan_tables():
+    tabs = {'ordered': BT.ordered(), 'shuffled': BT.shuffled(), 'shuffled_any_ties': BT.shuffled(keep_ties=False), 'nested': BT.nested(), 'identical': BT.identical()}
+    s0, e0 = BT.nested()
+    o = np.random.default_rng(5).permutation(s0.size)
+    tabs['nested_shuffled'] = (s0[o], e0[o])
+    return tabs
+
+
+@pytest.mark.parametrize('name', ['ordered', 'shuffled', 'shuffled_any_ties', 'nested', 'nested_shuffled', 'identical'])
+def test_block_plan_against_restatement(planlib, name):
+    """Sorted arrays and permutation (stable), `monotone`, every entry of the tile table for 896-site tiles (general kernel: forced, and uint16 rows) and
+    for 1024-site tiles (streaming kernel), the direct list; and for every block exactly one of "its tile's ring reaches it" and "in the direct list"."""
+    s0, e0 = _plan_tables()[name]
+    n = s0.size
+    assert n <= 400
+    want_flags = {'ordered': (True, True), 'shuffled': (False, True), 'nested': (True, False), 'nested_shuffled': (False, False), 'identical': (True, True)}
+    for elem, general in ((1, False), (1, True), (2, False)):
+        got = _plan(planlib, s0, e0, elem=elem, general=general)
+        want = _restated_plan(s0, e0, BT.N_TOTAL, elem, general)
+        assert got['rc'] == 0 and got['msg'] == ''
+        for key in ('sorted', 'monotone', 'n_tiles', 'x0', 'x1', 'perm', 'tile_first', 'direct'):
+            assert got[key] == want[key], (name, elem, general, key)
+        assert got['words'] == (2 if got['sorted'] else 3) * n + got['n_tiles'] + 1 + len(got['direct'])
+        if name in want_flags and elem == 1 and not general:
+            assert (got['sorted'], got['monotone']) == want_flags[name]
+        if got['monotone']:
+            in_direct = set(got['direct'])
+            for b in range(n):
+                x0, x1 = got['x0'][b], got['x1'][b]
+                t = planlib.blockplan_tile_of(x0, x1)
+                assert t == ((x1 - 1) // 1024 if x1 > x0 else x0 // 1024)
+                reached = bool(planlib.blockplan_ring_reaches(x0, x1, t))
+                assert reached != (b in in_direct), (name, b, x0, x1)
+                assert reached or x1 > x0
+                # the table puts the block into the tile the rule names (an empty block at the very end: into the last tile)
+                tt = min(t, got['n_tiles'] - 1)
+                assert got['tile_first'][tt] <= b < got['tile_first'][tt + 1], (name, b, x0, x1)
+    if name == 'ordered':
+        got = _plan(planlib, s0, e0)
+        assert len(got['direct']) >= 10 and got['x0'][got['direct'][0]] < got['x1'][got['direct'][0]]
+        lens = (e0 - s0).tolist()
+        assert 1024 in lens and 1025 in lens and (8191, 10691) in zip(s0.tolist(), e0.tolist())
+        assert (s0[0], e0[0]) == (0, 0) and (s0[-1], e0[-1]) == (BT.N_TOTAL, BT.N_TOTAL) and (s0[-2], e0[-2]) == (BT.N_TOTAL - 1, BT.N_TOTAL)
+        edges = set(s0.tolist()) | set(e0.tolist())
+        assert all(m + d in edges for tile in (896, 1024) for m in range(tile, BT.N_TOTAL, tile) for d in (-1, 0, 1))
+
+
+def test_block_plan_rules_on_a_grid(planlib):
+    """the two rules around every tile and run boundary of three runs, block lengths 0 .. 2 tiles + 1"""
+    for x0 in [b + d for b in range(0, 3 * 8192 + 1, 1024) for d in (-2, -1, 0, 1, 2) if b + d >= 0]:
+        for ln in (0, 1, 2, 1022, 1023, 1024, 1025, 1026, 2047, 2048, 2049):
+            x1 = x0 + ln
+            t = (x1 - 1) // 1024 if ln else x0 // 1024
+            assert planlib.blockplan_tile_of(x0, x1) == t
+            lo = t * 1024
+            want = ln == 0 or (x0 >= lo if t % 8 == 0 else x0 >= lo - 1023)
+            assert bool(planlib.blockplan_ring_reaches(x0, x1, t)) == want, (x0, x1)
+
+
+def test_block_plan_rows_that_fill_their_last_tile(planlib):
+    """n_total a multiple of both tiles: an empty block at n_total names a tile behind the last; the table keeps it in the last one"""
+    n_total = 7168
+    s0, e0 = np.array([0, 7000, n_total, n_total]), np.array([7000, n_total, n_total, n_total])
+    for general, n_tiles in ((False, 7), (True, 8)):
+        got = _plan(planlib, s0, e0, n_total=n_total, general=general)
+        want = _restated_plan(s0, e0, n_total, 1, general)
+        assert got['rc'] == 0 and got['n_tiles'] == n_tiles and got['tile_first'] == want['tile_first'] and got['direct'] == want['direct']
+        assert got['tile_first'][-2] <= 2 and got['tile_first'][-1] == 4         # the two empty blocks: in the last tile
+    assert planlib.blockplan_tile_of(n_total, n_total) == 7                  # one behind the streaming kernel's last tile
+
+
+def test_block_plan_refusals(planlib):
+    n = BT.N_TOTAL
+    for s0, e0, kw, text in (([5, -1], [9, 3], {}, 'block 1 = sites [-1, 3) is outside the %d sites of the beta files or reversed' % n),
+                             ([5, 9], [9, 3], {}, 'block 1 = sites [9, 3) is outside the %d sites of the beta files or reversed' % n),
+                             ([5], [n + 1], {}, 'block 0 = sites [5, %d) is outside the %d sites of the beta files or reversed' % (n + 1, n)),
+                             ([0, 3], [9, 3 + 65537], dict(elem=2, mode=0, n_total=70000), 'block 1: uint32 sums of uint16 counts are only exact up to 65536 sites per block'),
+                             ([0], [1], dict(mode=4), 'bad arguments to block_sums'),
+                             ([0], [1], dict(n_total=2 ** 31), 'too many blocks / sites for one block_sums call')):
+        got = _plan(planlib, s0, e0, **kw)
+        assert (got['rc'], got['msg']) == (E_ARG, text)
+    for kw in (dict(elem=2, mode=1, n_total=70000), dict(elem=1, mode=0, n_total=70000), dict(elem=2, mode=0, n_total=70000)):
+        assert _plan(planlib, [0, 3], [9, 3 + 65536 + (kw['elem'] == 1 or kw['mode'] == 1)], **kw)['rc'] == 0      # uint8 rows, other modes, exactly 65536 sites
+    got = _plan(planlib, [], [])
+    assert got['rc'] == 0 and got['words'] == 0

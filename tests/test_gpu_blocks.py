@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import block_sums as OB
+import block_tables as BT
 import cases
 from wgbs_tools_amd import _lib, synth, wgbs_tools
 from test_blocks_cpu import world          # noqa: F401  (fixture: betas, blocks tables and goldens on disk)
@@ -256,3 +257,55 @@ def test_bin_rows_of_a_corrupt_file_do_not_depend_on_the_kernel(monkeypatch):
         sums = OB.block_sums(d, s0, e0)
         assert (sums[:, 0] > sums[:, 1]).any()
         assert (res[0][s] == OB.trim(sums, False)).all()
+
+
+@pytest.fixture(scope='module')
+def plan_world():
+    """tests/block_tables.py's 17,413 sites: 5 samples of uint8 rows whose coverage reaches 255 (two workgroup rows of the four-samples-per-workgroup
+    grids, spw = 2 in the general kernel; the rescale of modes 1 and 2 fires), 2 samples of uint16 rows, and the oracle's sums of every table, once."""
+    rng = np.random.default_rng(1024)
+    n = BT.N_TOTAL
+    data = []
+    for s in range(5):
+        cov = rng.integers(0, 256, n)
+        cov[rng.random(n) < 0.3] = 255
+        if s == 3:
+            cov[6000:9000] = 0                                            # blocks without coverage: NaN in mode 3, whatever min_cov
+        meth = (cov * rng.random(n)).astype(np.int64)
+        data.append(np.ascontiguousarray(np.stack([meth, cov], axis=1).astype(np.uint8)))
+    ldata = [cases.lbeta_twin(d) for d in data[:2]]
+    tables = {'ordered': BT.ordered(), 'shuffled': BT.shuffled(), 'nested': BT.nested()}
+    want = {name: [OB.block_sums(d, s0, e0) for d in data] for name, (s0, e0) in tables.items()}
+    lwant = [OB.block_sums(d, *tables['ordered']) for d in ldata]
+    return dict(data=data, ldata=ldata, tables=tables, want=want, lwant=lwant)
+
+
+def _same_modes(sg, s0, e0, want, tag):
+    """modes 0 .. 3 (mode 3 with min_cov 1 and 3) of one table against the oracle's sums: exact, NaN positions included"""
+    got = {0: sg.block_sums(s0, e0, mode=0), 1: sg.block_sums(s0, e0, mode=1), 2: sg.block_sums(s0, e0, mode=2),
+           (3, 1): sg.block_sums(s0, e0, mode=3, min_cov=1), (3, 3): sg.block_sums(s0, e0, mode=3, min_cov=3)}
+    for s, w in enumerate(want):
+        bad = np.flatnonzero((got[0][s].astype(np.int64) != (w & 0xffffffff)).any(1))
+        assert bad.size == 0, '%s sample %d: block %d = [%d, %d): got %s want %s' % (tag, s, bad[0], s0[bad[0]], e0[bad[0]], got[0][s][bad[0]], w[bad[0]])
+        assert np.array_equal(got[1][s], OB.trim(w, False)) and np.array_equal(got[2][s], OB.trim(w, True)), (tag, s)
+        for mc in (1, 3):
+            w3 = OB.beta2vec(w, mc)
+            assert np.array_equal(np.isnan(got[(3, mc)][s]), np.isnan(w3)), (tag, s, mc)
+            assert np.array_equal(got[(3, mc)][s][~np.isnan(w3)].view(np.uint64), w3[~np.isnan(w3)].view(np.uint64)), (tag, s, mc)
+
+
+@pytest.mark.parametrize('general', [0, 1])
+def test_block_sums_of_the_plan_world_against_oracle(general, plan_world, monkeypatch):
+    """The tables the host plan is checked on (tests/test_blocks_cpu.py::test_block_plan_against_restatement) through the kernels: an edge at every
+    multiple of 896 and 1024 (-1, 0, +1), blocks of 1024, 1025 and 2,500 sites, empty blocks at both ends — ordered (streaming kernel, prep + run +
+    direct), shuffled (the same through the permutation), with a nested block (general kernel) — and the general kernel forced; uint16 rows."""
+    monkeypatch.setenv('WGBSSEG_BLOCK_SUMS_GENERAL', str(general))
+    with _lib.Segmenter(0) as sg:
+        sg.set_betas(plan_world['data'])
+        for name, (s0, e0) in plan_world['tables'].items():
+            _same_modes(sg, s0, e0, plan_world['want'][name], '%s (general %d)' % (name, general))
+            assert sg.last_block_sums_ms() > 0
+    if general == 0:
+        with _lib.Segmenter(0) as sg:
+            sg.set_lbetas(plan_world['ldata'])
+            _same_modes(sg, *plan_world['tables']['ordered'], plan_world['lwant'], 'ordered, uint16 rows')

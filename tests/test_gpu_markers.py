@@ -54,3 +54,24 @@ def test_marker_stats_kernel_against_numpy():
     assert np.array_equal(got.view(np.uint64) == want.view(np.uint64), np.ones_like(got, dtype=bool)) or \
         (np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(got[~np.isnan(got)], want[~np.isnan(want)]))
     print('k_marker_stats: %.3f ms for %d blocks x %d samples' % (ms, s0.size, len(tg) + len(bg)))
+
+
+def test_marker_stats_table_survives_a_debug_call():
+    """The ratio table of a mode-3 reduction has a buffer of its own: a wgbsseg_debug_* call between the reduction and marker_stats (they share
+    scratch among themselves) leaves the statistics as they are, bit for bit."""
+    n, N = 40000, 6
+    data = [synth.synth_betas(57, s, 0, n) for s in range(N)]
+    data[1][5000:9000, :] = 0
+    b = np.arange(0, n + 16, 16, dtype=np.int64).clip(max=n)
+    s0, e0 = b[:-1], b[1:]
+    tg, bg = [1], [0, 5, 2, 4]
+    with _lib.Segmenter(0) as sg:
+        sg.set_betas(data)
+        sg.block_sums(s0, e0, mode=3, min_cov=20)
+        want = sg.marker_stats(tg, bg, s0.size)
+        sg.block_sums(s0, e0, mode=3, min_cov=20)
+        cnt = np.arange(N * s0.size * 2, dtype=np.float32) % 97              # as many bytes as the table has
+        sg.debug_sample_terms(cnt * 0.5, cnt, 15.0)
+        got = sg.marker_stats(tg, bg, s0.size)
+    assert np.isnan(want[:, 2]).any() and not np.isnan(want[:, 2]).all()
+    assert np.array_equal(got.view(np.uint64), want.view(np.uint64))

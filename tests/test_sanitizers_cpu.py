@@ -1,5 +1,6 @@
 """Sanitizer builds of the host-side native code (the reference has none; its `segmentor` has a real UB at max_bp == 0):
-csrc/stitch.h + csrc/add_loci.h (chunk grid, junction stitching on the thread pool, BED rows) and the oracle's C restatement of the
+csrc/block_plan.h (the plan of a block reduction), csrc/stitch.h + csrc/add_loci.h (chunk grid, junction stitching on the thread pool, BED rows)
+and the oracle's C restatement of the
 chunk DP, each compiled plain, with AddressSanitizer + UndefinedBehaviorSanitizer, and with ThreadSanitizer, and run on
 deterministic toy inputs: every build must finish clean and print the same lines."""
 import os.path as op
@@ -48,6 +49,8 @@ def test_stitching_and_bed_rows_under_sanitizers(tmp_path):
             outs[(name, threads)] = (text, open(bed, 'rb').read())
     ref = outs[('plain', '1')]
     assert 'checksum' in ref[0] and ref[0].count('world') == 15 and 'rc 0' in ref[0] and len(ref[1]) > 5000
+    plan_line = [l for l in ref[0].splitlines() if l.startswith('block_plan: ')]
+    assert len(plan_line) == 1 and ', 14 plans, 10 refusals, checksum ' in plan_line[0]          # (identical across the builds: the loop below compares whole outputs)
     assert 'sitetable: ' in ref[0] and 'mismatches 0, concurrent misses 0' in ref[0]
     assert 'parse_blocks: rc 0 rows 40000 na 413' in ref[0] and 'parse_blocks on a float field: rc 1' in ref[0]
     assert ref[0].count('write_table pass') == 2 and 'DIFFERS' not in ref[0] and 'write_bedgraph: rc 0' in ref[0]

@@ -1,9 +1,9 @@
 // pat_kernels.h — the pat text format on gfx950: the staging of a tile of pat text in LDS, its line finding and the parsing of a
 // line, shared by every kernel that reads a pat file (k_pat_count here, k_homog_count in homog_kernels.h, k_bim_tile_count /
-// k_bim_fill in bimodal_kernels.h), and the pat -> beta kernels k_pat_count / k_pat_trim.  Includes seg_kernels.h, whose WG_BLOCK,
-// wg_wave_incl_scan_dpp_u32 and wg_block_sum_store it uses.
+// k_bim_fill in bimodal_kernels.h), and the pat -> beta kernels k_pat_count / k_pat_trim.  Includes block_kernels.h for the
+// wg_block_sum_store that k_pat_trim uses (and, through it, seg_kernels.h for WG_BLOCK and wg_wave_incl_scan_dpp_u32).
 #pragma once
-#include "seg_kernels.h"
+#include "block_kernels.h"
 
 // ------------------------------------------------------------------------------------------------------------
 // k_pat_count / k_pat_trim: a pat file -> (#meth, #cov) per CpG, the producer of the path's input (src/pat2beta/

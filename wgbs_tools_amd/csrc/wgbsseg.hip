@@ -1,5 +1,5 @@
 // wgbsseg.hip — host side of libwgbsseg.so: the C ABI of include/wgbsseg.h over the gfx950 kernels of
-// seg_kernels.h.  One context = one GPU (own streams, grow-only scratch in HBM).  No CPU compute path exists
+// seg_kernels.h and the other *_kernels.h.  One context = one GPU (own streams, grow-only scratch in HBM).  No CPU compute path exists
 // here: without a HIP device every entry point fails.
 //
 // Build (see wgbs_tools_amd/build.py):
@@ -16,6 +16,7 @@
 #include <cstring>
 #include <deque>
 #include <functional>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <thread>
@@ -30,6 +31,8 @@
 #include "../../include/wgbsseg.h"
 #include "owners.h"
 #include "seg_kernels.h"
+#include "block_plan.h"
+#include "block_kernels.h"
 #include "pat_kernels.h"
 #include "homog_kernels.h"
 #include "bimodal_kernels.h"
@@ -92,7 +95,8 @@ struct wgbsseg_ctx {
     DevBuf plan_cbase, plan_cum0, plan_tbase, plan_pairs, plan_tiles, plan_cnt, umax16;
     std::vector<PinnedBuf> pinned;
     std::vector<PinnedBuf> up_stage;   // the page-locked staging pieces of the uploads, `depth` per upload thread (run_upload); kept until destroy
-    DevBuf tiles[3], cost[3], stage_ctr, dpstate, tmp_borders, nb, boff, out_borders[2], edges, dbg_a, dbg_b, dbg_c, lookup;
+    DevBuf tiles[3], cost[3], stage_ctr, dpstate, tmp_borders, nb, boff, out_borders[2], edges, lookup;
+    DevBuf dbg_a, dbg_b, dbg_c;   // the wgbsseg_debug_* calls and wgbsseg_prefix_sums only
     int out_par = 0;              // which of the two result buffers the batch in flight writes: the lists of the previous batch may still be on their way home (below)
     // early delivery (segment_regions' first batch): k_copy_out (on the scan stream) writes the chunks' border lists into the page-locked result ...
     Event evS;     // the scan stream's last command of the batch in flight (the copy of its verdict)
@@ -121,13 +125,15 @@ struct wgbsseg_ctx {
     bool stage_gate_shared = false;
     int stage_gate = 768, last_stage_pct = -1, force_dp_mode = 0, force_ns = 0, force_ti = 0;
     double last_block_sums_ms = 0.0;
-    int64_t table_blocks = 0;  // > 0: dbg_b still holds the [n_samples][table_blocks] ratio table of the last mode-3 block reduction
+    int64_t table_blocks = 0;  // > 0: bs_out holds the [n_samples][table_blocks] ratio table of a mode-3 block reduction (what wgbsseg_marker_stats reads)
     bool accumulate = false;   // add to `tim` instead of resetting it (region-level calls span several batches)
     // site ranges whose `meth <= cov` check has run in the API call in flight (sorted, disjoint): the follow-up batches of a
     // region-level call hold junction patches only, all inside chunks its first batch has validated.  Never kept across
     // API calls: device-resident betas handed over by pointer may change between them.
     std::vector<std::pair<int64_t, int64_t>> validated;
-    DevBuf scan_pieces, divcheck, plan_sb, bs_desc;
+    DevBuf scan_pieces, divcheck, plan_sb;
+    DevBuf bs_plan, bs_desc, bs_out;   // wgbsseg_block_sums: the plan's tables (block_plan.h) | the streaming kernel's block descriptors | the result
+    DevBuf mk_out, cv_in, cv_out;      // wgbsseg_marker_stats: the statistics and the two sample lists; wgbsseg_convert_regions: the regions' columns | their CpG ranges
     DevBuf st_ranges, st_parts;     // wgbsseg_sample_stats: the range table | the tiles' partial results and the per-sample results
     std::vector<int32_t> h_stage_bounds;
     // the short division core of the narrow scoring tiles: verified on the device per pseudo count (k_check_div)
@@ -2237,123 +2243,101 @@ int wgbsseg_prefix_sums(wgbsseg_ctx* c, int64_t start0, int64_t len, uint32_t* o
     return WGBSSEG_OK;
 }
 
+}  // extern "C"
+
+namespace {
+
+// The timed tail of an auxiliary call (block_sums, marker_stats, sample_stats, convert_regions): begin() in front of its launches on stream A;
+// end() behind them brings the results home, waits, and leaves the launches' device time where wgbsseg_last_block_sums_ms reads it.
+struct AuxClock {
+    wgbsseg_ctx* c;
+    struct Fetch { void* dst; const void* src; size_t bytes; };
+    hipError_t begin() const { return hipEventRecord(c->ev[0], c->sA); }
+    hipError_t end(std::initializer_list<Fetch> home) const
+    {
+        hipError_t e = hipEventRecord(c->ev[1], c->sA);
+        for (const Fetch& f : home) if (e == hipSuccess) e = hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, c->sA);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->sA);
+        float ms = 0;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
+        if (e == hipSuccess) c->last_block_sums_ms = ms;
+        return e;
+    }
+};
+
+using BlockSumTables = BlockSumPlan::View<const int32_t>;      // a plan's tables on the device (bs_plan)
+
+// uint8 rows, a table ordered by first and last site: the descriptors of every block once (prep), the streamed pass, and a wavefront
+// per (block, sample) for the blocks the ring cannot serve
+int launch_block_sums_streaming(wgbsseg_ctx* c, const BlockSumPlan& p, const BlockSumTables& d, int mode, uint32_t min_cov, char* err, size_t errlen)
+{
+    const int64_t n_blocks = p.n_blocks;
+    int32_t* dd1 = c->bs_desc.as<int32_t>();
+    int32_t* dd0 = dd1 + n_blocks;
+    int32_t* drr = dd0 + n_blocks;
+    hipLaunchKernelGGL(k_block_sums_prep, dim3((unsigned)((n_blocks + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, c->sA, d.x0, d.x1, d.perm, n_blocks, p.n_tiles, dd1, dd0, drr);
+    HIP_TRY(hipGetLastError());
+    const unsigned gy = (unsigned)((c->n_samples + 3) / 4);
+    const dim3 grid((unsigned)((p.n_tiles + WG_BSR_RUN - 1) / WG_BSR_RUN), gy);
+#define WG_LAUNCH_BSR(M) hipLaunchKernelGGL(k_block_sums_run<M>, grid, dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, dd1, dd0, drr, d.tile_first, \
+                                            p.n_tiles, n_blocks, (int)c->n_samples, min_cov, c->bs_out.p)
+    if (mode == 0) WG_LAUNCH_BSR(0); else if (mode == 1) WG_LAUNCH_BSR(1); else if (mode == 2) WG_LAUNCH_BSR(2); else WG_LAUNCH_BSR(3);
+#undef WG_LAUNCH_BSR
+    HIP_TRY(hipGetLastError());
+    if (p.n_direct)
+        hipLaunchKernelGGL(k_block_sums_direct, dim3((unsigned)p.n_direct, gy), dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, d.x0, d.x1, d.perm,
+                           d.direct, p.n_direct, n_blocks, (int)c->n_samples, mode, min_cov, c->bs_out.p);
+    HIP_TRY(hipGetLastError());
+    return WGBSSEG_OK;
+}
+
+// every other table and uint16 rows: tiles of WG_BS_TILE sites, 4 x spw samples per workgroup
+template <int ELEM>
+int launch_block_sums_general(wgbsseg_ctx* c, const BlockSumPlan& p, const BlockSumTables& d, int spw, unsigned gy, int mode, uint32_t min_cov, char* err, size_t errlen)
+{
+    const int64_t gx = (p.n_tiles + WG_BS_RUN - 1) / WG_BS_RUN;
+    hipLaunchKernelGGL(k_block_sums<ELEM>, dim3((unsigned)gx, gy), dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total,
+                       d.x0, d.x1, d.perm, d.tile_first, p.n_tiles, p.n_blocks, (int)c->n_samples, spw, mode, min_cov, c->bs_out.p);
+    HIP_TRY(hipGetLastError());
+    return WGBSSEG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// plan (block_plan.h) -> upload -> launches -> fetch
 int wgbsseg_block_sums(wgbsseg_ctx* c, const int64_t* start0, const int64_t* end0, int64_t n_blocks, int32_t mode,
                        uint32_t min_cov, void* out, char* err, size_t errlen)
 {
     if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
     if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
-    if (n_blocks < 0 || mode < 0 || mode > 3 || (n_blocks && (!start0 || !end0 || !out))) { set_err(err, errlen, "bad arguments to block_sums"); return WGBSSEG_E_ARG; }
+    if (n_blocks > 0 && !out) { set_err(err, errlen, "bad arguments to block_sums"); return WGBSSEG_E_ARG; }
+    BlockSumPlan p;
+    std::string msg;
+    int rc = plan_block_sums(start0, end0, n_blocks, c->n_total, c->elem, mode, c->bs_general, p, msg);      // (bs_general: WGBSSEG_BLOCK_SUMS_GENERAL=1, tests)
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
     if (n_blocks == 0) return WGBSSEG_OK;
-    if (n_blocks > 0x7fffffff || c->n_total > 0x7fffffff) { set_err(err, errlen, "too many blocks / sites for one block_sums call"); return WGBSSEG_E_ARG; }
-    bool sorted = true;
-    for (int64_t i = 0; i < n_blocks; i++) {
-        if (start0[i] < 0 || end0[i] < start0[i] || end0[i] > c->n_total) {
-            set_err(err, errlen, "block %lld = sites [%lld, %lld) is outside the %lld sites of the beta files or reversed",
-                    (long long)i, (long long)start0[i], (long long)end0[i], (long long)c->n_total);
-            return WGBSSEG_E_ARG;
-        }
-        if (mode == 0 && c->elem == 2 && end0[i] - start0[i] > 65536) { set_err(err, errlen, "block %lld: uint32 sums of uint16 counts are only exact up to 65536 sites per block", (long long)i); return WGBSSEG_E_ARG; }
-        if (i && start0[i] < start0[i - 1]) sorted = false;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    // the kernel wants the blocks in order of their first site (a table a segmentation wrote already is): sort a copy
-    const int64_t n_tiles = (c->n_total + WG_BS_TILE - 1) / WG_BS_TILE;
-    std::vector<int32_t> h((size_t)n_blocks * (sorted ? 2 : 3) + (size_t)n_tiles + 1);
-    int32_t* hx0 = h.data();
-    int32_t* hx1 = hx0 + n_blocks;
-    int32_t* hperm = sorted ? nullptr : hx1 + n_blocks;
-    int32_t* htf = hx1 + n_blocks + (sorted ? 0 : n_blocks);
-    if (sorted) {
-        for (int64_t i = 0; i < n_blocks; i++) { hx0[i] = (int32_t)start0[i]; hx1[i] = (int32_t)end0[i]; }
-    } else {
-        for (int64_t i = 0; i < n_blocks; i++) hperm[i] = (int32_t)i;
-        std::stable_sort(hperm, hperm + n_blocks, [&](int32_t a, int32_t b) { return start0[a] < start0[b]; });
-        for (int64_t i = 0; i < n_blocks; i++) { hx0[i] = (int32_t)start0[hperm[i]]; hx1[i] = (int32_t)end0[hperm[i]]; }
-    }
-    {   // first block that starts at or after every tile's first site (empty blocks ride along with their start site)
-        int64_t b = 0;
-        for (int64_t t = 0; t <= n_tiles; t++) {
-            const int64_t lo = t * WG_BS_TILE;
-            while (b < n_blocks && hx0[b] < lo) b++;
-            htf[t] = (int32_t)b;
-        }
-        htf[n_tiles] = (int32_t)n_blocks;                          // blocks that start at n_total (empty) belong to the last tile
-    }
-    const size_t esz = mode == 0 ? 8 : (mode == 1 ? 2 : (mode == 2 ? 4 : 8));
-    const size_t obytes = (size_t)c->n_samples * (size_t)n_blocks * esz;
-    // uint8 rows and a table ordered by first AND last site (what a segmentation writes; beta_to_blocks' "nice" tables): the
-    // streaming kernel.  Its tile table: the first block whose last site lies at or behind every 1024-site tile's first site.
-    std::vector<int32_t> direct;
-    bool monotone = c->elem == 1 && (uint64_t)n_blocks * 8 < (1ull << 32);      // (32-bit output offsets in the streaming kernel)
-    for (int64_t i = 1; i < n_blocks && monotone; i++) monotone = hx1[i] >= hx1[i - 1];
-    if (c->bs_general) monotone = false;                         // WGBSSEG_BLOCK_SUMS_GENERAL=1 (tests): the general kernel for every table
-    const int64_t n_rtiles = (c->n_total + WG_BSR_TILE - 1) / WG_BSR_TILE;
-    if (monotone) {
-        h.resize((size_t)n_blocks * (sorted ? 2 : 3) + (size_t)n_rtiles + 1);
-        hx0 = h.data(); hx1 = hx0 + n_blocks; hperm = sorted ? nullptr : hx1 + n_blocks;
-        htf = hx1 + n_blocks + (sorted ? 0 : n_blocks);
-        int64_t b = 0;
-        for (int64_t t = 0; t <= n_rtiles; t++) {                  // tile of a block: the one holding its last site (empty blocks: their position)
-            while (b < n_blocks && (hx1[b] == 0 ? 0 : ((int64_t)std::max(hx1[b] - 1, hx0[b])) / WG_BSR_TILE) < t) b++;
-            htf[t] = (int32_t)b;
-        }
-        htf[n_rtiles] = (int32_t)n_blocks;
-        // blocks the streaming kernel cannot resolve from its two-tile ring (they begin before their run, or more than a tile
-        // before the tile they end in): a matter of the table alone; they get a wavefront per (block, sample) afterwards
-        for (int64_t i = 0; i < n_blocks; i++) {
-            if (hx1[i] <= hx0[i]) continue;
-            const int64_t t = (hx1[i] - 1) / WG_BSR_TILE, lo = t * WG_BSR_TILE;                 // (k_block_sums_prep applies the same rule)
-            if (t % WG_BSR_RUN == 0 ? hx0[i] < lo : hx0[i] < lo - (WG_BSR_TILE - 1)) direct.push_back((int32_t)i);
-        }
-        h.insert(h.end(), direct.begin(), direct.end());
-        hx0 = h.data(); hx1 = hx0 + n_blocks; hperm = sorted ? nullptr : hx1 + n_blocks;
-        htf = hx1 + n_blocks + (sorted ? 0 : n_blocks);
-    }
-    HIP_TRY(c->dbg_a.ensure(h.size() * 4));
-    HIP_TRY(c->dbg_b.ensure(obytes));
-    HIP_TRY(hipMemcpyAsync(c->dbg_a.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, c->sA));
-    const int32_t* dx0 = c->dbg_a.as<int32_t>();
-    const int32_t* dx1 = dx0 + n_blocks;
-    const int32_t* dperm = sorted ? nullptr : dx1 + n_blocks;
-    const int32_t* dtf = dx1 + n_blocks + (sorted ? 0 : n_blocks);
-    // samples per wavefront: enough workgroups to fill the chip, few enough that the block list is re-read rarely
-    // samples per wavefront (the kernel keeps two tiles of each in registers, one being reduced, one in flight)
+    // samples per wavefront of the general kernel (it keeps two tiles of each in registers, one being reduced, one in flight)
     const int spw = (c->elem == 1 && c->n_samples > 4) ? 2 : 1;
-    const int64_t gx = (n_tiles + WG_BS_RUN - 1) / WG_BS_RUN;
     const unsigned gy = (unsigned)((c->n_samples + 4 * spw - 1) / (4 * spw));
     if (gy > 65535) { set_err(err, errlen, "too many samples for one block_sums call"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipEventRecord(c->ev[0], c->sA));
-    if (monotone) {
-        HIP_TRY(c->bs_desc.ensure((size_t)n_blocks * 12));
-        int32_t* dd1 = c->bs_desc.as<int32_t>();
-        int32_t* dd0 = dd1 + n_blocks;
-        int32_t* drr = dd0 + n_blocks;
-        hipLaunchKernelGGL(k_block_sums_prep, dim3((unsigned)((n_blocks + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, c->sA, dx0, dx1, dperm, n_blocks, n_rtiles, dd1, dd0, drr);
-        HIP_TRY(hipGetLastError());
-        const dim3 grid((unsigned)((n_rtiles + WG_BSR_RUN - 1) / WG_BSR_RUN), (unsigned)((c->n_samples + 3) / 4));
-#define WG_LAUNCH_BSR(M) hipLaunchKernelGGL(k_block_sums_run<M>, grid, dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, dd1, dd0, drr, dtf, \
-                                            n_rtiles, n_blocks, (int)c->n_samples, min_cov, c->dbg_b.p)
-        if (mode == 0) WG_LAUNCH_BSR(0); else if (mode == 1) WG_LAUNCH_BSR(1); else if (mode == 2) WG_LAUNCH_BSR(2); else WG_LAUNCH_BSR(3);
-#undef WG_LAUNCH_BSR
-        if (!direct.empty()) {
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_block_sums_direct, dim3((unsigned)direct.size(), (unsigned)((c->n_samples + 3) / 4)), dim3(WG_BLOCK), 0, c->sA,
-                               c->betas, c->pitch, c->n_total, dx0, dx1, dperm, dtf + n_rtiles + 1, (int64_t)direct.size(), n_blocks,
-                               (int)c->n_samples, (int)mode, min_cov, c->dbg_b.p);
-        }
-    } else if (c->elem == 1)
-        hipLaunchKernelGGL(k_block_sums<1>, dim3((unsigned)gx, gy), dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total,
-                           dx0, dx1, dperm, dtf, n_tiles, n_blocks, (int)c->n_samples, spw, (int)mode, min_cov, c->dbg_b.p);
-    else
-        hipLaunchKernelGGL(k_block_sums<2>, dim3((unsigned)gx, gy), dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total,
-                           dx0, dx1, dperm, dtf, n_tiles, n_blocks, (int)c->n_samples, spw, (int)mode, min_cov, c->dbg_b.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[1], c->sA));
-    HIP_TRY(hipMemcpyAsync(out, c->dbg_b.p, obytes, hipMemcpyDeviceToHost, c->sA));
-    HIP_TRY(hipStreamSynchronize(c->sA));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->last_block_sums_ms = ms;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t esz = mode == 0 ? 8 : (mode == 1 ? 2 : (mode == 2 ? 4 : 8));
+    const size_t obytes = (size_t)c->n_samples * (size_t)n_blocks * esz;
+    c->table_blocks = 0;                                         // bs_out is about to change
+    HIP_TRY(c->bs_plan.ensure(p.upload.size() * 4));
+    HIP_TRY(c->bs_out.ensure(obytes));
+    if (p.monotone) HIP_TRY(c->bs_desc.ensure((size_t)n_blocks * 12));
+    HIP_TRY(hipMemcpyAsync(c->bs_plan.p, p.upload.data(), p.upload.size() * 4, hipMemcpyHostToDevice, c->sA));
+    const BlockSumTables d = p.view(c->bs_plan.as<const int32_t>());
+    const AuxClock clock{c};
+    HIP_TRY(clock.begin());
+    if (p.monotone) rc = launch_block_sums_streaming(c, p, d, mode, min_cov, err, errlen);
+    else if (c->elem == 1) rc = launch_block_sums_general<1>(c, p, d, spw, gy, mode, min_cov, err, errlen);
+    else rc = launch_block_sums_general<2>(c, p, d, spw, gy, mode, min_cov, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    HIP_TRY(clock.end({{out, c->bs_out.p, obytes}}));
     c->last_valid = false;
     c->table_blocks = mode == 3 ? n_blocks : 0;
     return WGBSSEG_OK;
@@ -2367,22 +2351,18 @@ int wgbsseg_marker_stats(wgbsseg_ctx* c, const int32_t* tg, int32_t n_tg, const 
     for (int i = 0; i < n_tg; i++) if (tg[i] < 0 || tg[i] >= c->n_samples) { set_err(err, errlen, "marker_stats: no sample %d", (int)tg[i]); return WGBSSEG_E_ARG; }
     for (int i = 0; i < n_bg; i++) if (bg[i] < 0 || bg[i] >= c->n_samples) { set_err(err, errlen, "marker_stats: no sample %d", (int)bg[i]); return WGBSSEG_E_ARG; }
     HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->dbg_c.ensure((size_t)n_blocks * 64 + (size_t)(n_tg + n_bg) * 4));
-    double* dout = c->dbg_c.as<double>();
+    HIP_TRY(c->mk_out.ensure((size_t)n_blocks * 64 + (size_t)(n_tg + n_bg) * 4));
+    double* dout = c->mk_out.as<double>();
     int32_t* dtg = reinterpret_cast<int32_t*>(dout + n_blocks * 8);
     int32_t* dbg = dtg + n_tg;
     HIP_TRY(hipMemcpyAsync(dtg, tg, (size_t)n_tg * 4, hipMemcpyHostToDevice, c->sA));
     HIP_TRY(hipMemcpyAsync(dbg, bg, (size_t)n_bg * 4, hipMemcpyHostToDevice, c->sA));
-    HIP_TRY(hipEventRecord(c->ev[0], c->sA));
-    hipLaunchKernelGGL(k_marker_stats, dim3((unsigned)(((n_blocks + 1) / 2 + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, c->sA, c->dbg_b.as<double>(), n_blocks,      // (two blocks per thread)
+    const AuxClock clock{c};
+    HIP_TRY(clock.begin());
+    hipLaunchKernelGGL(k_marker_stats, dim3((unsigned)(((n_blocks + 1) / 2 + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, c->sA, c->bs_out.as<double>(), n_blocks,      // (two blocks per thread)
                        dtg, (int)n_tg, dbg, (int)n_bg, dout);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[1], c->sA));
-    HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n_blocks * 64, hipMemcpyDeviceToHost, c->sA));
-    HIP_TRY(hipStreamSynchronize(c->sA));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->last_block_sums_ms = ms;
+    HIP_TRY(clock.end({{out, dout, (size_t)n_blocks * 64}}));
     return WGBSSEG_OK;
 }
 
@@ -2434,7 +2414,8 @@ int wgbsseg_sample_stats(wgbsseg_ctx* c, const int64_t* start0, const int64_t* e
     wg_stat_part* dparts = c->st_parts.as<wg_stat_part>();
     wg_sample_stat* dout = reinterpret_cast<wg_sample_stat*>(c->st_parts.as<uint8_t>() + part_bytes);
     const dim3 grid((unsigned)n_tiles, (unsigned)c->n_samples);
-    HIP_TRY(hipEventRecord(c->ev[0], c->sA));
+    const AuxClock clock{c};
+    HIP_TRY(clock.begin());
     if (c->elem == 1)
         hipLaunchKernelGGL(k_sample_stats<1>, grid, dim3(WG_ST_BLOCK), 0, c->sA, c->betas, c->pitch, dx0, dx0 + n_ranges, dx0 + 2 * n_ranges, n_ranges, n_vec, depth_at, dparts, n_tiles);
     else
@@ -2442,12 +2423,7 @@ int wgbsseg_sample_stats(wgbsseg_ctx* c, const int64_t* start0, const int64_t* e
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_sample_stats_fold, dim3((unsigned)c->n_samples), dim3(WG_ST_BLOCK), 0, c->sA, dparts, n_tiles, (uint64_t)n_sites, dout);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[1], c->sA));
-    HIP_TRY(hipMemcpyAsync(out, dout, sizeof(*out) * (size_t)c->n_samples, hipMemcpyDeviceToHost, c->sA));
-    HIP_TRY(hipStreamSynchronize(c->sA));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->last_block_sums_ms = ms;                                  // (the shared "last auxiliary kernel" clock: wgbsseg_last_block_sums_ms)
+    HIP_TRY(clock.end({{out, dout, sizeof(*out) * (size_t)c->n_samples}}));
     return WGBSSEG_OK;
 }
 
@@ -2657,28 +2633,22 @@ int wgbsseg_convert_regions(wgbsseg_ctx* c, const int64_t* chrom_lo, const int64
         }
     HIP_TRY(hipSetDevice(c->device));
     const size_t nb = (size_t)n * 8;
-    HIP_TRY(c->dbg_a.ensure(5 * nb + (size_t)n));
-    HIP_TRY(c->dbg_b.ensure(2 * nb));
-    c->table_blocks = 0;
-    char* d = c->dbg_a.as<char>();
+    HIP_TRY(c->cv_in.ensure(5 * nb + (size_t)n));
+    HIP_TRY(c->cv_out.ensure(2 * nb));
+    char* d = c->cv_in.as<char>();
     const int64_t* srcs[5] = {chrom_lo, chrom_hi, chrom_bp, start, end};
     for (int k = 0; k < 5; k++) HIP_TRY(hipMemcpyAsync(d + k * nb, srcs[k], nb, hipMemcpyHostToDevice, c->sA));
     HIP_TRY(hipMemcpyAsync(d + 5 * nb, slow, (size_t)n, hipMemcpyHostToDevice, c->sA));
-    int64_t* o = c->dbg_b.as<int64_t>();
+    int64_t* o = c->cv_out.as<int64_t>();
     const int64_t gx = (n + WG_BLOCK - 1) / WG_BLOCK;
     if (gx > 0x7fffffff) { set_err(err, errlen, "too many regions for one convert call"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipEventRecord(c->ev[0], c->sA));
+    const AuxClock clock{c};
+    HIP_TRY(clock.begin());
     hipLaunchKernelGGL(k_convert, dim3((unsigned)gx), dim3(WG_BLOCK), 0, c->sA, c->loci, reinterpret_cast<const int64_t*>(d),
                        reinterpret_cast<const int64_t*>(d + nb), reinterpret_cast<const int64_t*>(d + 2 * nb), reinterpret_cast<const int64_t*>(d + 3 * nb),
                        reinterpret_cast<const int64_t*>(d + 4 * nb), reinterpret_cast<const uint8_t*>(d + 5 * nb), n, o, o + n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(c->ev[1], c->sA));
-    HIP_TRY(hipMemcpyAsync(start_cpg, o, nb, hipMemcpyDeviceToHost, c->sA));
-    HIP_TRY(hipMemcpyAsync(end_cpg, o + n, nb, hipMemcpyDeviceToHost, c->sA));
-    HIP_TRY(hipStreamSynchronize(c->sA));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-    c->last_block_sums_ms = ms;                            // (shared "last auxiliary kernel" clock: wgbsseg_last_block_sums_ms)
+    HIP_TRY(clock.end({{start_cpg, o, nb}, {end_cpg, o + n, nb}}));
     return WGBSSEG_OK;
 }
 
