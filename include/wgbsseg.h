@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 250            /* 0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 260            /* 0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -320,6 +320,39 @@ typedef struct {
 } wgbsseg_sample_stat;
 int wgbsseg_sample_stats(wgbsseg_ctx* ctx, const int64_t* start0, const int64_t* end0, int64_t n_ranges, int32_t depth_at,
                          wgbsseg_sample_stat* out, char* err, size_t errlen);
+
+/*
+ * Pairwise 2-D histograms of the resident samples — what `wgbstools compare_betas` draws per pair of files
+ * (compare_betas.py:11-20: np.histogram2d of the two files' meth / cov over the sites both cover), in two passes because the
+ * cell edges of a pair come from the pair's own values.  Pair i = samples (a[i], b[i]); a pair may repeat, a == b is allowed.
+ * A site counts for a pair when min(cov_a, cov_b) >= min_cov; its values are fl(meth / cov), one IEEE double division
+ * (meth > cov is not checked: a ratio above 1 is a value like any other).
+ *
+ * wgbsseg_pair_ranges   out[i] = the number of such sites and the smallest and largest ratio of either sample over them
+ *                       (all four doubles 0 when n == 0): what np.histogram2d takes its range from.  Independent of launch
+ *                       geometry: min and max run on the doubles' bit patterns as integers.
+ * wgbsseg_pair_hist     edges = HOST doubles [n_pairs][2][bins + 1], axis 0 for sample b (x), axis 1 for sample a (y);
+ *                       counts = HOST uint64 [n_pairs][bins][bins], counts[i][x_cell][y_cell].  The cell of a value v is
+ *                       searchsorted(edges, v, 'right') - 1, v == the last edge falls in the last cell, v outside
+ *                       [edges[0], edges[bins]] is dropped: np.histogram2d's rule, nothing approximated.  Integer counting:
+ *                       a repeat gives the same bytes.
+ * wgbsseg_pair_hist_limits   the largest `bins` wgbsseg_pair_hist takes (what one workgroup's LDS holds beside the edges) and
+ *                       the run of sites one workgroup counts; either pointer may be NULL.
+ *
+ * Both work on uint8 rows (wgbsseg_set_betas_*) and uint16 rows (wgbsseg_set_lbetas_host); without rows: WGBSSEG_E_STATE.
+ * Refused with WGBSSEG_E_ARG and a message naming the offender: NULL pointers, n_pairs < 1, min_cov < 1 (a site without
+ * coverage has no ratio), a sample index outside the resident samples, bins < 1 or above the limit, edges that are not finite
+ * or not strictly ascending.  The kernels' HIP-event time is what wgbsseg_last_block_sums_ms returns afterwards.
+ */
+typedef struct {
+    uint64_t n;
+    double a_min, a_max, b_min, b_max;
+} wgbsseg_pair_range;
+int wgbsseg_pair_ranges(wgbsseg_ctx* ctx, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov,
+                        wgbsseg_pair_range* out, char* err, size_t errlen);
+int wgbsseg_pair_hist(wgbsseg_ctx* ctx, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov, int32_t bins,
+                      const double* edges, uint64_t* counts, char* err, size_t errlen);
+void wgbsseg_pair_hist_limits(int32_t* max_bins, int64_t* run_sites);
 
 /*
  * BED regions -> CpG index ranges: the join of `wgbstools convert -L` (convert.py:147-185 chr_thread, :133-145

@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 250          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 260          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -40,7 +40,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_homog_create', 'wgbsseg_homog_feed', 'wgbsseg_homog_finish', 'wgbsseg_homog_destroy', 'wgbsseg_homog_kernel_ms',
            'wgbsseg_debug_homog_bins',
            'wgbsseg_bimodal_create', 'wgbsseg_bimodal_feed', 'wgbsseg_bimodal_finish', 'wgbsseg_bimodal_destroy', 'wgbsseg_bimodal_kernel_ms',
-           'wgbsseg_debug_bimodal_terms', 'wgbsseg_sample_stats']
+           'wgbsseg_debug_bimodal_terms', 'wgbsseg_sample_stats',
+           'wgbsseg_pair_ranges', 'wgbsseg_pair_hist', 'wgbsseg_pair_hist_limits']
 
 
 class NativeLibraryError(RuntimeError):
@@ -64,6 +65,9 @@ class Params(C.Structure):
 SAMPLE_STAT_DTYPE = np.dtype([('n_sites', np.uint64), ('meth_sum', np.uint64), ('cov_sum', np.uint64), ('covered', np.uint64),
                               ('covered_at', np.uint64), ('orphans', np.uint64), ('ratio_lo', np.uint64), ('ratio_hi', np.uint64),
                               ('max_cov', np.uint32), ('reserved', np.uint32)])
+
+# wgbsseg_pair_range (include/wgbsseg.h): what Segmenter.pair_ranges returns one of per pair
+PAIR_RANGE_DTYPE = np.dtype([('n', np.uint64), ('a_min', np.float64), ('a_max', np.float64), ('b_min', np.float64), ('b_max', np.float64)])
 
 
 class Timings(C.Structure):
@@ -177,6 +181,12 @@ def load():
     L.wgbsseg_last_block_sums_ms.argtypes = [vp]
     L.wgbsseg_sample_stats.restype = i32
     L.wgbsseg_sample_stats.argtypes = [vp, vp, vp, i64, i32, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_pair_ranges.restype = i32
+    L.wgbsseg_pair_ranges.argtypes = [vp, vp, vp, i64, i32, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_pair_hist.restype = i32
+    L.wgbsseg_pair_hist.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_pair_hist_limits.restype = None
+    L.wgbsseg_pair_hist_limits.argtypes = [vp, vp]
     L.wgbsseg_set_site_base.restype = i32
     L.wgbsseg_set_site_base.argtypes = [vp, i64]
     L.wgbsseg_stitch_regions.restype = i32
@@ -461,6 +471,32 @@ class Segmenter:
                                             self._err, ERRLEN), self._err)
         return out
 
+    @staticmethod
+    def _pair_columns(pairs):
+        p = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        return np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+
+    def pair_ranges(self, pairs, min_cov):
+        """wgbsseg_pair_ranges: `pairs` = [(a, b), ...] resident sample indexes -> structured array [n_pairs] of PAIR_RANGE_DTYPE: the sites
+        with min(cov_a, cov_b) >= min_cov and the min / max of meth / cov of either sample over them (0 where n == 0)."""
+        a, b = self._pair_columns(pairs)
+        out = np.zeros(a.size, dtype=PAIR_RANGE_DTYPE)
+        _check(self._L.wgbsseg_pair_ranges(self._h, a.ctypes.data, b.ctypes.data, a.size, int(min_cov), out.ctypes.data, self._err, ERRLEN), self._err)
+        return out
+
+    def pair_hist(self, pairs, min_cov, bins, edges):
+        """wgbsseg_pair_hist: `edges` = float64 [n_pairs, 2, bins + 1] (axis 0: sample b = x, axis 1: sample a = y), finite and strictly
+        ascending -> uint64 [n_pairs, bins, bins], counts[pair, x_cell, y_cell] by np.histogram2d's cell rule."""
+        a, b = self._pair_columns(pairs)
+        bins = int(bins)
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+        if a.size and bins >= 1 and e.size != a.size * 2 * (bins + 1):      # (what the library cannot check; the rest is its to refuse)
+            raise ValueError('pair_hist: edges must hold [n_pairs = %d][2][bins + 1 = %d] doubles, got %d' % (a.size, bins + 1, e.size))
+        counts = np.zeros((a.size, max(bins, 0), max(bins, 0)), dtype=np.uint64)
+        _check(self._L.wgbsseg_pair_hist(self._h, a.ctypes.data, b.ctypes.data, a.size, int(min_cov), bins, e.ctypes.data, counts.ctypes.data,
+                                         self._err, ERRLEN), self._err)
+        return counts
+
     def last_block_sums_ms(self):
         return float(self._L.wgbsseg_last_block_sums_ms(self._h))
 
@@ -641,6 +677,14 @@ def debug_bimodal_terms(a, b):
     if rc != OK:
         raise SegmentorError(rc, 'debug_bimodal_terms failed')
     return out
+
+
+def pair_hist_limits():
+    """wgbsseg_pair_hist_limits -> (the largest `bins` of Segmenter.pair_hist, the sites one workgroup of its kernels takes)"""
+    L = load()
+    max_bins, run_sites = C.c_int32(0), C.c_int64(0)
+    L.wgbsseg_pair_hist_limits(C.byref(max_bins), C.byref(run_sites))
+    return int(max_bins.value), int(run_sites.value)
 
 
 def _stats_dict(stats):

@@ -33,6 +33,7 @@
 //   DP_DEBUG                 0              any                          batch    builds with -DWGBSSEG_DP_TIMING only: k_dp's timing modes (WRONG results)
 //   STITCH_THREADS           min(8,cores/2) clamped to >= 1              process  host threads of the stitching pool (1: everything on the caller)
 //   PROFILE_STITCH           0              flag                         call     host phases of the stitching on stderr
+//   PAIR_CORNERS             0              flag                         call     1: k_pair_hist counts the two corner cells in registers, not through LDS atomics (A/B, tests)
 #pragma once
 #include <climits>
 #include <cstdlib>

@@ -37,6 +37,7 @@
 #include "homog_kernels.h"
 #include "bimodal_kernels.h"
 #include "stats_kernels.h"
+#include "pair_kernels.h"
 #include "plain_dp.h"
 #include "stitch.h"
 #include "add_loci.h"
@@ -135,6 +136,7 @@ struct wgbsseg_ctx {
     DevBuf bs_plan, bs_desc, bs_out;   // wgbsseg_block_sums: the plan's tables (block_plan.h) | the streaming kernel's block descriptors | the result
     DevBuf mk_out, cv_in, cv_out;      // wgbsseg_marker_stats: the statistics and the two sample lists; wgbsseg_convert_regions: the regions' columns | their CpG ranges
     DevBuf st_ranges, st_parts;     // wgbsseg_sample_stats: the range table | the tiles' partial results and the per-sample results
+    DevBuf ph_pairs, ph_edges, ph_out;   // wgbsseg_pair_ranges / _pair_hist: the pair list (a | b) | the edges | the ranges or the counts
     std::vector<int32_t> h_stage_bounds;
     // the short division core of the narrow scoring tiles: verified on the device per pseudo count (k_check_div)
     float divs_pc = -1.0f;     // pseudo count the verdict below is for
@@ -2302,6 +2304,18 @@ int launch_block_sums_general(wgbsseg_ctx* c, const BlockSumPlan& p, const Block
     return WGBSSEG_OK;
 }
 
+// what both pair calls begin with: the checks of pair_plan.h, then the pair list on the device (a | b)
+int pair_list_up(wgbsseg_ctx* c, const char* who, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov, char* err, size_t errlen)
+{
+    std::string msg;
+    if (!wg_pair_check_list(who, a, b, n_pairs, min_cov, c->n_samples, c->n_total, msg)) { set_err(err, errlen, "%s", msg.c_str()); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->ph_pairs.ensure((size_t)n_pairs * 8));
+    HIP_TRY(hipMemcpyAsync(c->ph_pairs.p, a, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->sA));
+    HIP_TRY(hipMemcpyAsync(c->ph_pairs.as<int32_t>() + n_pairs, b, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->sA));
+    return WGBSSEG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2425,6 +2439,74 @@ int wgbsseg_sample_stats(wgbsseg_ctx* c, const int64_t* start0, const int64_t* e
     HIP_TRY(hipGetLastError());
     HIP_TRY(clock.end({{out, dout, sizeof(*out) * (size_t)c->n_samples}}));
     return WGBSSEG_OK;
+}
+
+static_assert(sizeof(wgbsseg_pair_range) == sizeof(wg_pair_range) && sizeof(wg_pair_range) == 40, "wgbsseg_pair_range is the kernels' wg_pair_range");
+
+int wgbsseg_pair_ranges(wgbsseg_ctx* c, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov,
+                        wgbsseg_pair_range* out, char* err, size_t errlen)
+{
+    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
+    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
+    if (!out) { set_err(err, errlen, "pair_ranges: out is NULL"); return WGBSSEG_E_ARG; }
+    const int rc = pair_list_up(c, "pair_ranges", a, b, n_pairs, min_cov, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    const wgbsseg_pair_range start = {0, 0, 0, 0, 0};
+    std::vector<wg_pair_range> init((size_t)n_pairs, wg_pair_range{0, ~0ull, 0, ~0ull, 0});
+    HIP_TRY(c->ph_out.ensure(init.size() * sizeof(wg_pair_range)));
+    wg_pair_range* dout = c->ph_out.as<wg_pair_range>();
+    HIP_TRY(hipMemcpyAsync(dout, init.data(), init.size() * sizeof(wg_pair_range), hipMemcpyHostToDevice, c->sA));
+    const int32_t* dpa = c->ph_pairs.as<int32_t>();
+    const dim3 grid((unsigned)((c->n_total + WG_PH_RUN - 1) / WG_PH_RUN * n_pairs));
+    const AuxClock clock{c};
+    HIP_TRY(clock.begin());
+    if (c->elem == 1)
+        hipLaunchKernelGGL(k_pair_ranges<1>, grid, dim3(WG_PH_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, dpa, dpa + n_pairs, (int32_t)n_pairs, min_cov, dout);
+    else
+        hipLaunchKernelGGL(k_pair_ranges<2>, grid, dim3(WG_PH_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, dpa, dpa + n_pairs, (int32_t)n_pairs, min_cov, dout);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(clock.end({{out, dout, sizeof(*out) * (size_t)n_pairs}}));
+    for (int64_t i = 0; i < n_pairs; i++) if (out[i].n == 0) out[i] = start;      // (the bit patterns min and max began with are no doubles to hand out)
+    return WGBSSEG_OK;
+}
+
+int wgbsseg_pair_hist(wgbsseg_ctx* c, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov, int32_t bins,
+                      const double* edges, uint64_t* counts, char* err, size_t errlen)
+{
+    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
+    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
+    if (!counts) { set_err(err, errlen, "pair_hist: counts is NULL"); return WGBSSEG_E_ARG; }
+    std::string msg;
+    if (!wg_pair_check_bins(bins, msg)) { set_err(err, errlen, "%s", msg.c_str()); return WGBSSEG_E_ARG; }
+    if (n_pairs >= 1 && !wg_pair_check_edges(edges, n_pairs, bins, msg)) { set_err(err, errlen, "%s", msg.c_str()); return WGBSSEG_E_ARG; }
+    const int rc = pair_list_up(c, "pair_hist", a, b, n_pairs, min_cov, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    const size_t ebytes = (size_t)n_pairs * 2 * (size_t)(bins + 1) * 8, cbytes = (size_t)n_pairs * (size_t)bins * (size_t)bins * 8;
+    HIP_TRY(c->ph_edges.ensure(ebytes));
+    HIP_TRY(c->ph_out.ensure(cbytes));
+    HIP_TRY(hipMemcpyAsync(c->ph_edges.p, edges, ebytes, hipMemcpyHostToDevice, c->sA));
+    unsigned long long* dcounts = c->ph_out.as<unsigned long long>();
+    const int32_t* dpa = c->ph_pairs.as<int32_t>();
+    const dim3 grid((unsigned)((c->n_total + WG_PH_RUN - 1) / WG_PH_RUN * n_pairs));
+    const size_t lds = (size_t)wg_ph_lds_bytes(bins);
+    const bool corners = env_flag("WGBSSEG_PAIR_CORNERS", false);     // (read per call: env.h; off: measured 5 % slower on the benchmark rows)
+    const AuxClock clock{c};
+    HIP_TRY(clock.begin());
+    HIP_TRY(hipMemsetAsync(dcounts, 0, cbytes, c->sA));
+#define WG_LAUNCH_PH(E, C) hipLaunchKernelGGL((k_pair_hist<E, C>), grid, dim3(WG_PH_BLOCK), lds, c->sA, c->betas, c->pitch, c->n_total, dpa, dpa + n_pairs, \
+                                              (int32_t)n_pairs, min_cov, bins, c->ph_edges.as<const double>(), dcounts)
+    if (c->elem == 1) { if (corners) WG_LAUNCH_PH(1, true); else WG_LAUNCH_PH(1, false); }
+    else { if (corners) WG_LAUNCH_PH(2, true); else WG_LAUNCH_PH(2, false); }
+#undef WG_LAUNCH_PH
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(clock.end({{counts, dcounts, cbytes}}));
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_pair_hist_limits(int32_t* max_bins, int64_t* run_sites)
+{
+    if (max_bins) *max_bins = WG_PH_MAX_BINS;
+    if (run_sites) *run_sites = WG_PH_RUN;
 }
 
 int wgbsseg_add_loci(const uint32_t* loci, int64_t n_sites, const int64_t* chrom_cum, const char* const* chrom_names,
