@@ -200,7 +200,8 @@ int wgbsseg_set_site_base(wgbsseg_ctx* ctx, int64_t site_base);
 typedef struct wgbsseg_group wgbsseg_group;
 /* The planner on its own (host only, no device): own_lo/own_hi = 0-based sites [lo, hi) of the chunks given to each of the
  * n_shares shares (hi == lo: none), win_* = those +- halo.  The multi-process driver (one rank per GPU) cuts the genome
- * with it so that every rank computes the same shares. */
+ * with it so that every rank computes the same shares.  (The planner, the routing of a batch and the rule of the streaming upload:
+ * csrc/share_plan.h.) */
 int wgbsseg_plan_shares(const uint32_t* loci, int64_t n_sites, const int64_t* region_start, const int64_t* region_end,
                         int64_t n_regions, int64_t chunk_size, const wgbsseg_params* params, int32_t n_shares, int64_t halo,
                         int64_t* own_lo, int64_t* own_hi, int64_t* win_lo, int64_t* win_hi, int64_t* share_chunks,

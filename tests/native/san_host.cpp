@@ -1,5 +1,5 @@
 // Sanitizer harness for the host-side C++ of the library (TEST INFRASTRUCTURE): csrc/block_plan.h (the plan of a block reduction),
-// csrc/stitch.h (chunk grid, junction rehearsal, pairwise trees on the thread pool, flattening) and csrc/add_loci.h (BED rows), driven by a toy chunk engine that is a pure
+// csrc/share_plan.h (the plan of a share group, its router and the rule of its streaming upload), csrc/stitch.h (chunk grid, junction rehearsal, pairwise trees on the thread pool, flattening) and csrc/add_loci.h (BED rows), driven by a toy chunk engine that is a pure
 // function of the site range — as the real DP is — so that junction patches share borders with their chunks or, where the toy
 // makes them disagree, force the patch to double.  Built by tests/test_sanitizers_cpu.py three times (plain, ASan + UBSan,
 // TSan); every build must print the same checksum lines.
@@ -21,6 +21,7 @@
 #include "add_loci.h"
 #include "table_io.h"
 #include "block_plan.h"
+#include "share_plan.h"
 
 static uint64_t mix(uint64_t x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33; return x; }
 
@@ -39,12 +40,20 @@ static void toy_borders(int64_t a, int64_t b, int fuzzy, std::vector<int32_t>& o
     out.push_back((int32_t)(b - a));
 }
 
+// the regions of a toy world (1-based half-open, one behind the other); returns one past the last site
+static int64_t world_regions(int n_regions, int64_t region_len, std::vector<int64_t>& rs, std::vector<int64_t>& re)
+{
+    rs.assign((size_t)n_regions, 0); re.assign((size_t)n_regions, 0);
+    int64_t pos = 1;
+    for (int r = 0; r < n_regions; r++) { rs[(size_t)r] = pos; pos += region_len + 37 * r; re[(size_t)r] = pos; }
+    return pos;
+}
+
 static uint64_t run_world(int n_regions, int64_t region_len, int64_t chunk, int fuzzy, bool speculate, std::vector<int64_t>& starts_out,
                           std::vector<int64_t>& ends_out)
 {
-    std::vector<int64_t> rs((size_t)n_regions), re((size_t)n_regions);
-    int64_t pos = 1;
-    for (int r = 0; r < n_regions; r++) { rs[(size_t)r] = pos; pos += region_len + 37 * r; re[(size_t)r] = pos; }
+    std::vector<int64_t> rs, re;
+    const int64_t pos = world_regions(n_regions, region_len, rs, re);
     int64_t n_batches = 0;
     wgstitch::BatchFn fn = [&](const std::vector<wgstitch::Sites>& todo, wgstitch::BatchResult& res, std::string&) -> int {
         res.ptr.resize(todo.size()); res.cnt.resize(todo.size());
@@ -133,11 +142,180 @@ static void block_plan_line()
     printf("block_plan: %zu tables of up to %zu blocks, %d plans, %d refusals, checksum %016llx\n", tables.size(), nest.size(), n_ok, n_refused, (unsigned long long)h);
 }
 
+// The rule of wgshare::route, stated by scanning: the last share that begins at or before `lo`, stepping back over shares that own nothing; that
+// share, the next, the one before - the first of them whose window is not empty and holds [lo, hi).
+static int route_by_scan(const std::vector<wgshare::Span>& sp, int64_t lo, int64_t hi)
+{
+    int d = 0;
+    for (int q = 0; q < (int)sp.size(); q++) if (sp[(size_t)q].own_lo <= lo) d = q;
+    while (d > 0 && sp[(size_t)d].own_hi == sp[(size_t)d].own_lo) d--;
+    const int cand[3] = {d, d + 1, d - 1};
+    for (int q : cand) {
+        if (q < 0 || q >= (int)sp.size()) continue;
+        const wgshare::Span& s = sp[(size_t)q];
+        if (s.win_hi > s.win_lo && s.win_lo <= lo && hi <= s.win_hi) return q;
+    }
+    return -1;
+}
+
+static const wgshare::Span& same_span(const wgshare::Span& s) { return s; }
+
+// wgshare::route on span sets made by hand, for the steps of the rule that no plan over contiguous regions reaches; the answers are written down here:
+// the share whose window holds the range, the owner of its first site before its neighbours.  Returns the number of wrong answers.
+static long route_by_hand(long& n_cases)
+{
+    typedef std::vector<wgshare::Span> Spans;                   // {own_lo, own_hi, win_lo, win_hi, chunks, work}
+    // two shares that own nothing between two regions with a gap: sites in the gap "belong" to the last of them; the rule steps back over both
+    const Spans gap{{0, 100, 0, 150, 1, 1}, {100, 100, 0, 0, 0, 0}, {100, 100, 0, 0, 0, 0}, {300, 400, 250, 450, 1, 1}};
+    // a short middle share whose neighbours' windows reach further than its own (hand-made: a plan's windows do not nest like this)
+    const Spans nest{{0, 1000, 0, 3000, 1, 1}, {1000, 1100, 896, 1200, 1, 1}, {1100, 2000, 1024, 2100, 1, 1}};
+    // the first share owns nothing and the regions begin at site 5: sites before it fall to share 0, whose empty window [0, 0) must hold nothing
+    const Spans lead{{5, 5, 0, 0, 0, 0}, {5, 100, 0, 150, 1, 1}};
+    const struct { const Spans* sp; int64_t lo, hi; int want; } cases[] = {
+        {&gap, 120, 140, 0}, {&gap, 100, 150, 0}, {&gap, 120, 151, -1}, {&gap, 260, 299, -1}, {&gap, 300, 310, 3}, {&gap, 90, 100, 0}, {&gap, 320, 451, -1},
+        {&nest, 1050, 1150, 1}, {&nest, 1050, 1300, 2}, {&nest, 1000, 1300, 0}, {&nest, 1000, 3001, -1}, {&nest, 900, 1150, 0}, {&nest, 1100, 2100, 2}, {&nest, 1100, 2101, -1},
+        {&lead, 0, 0, 1}, {&lead, 2, 50, 1}, {&lead, 5, 150, 1}, {&lead, 5, 151, -1},
+    };
+    long wrong = 0;
+    for (auto& c : cases) { n_cases++; wrong += wgshare::route(*c.sp, same_span, c.lo, c.hi) != c.want; }
+    return wrong;
+}
+
+// The take rule walked the way the polling loop walks it, over every number of resident sites from none to the whole window: wgshare::take_upto
+// against the rule stated by scanning - nothing while the next item's last site is not resident or fewer than min_take sites behind its first site
+// are, else every item up to the first whose last site is not resident.  Every item is taken once, in order of its last site, never before that
+// site is resident.  Returns the number of violations.
+static long walk_take_rule(const std::vector<wgshare::Range>& items, const wgshare::Span& s, int64_t mt, long& n_subs, uint64_t& h)
+{
+    long bad = 0;
+    std::vector<int> taken(items.size(), 0);
+    size_t pos = 0;
+    for (int64_t R = s.win_lo; R <= s.win_hi && pos < items.size(); R++)
+        for (;;) {                                                  // (after a sub-batch the loop asks again, maybe at the same count)
+            const size_t end = wgshare::take_upto(items, pos, R, mt);
+            size_t want = pos;
+            if (items[pos].hi <= R && R - items[pos].lo >= mt) while (want < items.size() && items[want].hi <= R) want++;
+            bad += end != want;
+            if (end <= pos || end > items.size()) { bad += end != pos; break; }
+            for (size_t k = pos; k < end; k++) { taken[k]++; bad += items[k].hi > R || R - items[pos].lo < mt || (k && items[k].hi < items[k - 1].hi); }
+            n_subs++; h = (h ^ (uint64_t)end) * 1099511628211ULL; h = (h ^ (uint64_t)R) * 1099511628211ULL;
+            pos = end;
+            if (pos == items.size()) break;
+        }
+    // what min_take still holds back when every site is resident goes when the uploader has finished: the caller's step, not the rule's
+    for (size_t k = 0; k < items.size(); k++) bad += taken[k] != (k < pos ? 1 : 0);
+    for (size_t k = pos; k < items.size(); k++) bad += !(s.win_hi - items[pos].lo < mt);
+    return bad;
+}
+
+// The plans of the share groups (share_plan.h) over the toy worlds of main(), with positions that restart at every region: 1 to 64 shares (more
+// than the 62, 54, 13 and 3 chunks of the worlds), even and weighted (one weight zero), a halo of 6000 sites and one of 10.  Every plan must
+// tile the chunk grid; every chunk and every junction range of +-50 and +-5000 sites around a share boundary is routed and compared with the rule
+// stated by scanning (a chunk: with its owner); the router's hand-made cases; the refusals; and the take rule.  One line.
+static void share_plan_line()
+{
+    const struct { int n_regions; int64_t len, chunk; } worlds[4] = {{7, 40000, 5000}, {5, 30000, 3000}, {1, 9000, 700}, {3, 500, 60000}};
+    const wgbsseg_params P = {15.0f, 50, 300};
+    uint64_t h = 1469598103934665603ULL;
+    auto fold = [&](uint64_t v) { h = (h ^ v) * 1099511628211ULL; };
+    long n_plans = 0, n_chunks_routed = 0, n_routed = 0, n_unroutable = 0, n_refused = 0, bad = 0, n_idle = 0, n_hand = 0;
+    bad += route_by_hand(n_hand);
+    std::vector<wgshare::Span> kept;                           // world 0 over 3 shares at the large halo: the take rule's
+    std::vector<wgshare::Range> kept_chunks;
+    for (int w = 0; w < 4; w++) {
+        std::vector<int64_t> rs, re;
+        const int64_t n_sites = world_regions(worlds[w].n_regions, worlds[w].len, rs, re) - 1;
+        std::vector<uint32_t> loci((size_t)n_sites);
+        for (int r = 0; r < worlds[w].n_regions; r++)
+            for (int64_t i = rs[(size_t)r] - 1; i < re[(size_t)r] - 1; i++) loci[(size_t)i] = (uint32_t)(100 + 13 * (i - rs[(size_t)r] + 1) + (int64_t)(mix((uint64_t)i) % 7));
+        std::vector<wgshare::Range> chunks;
+        for (int r = 0; r < worlds[w].n_regions; r++)
+            for (int64_t s0 = rs[(size_t)r]; s0 < re[(size_t)r]; s0 += worlds[w].chunk) chunks.push_back({s0 - 1, std::min(s0 + worlds[w].chunk, re[(size_t)r]) - 1});
+        for (int G : {1, 2, 3, 5, 8, 64})
+            for (int weighted = 0; weighted < 2; weighted++)
+                for (int64_t halo : {(int64_t)6000, (int64_t)10}) {
+                    std::vector<double> wt((size_t)G);
+                    for (int d = 0; d < G; d++) wt[(size_t)d] = d % 4 == 1 ? 0.0 : 0.5 + (double)(d % 3);
+                    if (G == 1) wt[0] = 1.0;
+                    std::vector<wgshare::Span> sp;
+                    std::string msg;
+                    const int rc = wgshare::plan_shares(loci.data(), n_sites, rs.data(), re.data(), worlds[w].n_regions, worlds[w].chunk, &P, G, weighted ? wt.data() : nullptr, halo, sp, msg);
+                    if (rc != WGBSSEG_OK || (int)sp.size() != G) { bad++; continue; }
+                    n_plans++;
+                    // the shares' runs tile the grid, in order; windows: the run +- halo inside the sites, the lower edge on a multiple of 128
+                    size_t c = 0;
+                    for (int d = 0; d < G; d++) {
+                        const wgshare::Span& s = sp[(size_t)d];
+                        fold((uint64_t)s.own_lo); fold((uint64_t)s.own_hi); fold((uint64_t)s.win_lo); fold((uint64_t)s.win_hi); fold((uint64_t)s.chunks); fold((uint64_t)s.work);
+                        if (!s.chunks) { n_idle++; bad += s.own_lo != s.own_hi || s.win_lo != 0 || s.win_hi != 0; continue; }
+                        bad += c + (size_t)s.chunks > chunks.size() || s.own_lo != chunks[c].lo || s.own_hi != chunks[c + (size_t)s.chunks - 1].hi;
+                        bad += s.win_lo % 128 != 0 || s.win_lo > std::max<int64_t>(0, s.own_lo - halo) || s.win_lo + 128 <= std::max<int64_t>(0, s.own_lo - halo);
+                        bad += s.win_hi != std::min(n_sites, s.own_hi + halo);
+                        c += (size_t)s.chunks;
+                    }
+                    bad += c != chunks.size();
+                    auto route = [&](int64_t lo, int64_t hi, int owner) {
+                        const int got = wgshare::route(sp, same_span, lo, hi), want = route_by_scan(sp, lo, hi);
+                        bad += got != want || (owner >= 0 && got != owner);
+                        if (got >= 0) bad += !(sp[(size_t)got].win_lo <= lo && hi <= sp[(size_t)got].win_hi);
+                        else for (auto& o : sp) bad += o.own_lo <= lo && lo < o.own_hi && o.win_lo <= lo && hi <= o.win_hi;      // (refused: the owner does not hold it)
+                        if (owner >= 0) n_chunks_routed++;
+                        else (got >= 0 ? n_routed : n_unroutable)++;
+                        fold((uint64_t)(int64_t)got);
+                    };
+                    c = 0;
+                    for (int d = 0; d < G; d++)
+                        for (int64_t k = 0; k < sp[(size_t)d].chunks; k++, c++) route(chunks[c].lo, chunks[c].hi, d);
+                    for (int d = 0; d < G; d++) {
+                        const int64_t b = sp[(size_t)d].own_hi;
+                        if (!sp[(size_t)d].chunks || b == chunks.back().hi) continue;
+                        for (int64_t reach : {(int64_t)50, (int64_t)5000}) route(std::max<int64_t>(0, b - reach), std::min(n_sites, b + reach), -1);
+                    }
+                    if (w == 0 && G == 3 && !weighted && halo == 6000) { kept = sp; kept_chunks = chunks; }
+                }
+        if (w == 0) {                                              // the refusals: arguments, max_bp 0, an empty region, regions out of order, a negative weight, weights all zero
+            const wgbsseg_params P0 = {15.0f, 50, 0};
+            const int64_t es[2] = {1, 500}, ee[2] = {500, 500}, ds[2] = {500, 1}, de[2] = {900, 500};
+            const double neg[2] = {1.0, -1.0}, zero[2] = {0.0, 0.0};
+            std::vector<wgshare::Span> sp;
+            std::string msg;
+            for (int k = 0; k < 6; k++) {
+                const int rc = k == 0 ? wgshare::plan_shares(loci.data(), n_sites, rs.data(), re.data(), worlds[w].n_regions, worlds[w].chunk, &P, 0, nullptr, -1, sp, msg)
+                             : k == 1 ? wgshare::plan_shares(loci.data(), n_sites, rs.data(), re.data(), worlds[w].n_regions, worlds[w].chunk, &P0, 2, nullptr, -1, sp, msg)
+                             : k == 2 ? wgshare::plan_shares(loci.data(), n_sites, es, ee, 2, worlds[w].chunk, &P, 2, nullptr, -1, sp, msg)
+                             : k == 3 ? wgshare::plan_shares(loci.data(), n_sites, ds, de, 2, worlds[w].chunk, &P, 2, nullptr, -1, sp, msg)
+                             : wgshare::plan_shares(loci.data(), n_sites, rs.data(), re.data(), worlds[w].n_regions, worlds[w].chunk, &P, 2, k == 4 ? neg : zero, -1, sp, msg);
+                n_refused += rc == WGBSSEG_E_ARG && !msg.empty();
+                for (char ch : msg) fold((uint64_t)(unsigned char)ch);
+            }
+        }
+    }
+    // the take rule: the middle share's chunks, the ranges around its two boundaries and a short patch that ends where each chunk ends (ties), in
+    // order of their last site (ties as they came); with the group's min_take, which holds the first sub-batch back long after its items are
+    // resident, and with min_take 1 and 700, where residency is what binds
+    long n_items = 0, n_subs = 0;
+    if (kept.size() == 3 && kept[1].chunks) {
+        const wgshare::Span& s = kept[1];
+        std::vector<wgshare::Range> items;
+        for (auto& c : kept_chunks) if (s.own_lo <= c.lo && c.hi <= s.own_hi) { items.push_back(c); items.push_back({c.hi - 60, c.hi}); }
+        for (int64_t b : {s.own_lo, s.own_hi}) for (int64_t reach : {(int64_t)50, (int64_t)5000}) items.push_back({b - reach, b + reach});
+        std::stable_sort(items.begin(), items.end(), [](const wgshare::Range& a, const wgshare::Range& b) { return a.hi < b.hi; });
+        const int64_t mt = wgshare::min_take(5000, s);
+        bad += mt != std::max<int64_t>(20000, (s.win_hi - s.win_lo) / 5);
+        for (int64_t m : {mt, (int64_t)1, (int64_t)700}) bad += walk_take_rule(items, s, m, n_subs, h);
+        n_items = (long)items.size();
+    } else bad++;
+    printf("share_plan: %ld plans, %ld idle shares, %ld chunks routed to their owners, %ld junction ranges routed, %ld unroutable, %ld routes by hand, %ld refusals, "
+           "take rule: %ld items in %ld sub-batches of 3 walks, %ld mismatches, checksum %016llx\n",
+           n_plans, n_idle, n_chunks_routed, n_routed, n_unroutable, n_hand, n_refused, n_items, n_subs, bad, (unsigned long long)h);
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 3) { fprintf(stderr, "usage: san_host <threads> <out.bed>\n"); return 2; }
     setenv("WGBSSEG_STITCH_THREADS", argv[1], 1);
     block_plan_line();
+    share_plan_line();
     std::vector<int64_t> s, e;
     for (int rep = 0; rep < 3; rep++) {                                      // the pool is reused across calls
         std::vector<int64_t> s1, e1;

@@ -1,10 +1,11 @@
 """Sanitizer builds of the host-side native code (the reference has none; its `segmentor` has a real UB at max_bp == 0):
-csrc/block_plan.h (the plan of a block reduction), csrc/stitch.h + csrc/add_loci.h (chunk grid, junction stitching on the thread pool, BED rows)
+csrc/block_plan.h (the plan of a block reduction), csrc/share_plan.h (the plan of a share group, its router, its take rule), csrc/stitch.h + csrc/add_loci.h (chunk grid, junction stitching on the thread pool, BED rows)
 and the oracle's C restatement of the
 chunk DP, each compiled plain, with AddressSanitizer + UndefinedBehaviorSanitizer, and with ThreadSanitizer, and run on
 deterministic toy inputs: every build must finish clean and print the same lines."""
 import os.path as op
 import platform
+import re
 import shutil
 import subprocess
 
@@ -51,6 +52,21 @@ def test_stitching_and_bed_rows_under_sanitizers(tmp_path):
     assert 'checksum' in ref[0] and ref[0].count('world') == 15 and 'rc 0' in ref[0] and len(ref[1]) > 5000
     plan_line = [l for l in ref[0].splitlines() if l.startswith('block_plan: ')]
     assert len(plan_line) == 1 and ', 14 plans, 10 refusals, checksum ' in plan_line[0]          # (identical across the builds: the loop below compares whole outputs)
+    share_line = [l for l in ref[0].splitlines() if l.startswith('share_plan: ')]
+    assert len(share_line) == 1
+    m = re.match(r'share_plan: (\d+) plans, (\d+) idle shares, (\d+) chunks routed to their owners, (\d+) junction ranges routed, (\d+) unroutable, (\d+) routes by hand, '
+                 r'(\d+) refusals, take rule: (\d+) items in (\d+) sub-batches of 3 walks, (\d+) mismatches, checksum ', share_line[0])
+    plans, idle, chunks, routed, unroutable, by_hand, refusals, items, subs, mismatches = (int(x) for x in m.groups())
+    # the program's worlds: (regions, sites of the first region - region r has 37 r more -, chunk); each planned for 6 share counts, even | weighted, 2 halos
+    worlds, counts = [(7, 40000, 5000), (5, 30000, 3000), (1, 9000, 700), (3, 500, 60000)], (1, 2, 3, 5, 8, 64)
+    n_chunks = sum(-(-(n + 37 * r) // c) for k, n, c in worlds for r in range(k))
+    assert plans == len(worlds) * len(counts) * 4 and refusals == 6 and by_hand == 18 and mismatches == 0
+    assert chunks == n_chunks * len(counts) * 4                    # every chunk of every plan, each routed to the share that owns it
+    # two ranges (+-50, +-5000 sites) at every boundary between two shares that own chunks
+    assert routed + unroutable == 2 * (len(worlds) * 4 * sum(counts) - idle - plans)
+    # 64 shares over at most 62 chunks and the zero weights leave shares idle; the +-50 ranges outgrow the halo of 10; the middle share of three takes
+    # two items per chunk and four junction ranges, in more than one sub-batch per walk and (min_take 1: one per distinct last site) fewer than items per walk
+    assert idle >= len(worlds) * 4 * 2 and routed > 0 and unroutable > 0 and items > 4 and items % 2 == 0 and 3 < subs < 3 * items
     assert 'sitetable: ' in ref[0] and 'mismatches 0, concurrent misses 0' in ref[0]
     assert 'parse_blocks: rc 0 rows 40000 na 413' in ref[0] and 'parse_blocks on a float field: rc 1' in ref[0]
     assert ref[0].count('write_table pass') == 2 and 'DIFFERS' not in ref[0] and 'write_bedgraph: rc 0' in ref[0]

@@ -32,6 +32,7 @@
 #include "owners.h"
 #include "seg_kernels.h"
 #include "block_plan.h"
+#include "share_plan.h"
 #include "block_kernels.h"
 #include "pat_kernels.h"
 #include "homog_kernels.h"
@@ -1772,17 +1773,9 @@ int wgbsseg_first_batch_items(const int64_t* region_start, const int64_t* region
 // from the loci); a share keeps only its own window of the beta bytes.  Every batch of the stitching loop is routed
 // item by item to the share that holds it and runs on one host thread per share; the reference's pairwise tree
 // then runs ONCE, on the host, over all shares' results — the answer does not depend on the number of shares.
+// The plan, the routing rule and the rule of the streaming upload are share_plan.h's (no HIP there).
 // ------------------------------------------------------------------------------------------------------------
 struct wgbsseg_group {
-    std::vector<wgbsseg_ctx*> shares;
-    std::vector<int64_t> own_lo, own_hi;     // 0-based sites [lo, hi) of the chunks a share owns (hi == lo: none)
-    std::vector<int64_t> win_lo, win_hi;     // resident window of the share: owned sites +- halo, inside [0, n_sites)
-    std::vector<int64_t> rs, re;             // the planned regions (1-based half-open)
-    std::vector<int64_t> share_chunks, share_work;
-    int64_t chunk_size = 0, n_sites = 0, halo = 0;
-    wgbsseg_params P = {};
-    bool planned = false;
-    std::vector<char> loaded;
     // streaming upload (wgbsseg_group_load_host_async): one uploader per share; `ready` = sites of the share's window that are
     // resident for EVERY sample, counted from the window's first site
     struct Loader {
@@ -1791,35 +1784,155 @@ struct wgbsseg_group {
         std::atomic<int> finished{0};
         int rc = WGBSSEG_OK;
         std::string msg;
+        void join() { if (th.joinable()) th.join(); }
+        ~Loader() { join(); }
     };
-    std::vector<std::unique_ptr<Loader>> loaders;
+    struct CtxDeleter { void operator()(wgbsseg_ctx* c) const { wgbsseg_destroy(c); } };
+    struct Share {
+        std::unique_ptr<wgbsseg_ctx, CtxDeleter> ctx;   // (declared first: goes last.  The uploader's thread holds this pointer raw; ~Loader joins it before the context goes)
+        wgshare::Span span;
+        bool loaded = false;
+        std::unique_ptr<Loader> loader;
+    };
+    std::vector<Share> shares;
+    std::vector<int64_t> rs, re;             // the planned regions (1-based half-open)
+    int64_t chunk_size = 0, n_sites = 0, halo = 0;
+    wgbsseg_params P = {};
+    bool planned = false;
     bool streaming = false;
 };
 
 namespace {
 
-// number of scored blocks of a chunk: sum over its sites k of F_k (segmentor.cpp:111-117), by two pointers
-int64_t chunk_work(const uint32_t* loci, int64_t lo, int64_t hi, uint32_t max_cpg, uint32_t max_bp)
+// f(share, msg) -> code for every share of `which` (ascending); the first failure comes back as "share d: msg" with that share's code.
+// pooled: the work-stealing pool, at most 64 threads (plan, load).  Else one thread per share, inline when there is only one, never
+// capped (a batch): a share may block while it waits for its uploader, and a capped pool would line the shares behind it up.
+template <class F>
+int for_shares(const std::vector<int>& which, bool pooled, F f, std::string& msg)
 {
-    int64_t w = 0, e = lo;
-    for (int64_t k = lo; k < hi; k++) {
-        if (e < k + 1) e = k + 1;
-        while (e < hi && e - k < (int64_t)max_cpg && loci[e] >= loci[k] && (uint64_t)loci[e] - loci[k] <= max_bp) e++;
-        w += e - k;
+    std::vector<int> rcs(which.size(), WGBSSEG_OK);
+    std::vector<std::string> msgs(which.size());
+    auto one = [&](int64_t i) { rcs[(size_t)i] = f(which[(size_t)i], msgs[(size_t)i]); };
+    if (pooled) wgshare::parallel_for((int64_t)which.size(), 64, one);
+    else if (which.size() == 1) one(0);
+    else {
+        std::vector<std::thread> th;
+        for (size_t i = 0; i < which.size(); i++) th.emplace_back(one, (int64_t)i);
+        for (auto& x : th) x.join();
     }
-    return w;
+    for (size_t i = 0; i < which.size(); i++)
+        if (rcs[i] != WGBSSEG_OK) { msg = "share " + std::to_string(which[i]) + ": " + msgs[i]; return rcs[i]; }
+    return WGBSSEG_OK;
 }
 
-template <class F>
-void parallel_for(int64_t n, int max_threads, F f)
+std::vector<int> resident_shares(const wgbsseg_group* g)
 {
-    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(max_threads, (int64_t)std::thread::hardware_concurrency()), n));
-    if (T <= 1) { for (int64_t i = 0; i < n; i++) f(i); return; }
-    std::atomic<int64_t> next(0);
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; t++) th.emplace_back([&]() { for (int64_t i; (i = next.fetch_add(1)) < n;) f(i); });
-    for (auto& x : th) x.join();
+    std::vector<int> which;
+    for (size_t d = 0; d < g->shares.size(); d++) if (g->shares[d].span.resident()) which.push_back((int)d);
+    return which;
 }
+
+void scatter_spans(const std::vector<wgshare::Span>& spans, int64_t* own_lo, int64_t* own_hi, int64_t* win_lo, int64_t* win_hi, int64_t* share_chunks, int64_t* share_work)
+{
+    for (size_t d = 0; d < spans.size(); d++) {
+        if (own_lo) own_lo[d] = spans[d].own_lo;
+        if (own_hi) own_hi[d] = spans[d].own_hi;
+        if (win_lo) win_lo[d] = spans[d].win_lo;
+        if (win_hi) win_hi[d] = spans[d].win_hi;
+        if (share_chunks) share_chunks[d] = spans[d].chunks;
+        if (share_work) share_work[d] = spans[d].work;
+    }
+}
+
+// What one call of wgbsseg_group_segment_region_range keeps per share
+struct ShareCall {
+    bool ran = false;              // the share's timings: reset on its first batch of the FIRST slice of the regions, summed after
+    int64_t slot_next = 0;         // page-locked result buffers of the share used by this call so far
+    std::vector<size_t> items;                          // the batch under way: its items for this share (indices into todo),
+    std::vector<std::unique_ptr<int32_t[]>> owned;      // the fallback buffers they came back in
+};
+
+// One batch of the stitcher over a group: `todo`, where its lists go, and the call's state
+struct GroupBatch {
+    wgbsseg_group* g;
+    const std::vector<wgstitch::Sites>& todo;
+    wgstitch::BatchResult& res;
+    std::vector<ShareCall>& calls;
+
+    // every item to the share that holds it (wgshare::route); none does: a refusal, not a wrong answer
+    int route(std::string& msg)
+    {
+        for (auto& c : calls) c.items.clear();
+        for (size_t i = 0; i < todo.size(); i++) {
+            const int64_t lo = todo[i].first - 1, hi = todo[i].second - 1;
+            if (hi - lo > 0x7fffffff) { msg = "chunk too long"; return WGBSSEG_E_ARG; }
+            const int pick = wgshare::route(g->shares, [](const wgbsseg_group::Share& s) -> const wgshare::Span& { return s.span; }, lo, hi);
+            if (pick < 0) {
+                msg = "sites [" + std::to_string(lo + 1) + ", " + std::to_string(hi + 1) + ") are not resident on any single share (halo " +
+                      std::to_string(g->halo) + " sites): a junction patch outgrew it; rerun on one share";
+                return WGBSSEG_E_STATE;
+            }
+            calls[(size_t)pick].items.push_back(i);
+        }
+        res.ptr.assign(todo.size(), nullptr);
+        res.cnt.assign(todo.size(), 0);
+        return WGBSSEG_OK;
+    }
+
+    // one launch sequence of share d over the items `it`; their lists into res
+    int run_items(int d, const std::vector<size_t>& it, std::string& msg)
+    {
+        auto& sh = g->shares[(size_t)d];
+        ShareCall& call = calls[(size_t)d];
+        std::vector<int64_t> st0(it.size()), off;
+        std::vector<int32_t> ln(it.size());
+        for (size_t k = 0; k < it.size(); k++) {
+            st0[k] = todo[it[k]].first - 1 - sh.span.win_lo;
+            ln[k] = (int32_t)(todo[it[k]].second - todo[it[k]].first);
+        }
+        const int32_t* flat = nullptr;
+        std::unique_ptr<int32_t[]> own;
+        const int rc = run_ctx_batch(sh.ctx.get(), st0, ln, &g->P, call.slot_next++, call.ran, flat, off, own, msg);
+        if (rc != WGBSSEG_OK) return rc;
+        if (own) call.owned.push_back(std::move(own));
+        call.ran = true;
+        for (size_t k = 0; k < it.size(); k++) { res.ptr[it[k]] = flat + off[k]; res.cnt[it[k]] = off[k + 1] - off[k]; }
+        return WGBSSEG_OK;
+    }
+
+    // the share's bytes are still arriving (front to back): segment what is resident while the rest is on its way —
+    // items in order of their last site, a sub-batch whenever a fair part of the share has landed (wgshare::take_upto)
+    int run_streaming(int d, const wgbsseg_group::Loader* L, std::string& msg)
+    {
+        const wgshare::Span& span = g->shares[(size_t)d].span;
+        std::vector<size_t> order(calls[(size_t)d].items);
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return todo[a].second < todo[b].second; });
+        std::vector<wgshare::Range> sites(order.size());
+        for (size_t k = 0; k < order.size(); k++) sites[k] = {todo[order[k]].first - 1, todo[order[k]].second - 1};
+        const int64_t min_take = wgshare::min_take(g->chunk_size, span);
+        for (size_t pos = 0, end = 0; pos < order.size(); pos = end) {
+            for (;;) {
+                const bool fin = L->finished.load() != 0;
+                const int64_t r = L->ready.load();
+                if (fin && L->rc != WGBSSEG_OK) { msg = L->msg; return L->rc; }
+                end = fin ? order.size() : wgshare::take_upto(sites, pos, span.win_lo + r, min_take);
+                if (end > pos) break;
+                std::this_thread::sleep_for(std::chrono::microseconds(200));
+            }
+            const int rc = run_items(d, std::vector<size_t>(order.begin() + (ptrdiff_t)pos, order.begin() + (ptrdiff_t)end), msg);
+            if (rc != WGBSSEG_OK) return rc;
+        }
+        return WGBSSEG_OK;
+    }
+
+    int run_share(int d, std::string& msg)
+    {
+        const auto* L = g->streaming ? g->shares[(size_t)d].loader.get() : nullptr;
+        if (L && !L->finished.load()) return run_streaming(d, L, msg);
+        if (L && L->rc != WGBSSEG_OK) { msg = L->msg; return L->rc; }
+        return run_items(d, calls[(size_t)d].items, msg);
+    }
+};
 
 }  // namespace
 
@@ -1837,25 +1950,23 @@ int wgbsseg_group_create(const int32_t* devices, int32_t n_shares, wgbsseg_group
     // (measured: a group of eight on one MI355X 34.4 -> 38.7-40.6 ms per step).
     bool doubled = false;
     for (int32_t a = 0; a < n_shares && !doubled; a++) for (int32_t b = a + 1; b < n_shares; b++) if (devices[a] == devices[b]) { doubled = true; break; }
+    g->shares.resize((size_t)n_shares);
     for (int32_t d = 0; d < n_shares; d++) {
         wgbsseg_ctx* c = nullptr;
         const int rc = create_ctx(devices[d], !doubled, &c, err, errlen);
-        if (rc != WGBSSEG_OK) { for (auto* x : g->shares) wgbsseg_destroy(x); return rc; }
-        g->shares.push_back(c);
+        if (rc != WGBSSEG_OK) return rc;                    // (the shares made so far go with g)
+        g->shares[(size_t)d].ctx.reset(c);
     }
-    g->loaded.assign((size_t)n_shares, 0);
     *out = g.release();
     return WGBSSEG_OK;
 }
 
-void group_join_loaders(wgbsseg_group* g);
-
 void wgbsseg_group_destroy(wgbsseg_group* g)
 {
     if (!g) return;
-    group_join_loaders(g);
+    for (auto& sh : g->shares) if (sh.loader) sh.loader->join();
     // releasing gigabytes of device buffers takes milliseconds per context: do the shares side by side
-    parallel_for((int64_t)g->shares.size(), 64, [&](int64_t d) { wgbsseg_destroy(g->shares[(size_t)d]); });
+    wgshare::parallel_for((int64_t)g->shares.size(), 64, [&](int64_t d) { g->shares[(size_t)d].ctx.reset(); });
     delete g;
 }
 
@@ -1873,64 +1984,12 @@ int wgbsseg_plan_shares_weighted(const uint32_t* loci, int64_t n_sites, const in
                                  int64_t chunk_size, const wgbsseg_params* P, int32_t n_shares, const double* weights, int64_t halo, int64_t* own_lo,
                                  int64_t* own_hi, int64_t* win_lo, int64_t* win_hi, int64_t* share_chunks, int64_t* share_work, char* err, size_t errlen)
 {
-    if (!loci || n_sites < 1 || !region_start || !region_end || n_regions < 1 || chunk_size < 1 || !P || n_shares < 1 || !own_lo || !own_hi) {
-        set_err(err, errlen, "bad arguments to plan_shares"); return WGBSSEG_E_ARG;
-    }
-    if (P->max_bp == 0 || P->max_cpg < 1) { set_err(err, errlen, "max_bp and max_cpg must be >= 1"); return WGBSSEG_E_ARG; }
-    const int G = n_shares;
-    struct Ck { int64_t lo, hi, w; };
-    std::vector<Ck> cks;
-    for (int64_t r = 0; r < n_regions; r++) {
-        const int64_t a = region_start[r], b = region_end[r];
-        if (a < 1 || b <= a || b - 1 > n_sites) { set_err(err, errlen, "region %lld = [%lld, %lld) is empty or outside the %lld sites", (long long)r, (long long)a, (long long)b, (long long)n_sites); return WGBSSEG_E_ARG; }
-        if (r && a < region_end[r - 1]) { set_err(err, errlen, "plan_shares: regions must be ascending and disjoint"); return WGBSSEG_E_ARG; }
-        for (int64_t s0 = a; s0 < b; s0 += chunk_size) cks.push_back({s0 - 1, std::min(s0 + chunk_size, b) - 1, 0});
-    }
-    // share d's target: weights[d] / sum(weights) of the work (NULL: equal shares)
-    std::vector<double> upto((size_t)G);
-    {
-        double sum = 0;
-        for (int d = 0; d < G; d++) {
-            const double w = weights ? weights[d] : 1.0;
-            if (!(w >= 0.0)) { set_err(err, errlen, "plan_shares: weights must be >= 0"); return WGBSSEG_E_ARG; }
-            sum += w; upto[(size_t)d] = sum;
-        }
-        if (!(sum > 0.0)) { set_err(err, errlen, "plan_shares: all weights are zero"); return WGBSSEG_E_ARG; }
-        for (auto& u : upto) u /= sum;
-    }
-    if (G == 1) {
-        for (auto& c : cks) c.w = c.hi - c.lo;                  // nothing to balance: do not walk the loci
-    } else {
-        parallel_for((int64_t)cks.size(), 32, [&](int64_t i) {
-            Ck& c = cks[(size_t)i];
-            c.w = chunk_work(loci, c.lo, c.hi, P->max_cpg, P->max_bp) + 4 * (c.hi - c.lo);     // + the per-site passes (scan, windows, recurrence)
-        });
-    }
-    int64_t total = 0;
-    for (auto& c : cks) total += c.w;
-    if (halo < 0) halo = std::max<int64_t>(chunk_size, 4096);
-    std::vector<int64_t> nch((size_t)G, 0), wk((size_t)G, 0);
-    std::vector<char> any((size_t)G, 0);
-    {   // contiguous runs of chunks: share d ends where the cumulative work passes (d+1)/G of the total
-        int d = 0;
-        int64_t acc = 0;
-        for (auto& c : cks) {
-            while (d < G - 1 && (double)acc >= (double)total * (weights ? upto[(size_t)d] : (double)(d + 1) / G)) d++;
-            if (!any[(size_t)d]) { own_lo[d] = c.lo; any[(size_t)d] = 1; }
-            own_hi[d] = c.hi;
-            nch[(size_t)d]++; wk[(size_t)d] += c.w;
-            acc += c.w;
-        }
-    }
-    for (int q = 0; q < G; q++) {
-        if (!any[(size_t)q]) own_lo[q] = own_hi[q] = q ? own_hi[q - 1] : cks.front().lo;
-        // window: owned sites +- halo, the lower edge on a multiple of 128 sites (views into one device buffer stay 256-byte aligned)
-        const bool has = own_hi[q] > own_lo[q];
-        if (win_lo) win_lo[q] = has ? (std::max<int64_t>(0, own_lo[q] - halo) & ~127LL) : 0;
-        if (win_hi) win_hi[q] = has ? std::min<int64_t>(n_sites, own_hi[q] + halo) : 0;
-        if (share_chunks) share_chunks[q] = nch[(size_t)q];
-        if (share_work) share_work[q] = wk[(size_t)q];
-    }
+    if (!own_lo || !own_hi) { set_err(err, errlen, "bad arguments to plan_shares"); return WGBSSEG_E_ARG; }
+    std::vector<wgshare::Span> spans;
+    std::string msg;
+    const int rc = wgshare::plan_shares(loci, n_sites, region_start, region_end, n_regions, chunk_size, P, n_shares, weights, halo, spans, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    scatter_spans(spans, own_lo, own_hi, win_lo, win_hi, share_chunks, share_work);
     return WGBSSEG_OK;
 }
 
@@ -1939,36 +1998,29 @@ int wgbsseg_group_plan(wgbsseg_group* g, const uint32_t* loci, int64_t n_sites, 
                        int64_t* share_chunks, int64_t* share_work, char* err, size_t errlen)
 {
     if (!g) { set_err(err, errlen, "group is NULL"); return WGBSSEG_E_ARG; }
-    const int G = (int)g->shares.size();
     g->planned = false;
-    std::fill(g->loaded.begin(), g->loaded.end(), 0);
-    g->own_lo.assign((size_t)G, 0); g->own_hi.assign((size_t)G, 0);
-    g->win_lo.assign((size_t)G, 0); g->win_hi.assign((size_t)G, 0);
-    g->share_chunks.assign((size_t)G, 0); g->share_work.assign((size_t)G, 0);
-    if (halo < 0) halo = std::max<int64_t>(chunk_size, 4096);
-    int rc = wgbsseg_plan_shares(loci, n_sites, region_start, region_end, n_regions, chunk_size, P, G, halo, g->own_lo.data(), g->own_hi.data(),
-                                 g->win_lo.data(), g->win_hi.data(), g->share_chunks.data(), g->share_work.data(), err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
+    for (auto& s : g->shares) { s.span = wgshare::Span(); s.loaded = false; }
+    std::vector<wgshare::Span> spans;
+    std::string msg;
+    halo = wgshare::resolve_halo(halo, chunk_size);
+    int rc = wgshare::plan_shares(loci, n_sites, region_start, region_end, n_regions, chunk_size, P, (int32_t)g->shares.size(), nullptr, halo, spans, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    for (size_t d = 0; d < spans.size(); d++) g->shares[d].span = spans[d];
     g->rs.assign(region_start, region_start + n_regions);
     g->re.assign(region_end, region_end + n_regions);
     g->chunk_size = chunk_size; g->n_sites = n_sites; g->halo = halo; g->P = *P;
     // every share's window of the loci goes to its device now (4 bytes per site)
-    std::vector<int> rcs((size_t)G, WGBSSEG_OK);
-    std::vector<std::string> msgs((size_t)G);
-    parallel_for(G, 64, [&](int64_t d) {
-        if (g->win_hi[(size_t)d] <= g->win_lo[(size_t)d]) return;
+    rc = for_shares(resident_shares(g), true, [&](int d, std::string& m) {
+        const wgshare::Span& s = g->shares[(size_t)d].span;
+        wgbsseg_ctx* c = g->shares[(size_t)d].ctx.get();
         char eb[512] = {0};
-        rcs[(size_t)d] = wgbsseg_set_loci_host(g->shares[(size_t)d], loci + g->win_lo[(size_t)d], g->win_hi[(size_t)d] - g->win_lo[(size_t)d], eb, sizeof(eb));
-        g->shares[(size_t)d]->site_base = g->win_lo[(size_t)d];
-        msgs[(size_t)d] = eb;
-    });
-    for (int d = 0; d < G; d++) if (rcs[(size_t)d] != WGBSSEG_OK) { set_err(err, errlen, "share %d: %s", d, msgs[(size_t)d].c_str()); return rcs[(size_t)d]; }
-    for (int d = 0; d < G; d++) {
-        if (win_lo) win_lo[d] = g->win_lo[(size_t)d];
-        if (win_hi) win_hi[d] = g->win_hi[(size_t)d];
-        if (share_chunks) share_chunks[d] = g->share_chunks[(size_t)d];
-        if (share_work) share_work[d] = g->share_work[(size_t)d];
-    }
+        const int r = wgbsseg_set_loci_host(c, loci + s.win_lo, s.win_hi - s.win_lo, eb, sizeof(eb));
+        c->site_base = s.win_lo;
+        m = eb;
+        return r;
+    }, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    scatter_spans(spans, nullptr, nullptr, win_lo, win_hi, share_chunks, share_work);
     g->planned = true;
     return WGBSSEG_OK;
 }
@@ -1977,26 +2029,19 @@ int wgbsseg_group_load_host(wgbsseg_group* g, const uint8_t* const* samples, int
 {
     if (!g || !g->planned) { set_err(err, errlen, "group_load_host: call wgbsseg_group_plan first"); return WGBSSEG_E_STATE; }
     if (!samples || n_samples < 1 || n_sites != g->n_sites) { set_err(err, errlen, "group_load_host: bad arguments (the plan is for %lld sites)", (long long)g->n_sites); return WGBSSEG_E_ARG; }
-    const int G = (int)g->shares.size();
-    std::vector<int> rcs((size_t)G, WGBSSEG_OK);
-    std::vector<std::string> msgs((size_t)G);
-    parallel_for(G, 64, [&](int64_t d) {
-        const int64_t lo = g->win_lo[(size_t)d], hi = g->win_hi[(size_t)d];
-        if (hi <= lo) return;
+    std::string msg;
+    const int rc = for_shares(resident_shares(g), true, [&](int d, std::string& m) {
+        auto& sh = g->shares[(size_t)d];
         std::vector<const uint8_t*> ptrs((size_t)n_samples);
-        for (int64_t s = 0; s < n_samples; s++) ptrs[(size_t)s] = samples[s] + 2 * lo;
+        for (int64_t s = 0; s < n_samples; s++) ptrs[(size_t)s] = samples[s] + 2 * sh.span.win_lo;
         char eb[512] = {0};
-        rcs[(size_t)d] = wgbsseg_set_betas_host(g->shares[(size_t)d], ptrs.data(), n_samples, hi - lo, eb, sizeof(eb));
-        msgs[(size_t)d] = eb;
-        if (rcs[(size_t)d] == WGBSSEG_OK) g->loaded[(size_t)d] = 1;
-    });
-    for (int d = 0; d < G; d++) if (rcs[(size_t)d] != WGBSSEG_OK) { set_err(err, errlen, "share %d: %s", d, msgs[(size_t)d].c_str()); return rcs[(size_t)d]; }
-    return WGBSSEG_OK;
-}
-
-void group_join_loaders(wgbsseg_group* g)
-{
-    for (auto& l : g->loaders) if (l && l->th.joinable()) l->th.join();
+        const int r = wgbsseg_set_betas_host(sh.ctx.get(), ptrs.data(), n_samples, sh.span.win_hi - sh.span.win_lo, eb, sizeof(eb));
+        m = eb;
+        if (r == WGBSSEG_OK) sh.loaded = true;
+        return r;
+    }, msg);
+    if (rc != WGBSSEG_OK) set_err(err, errlen, "%s", msg.c_str());
+    return rc;
 }
 
 int wgbsseg_group_load_host_async(wgbsseg_group* g, const uint8_t* const* samples, int64_t n_samples, int64_t n_sites, char* err, size_t errlen)
@@ -2004,35 +2049,30 @@ int wgbsseg_group_load_host_async(wgbsseg_group* g, const uint8_t* const* sample
     if (!g || !g->planned) { set_err(err, errlen, "group_load_host_async: call wgbsseg_group_plan first"); return WGBSSEG_E_STATE; }
     if (!samples || n_samples < 1 || n_sites != g->n_sites) { set_err(err, errlen, "group_load_host_async: bad arguments (the plan is for %lld sites)", (long long)g->n_sites); return WGBSSEG_E_ARG; }
     for (int64_t s = 0; s < n_samples; s++) if (!samples[s]) { set_err(err, errlen, "samples[%lld] is NULL", (long long)s); return WGBSSEG_E_ARG; }
-    group_join_loaders(g);
-    const int G = (int)g->shares.size();
-    g->loaders.clear();
-    g->loaders.resize((size_t)G);
+    for (auto& sh : g->shares) sh.loader.reset();            // (joins the uploader of an earlier call)
     // the device rows exist (and the contexts point at them) before any byte moves; the uploaders then fill them front to back.
     // A failure here leaves no share half-way: nothing counts as loaded, no loader runs, the group is not streaming.
     auto fail = [&](hipError_t e, const char* what) {
-        for (int q = 0; q < G; q++) { g->loaded[(size_t)q] = 0; g->shares[(size_t)q]->last_valid = false; }
-        g->loaders.clear();
+        for (auto& sh : g->shares) { sh.loaded = false; sh.ctx->last_valid = false; }
         g->streaming = false;
         set_err(err, errlen, "group_load_host_async: %s: %s", what, hipGetErrorString(e));
         return e == hipErrorOutOfMemory ? WGBSSEG_E_NOMEM : WGBSSEG_E_HIP;
     };
-    for (int d = 0; d < G; d++) {
-        const int64_t lo = g->win_lo[(size_t)d], hi = g->win_hi[(size_t)d];
-        if (hi <= lo) continue;
-        wgbsseg_ctx* c = g->shares[(size_t)d];
-        hipError_t e = hipSetDevice(c->device);
+    const std::vector<int> which = resident_shares(g);
+    for (int d : which) {
+        const auto& sh = g->shares[(size_t)d];
+        hipError_t e = hipSetDevice(sh.ctx->device);
         if (e != hipSuccess) return fail(e, "hipSetDevice");
-        e = own_rows(c, n_samples, hi - lo, 1);
+        e = own_rows(sh.ctx.get(), n_samples, sh.span.win_hi - sh.span.win_lo, 1);
         if (e != hipSuccess) return fail(e, "device rows of a share");
     }
     std::vector<const uint8_t*> base(samples, samples + n_samples);
-    for (int d = 0; d < G; d++) {
-        const int64_t lo = g->win_lo[(size_t)d], hi = g->win_hi[(size_t)d];
-        if (hi <= lo) continue;
-        g->loaders[(size_t)d].reset(new wgbsseg_group::Loader());
-        wgbsseg_group::Loader* L = g->loaders[(size_t)d].get();
-        wgbsseg_ctx* c = g->shares[(size_t)d];
+    for (int d : which) {
+        auto& sh = g->shares[(size_t)d];
+        sh.loader.reset(new wgbsseg_group::Loader());
+        auto* L = sh.loader.get();
+        wgbsseg_ctx* c = sh.ctx.get();
+        const int64_t lo = sh.span.win_lo, hi = sh.span.win_hi;
         L->th = std::thread([L, c, base, lo, hi, n_samples]() {
             std::vector<const uint8_t*> ptrs((size_t)n_samples);
             for (int64_t s = 0; s < n_samples; s++) ptrs[(size_t)s] = base[(size_t)s] + 2 * lo;
@@ -2040,7 +2080,7 @@ int wgbsseg_group_load_host_async(wgbsseg_group* g, const uint8_t* const* sample
             L->ready.store(L->rc == WGBSSEG_OK ? hi - lo : L->ready.load());
             L->finished.store(1);
         });
-        g->loaded[(size_t)d] = 1;
+        sh.loaded = true;
     }
     g->streaming = true;
     return WGBSSEG_OK;
@@ -2049,10 +2089,12 @@ int wgbsseg_group_load_host_async(wgbsseg_group* g, const uint8_t* const* sample
 int wgbsseg_group_load_wait(wgbsseg_group* g, char* err, size_t errlen)
 {
     if (!g) { set_err(err, errlen, "group is NULL"); return WGBSSEG_E_ARG; }
-    group_join_loaders(g);
+    for (auto& sh : g->shares) if (sh.loader) sh.loader->join();
     g->streaming = false;
-    for (size_t d = 0; d < g->loaders.size(); d++)
-        if (g->loaders[d] && g->loaders[d]->rc != WGBSSEG_OK) { set_err(err, errlen, "share %d: %s", (int)d, g->loaders[d]->msg.c_str()); return g->loaders[d]->rc; }
+    for (size_t d = 0; d < g->shares.size(); d++) {
+        const auto* L = g->shares[d].loader.get();
+        if (L && L->rc != WGBSSEG_OK) { set_err(err, errlen, "share %d: %s", (int)d, L->msg.c_str()); return L->rc; }
+    }
     return WGBSSEG_OK;
 }
 
@@ -2060,10 +2102,10 @@ int wgbsseg_group_share_set_device(wgbsseg_group* g, int32_t share, const void* 
 {
     if (!g || !g->planned) { set_err(err, errlen, "group_share_set_device: call wgbsseg_group_plan first"); return WGBSSEG_E_STATE; }
     if (share < 0 || share >= (int32_t)g->shares.size()) { set_err(err, errlen, "no share %d", (int)share); return WGBSSEG_E_ARG; }
-    const int64_t n = g->win_hi[(size_t)share] - g->win_lo[(size_t)share];
-    if (n <= 0) return WGBSSEG_OK;                          // a share without chunks needs no data
-    const int rc = wgbsseg_set_betas_device(g->shares[(size_t)share], base, n_samples, pitch_bytes, n, err, errlen);
-    if (rc == WGBSSEG_OK) g->loaded[(size_t)share] = 1;
+    auto& sh = g->shares[(size_t)share];
+    if (!sh.span.resident()) return WGBSSEG_OK;             // a share without chunks needs no data
+    const int rc = wgbsseg_set_betas_device(sh.ctx.get(), base, n_samples, pitch_bytes, sh.span.win_hi - sh.span.win_lo, err, errlen);
+    if (rc == WGBSSEG_OK) sh.loaded = true;
     return rc;
 }
 
@@ -2079,103 +2121,27 @@ int wgbsseg_group_segment_region_range(wgbsseg_group* g, int64_t first_region, i
 {
     if (!g || !g->planned) { set_err(err, errlen, "group_segment_regions: call wgbsseg_group_plan first"); return WGBSSEG_E_STATE; }
     if (first_region < 0 || end_region <= first_region || end_region > (int64_t)g->rs.size()) { set_err(err, errlen, "group_segment_region_range: regions [%lld, %lld) of %lld planned", (long long)first_region, (long long)end_region, (long long)g->rs.size()); return WGBSSEG_E_ARG; }
-    const int G = (int)g->shares.size();
-    for (int d = 0; d < G; d++)
-        if (g->win_hi[(size_t)d] > g->win_lo[(size_t)d] && !g->loaded[(size_t)d]) { set_err(err, errlen, "share %d has no beta data yet", d); return WGBSSEG_E_STATE; }
-    int64_t n_batches = 0;
-    std::vector<char> ran((size_t)G, first_region > 0 ? 1 : 0);     // the share's timings: reset on its first batch of the FIRST slice of the regions, summed after
-    std::vector<int64_t> slot_next((size_t)G, 0);            // page-locked result buffers of a share used by this call so far
+    for (int d : resident_shares(g))
+        if (!g->shares[(size_t)d].loaded) { set_err(err, errlen, "share %d has no beta data yet", d); return WGBSSEG_E_STATE; }
+    std::vector<ShareCall> calls(g->shares.size());
+    for (auto& c : calls) c.ran = first_region > 0;
     wgstitch::BatchFn run_batch = [&](const std::vector<wgstitch::Sites>& todo, wgstitch::BatchResult& res, std::string& msg) -> int {
-        // route: the share that owns the first site of the range; a junction patch reaches into the next share's first chunk,
-        // which the halo of the window covers
-        std::vector<std::vector<size_t>> items((size_t)G);
-        for (size_t i = 0; i < todo.size(); i++) {
-            const int64_t lo = todo[i].first - 1, hi = todo[i].second - 1;
-            if (hi - lo > 0x7fffffff) { msg = "chunk too long"; return WGBSSEG_E_ARG; }
-            int d = (int)(std::upper_bound(g->own_lo.begin(), g->own_lo.end(), lo) - g->own_lo.begin()) - 1;
-            d = std::max(d, 0);
-            while (d > 0 && g->own_hi[(size_t)d] <= g->own_lo[(size_t)d]) d--;              // shares without chunks own nothing
-            int pick = -1;
-            for (int q : {d, d + 1, d - 1})
-                if (q >= 0 && q < G && g->win_lo[(size_t)q] <= lo && hi <= g->win_hi[(size_t)q] && g->win_hi[(size_t)q] > g->win_lo[(size_t)q]) { pick = q; break; }
-            if (pick < 0) {
-                msg = "sites [" + std::to_string(lo + 1) + ", " + std::to_string(hi + 1) + ") are not resident on any single share (halo " +
-                      std::to_string(g->halo) + " sites): a junction patch outgrew it; rerun on one share";
-                return WGBSSEG_E_STATE;
-            }
-            items[(size_t)pick].push_back(i);
+        GroupBatch batch{g, todo, res, calls};
+        int rc = batch.route(msg);
+        if (rc != WGBSSEG_OK) return rc;
+        std::vector<int> busy;
+        for (size_t d = 0; d < calls.size(); d++) if (!calls[d].items.empty()) busy.push_back((int)d);
+        rc = for_shares(busy, false, [&](int d, std::string& m) { return batch.run_share(d, m); }, msg);
+        if (rc != WGBSSEG_OK) return rc;
+        for (int d : busy) {                                // the fallback buffers of this batch go with its result
+            for (auto& o : calls[(size_t)d].owned) res.owned.push_back(std::move(o));
+            calls[(size_t)d].owned.clear();
         }
-        res.ptr.assign(todo.size(), nullptr);
-        res.cnt.assign(todo.size(), 0);
-        std::vector<int> rcs((size_t)G, WGBSSEG_OK);
-        std::vector<std::string> msgs((size_t)G);
-        std::vector<std::vector<std::unique_ptr<int32_t[]>>> owned((size_t)G);
-        auto run_items = [&](int d, const std::vector<size_t>& it) -> bool {
-            std::vector<int64_t> st0(it.size()), off;
-            std::vector<int32_t> ln(it.size());
-            for (size_t k = 0; k < it.size(); k++) {
-                st0[k] = todo[it[k]].first - 1 - g->win_lo[(size_t)d];
-                ln[k] = (int32_t)(todo[it[k]].second - todo[it[k]].first);
-            }
-            const int32_t* flat = nullptr;
-            std::unique_ptr<int32_t[]> own;
-            rcs[(size_t)d] = run_ctx_batch(g->shares[(size_t)d], st0, ln, &g->P, slot_next[(size_t)d]++, ran[(size_t)d] != 0, flat, off, own, msgs[(size_t)d]);
-            if (rcs[(size_t)d] != WGBSSEG_OK) return false;
-            if (own) owned[(size_t)d].push_back(std::move(own));
-            ran[(size_t)d] = 1;
-            for (size_t k = 0; k < it.size(); k++) { res.ptr[it[k]] = flat + off[k]; res.cnt[it[k]] = off[k + 1] - off[k]; }
-            return true;
-        };
-        auto work = [&](int d) {
-            const std::vector<size_t>& it = items[(size_t)d];
-            if (it.empty()) return;
-            wgbsseg_group::Loader* L = (g->streaming && (size_t)d < g->loaders.size()) ? g->loaders[(size_t)d].get() : nullptr;
-            if (!L || L->finished.load()) {
-                if (L && L->rc != WGBSSEG_OK) { rcs[(size_t)d] = L->rc; msgs[(size_t)d] = L->msg; return; }
-                run_items(d, it);
-                return;
-            }
-            // the share's bytes are still arriving (front to back): segment what is resident while the rest is on its way —
-            // items in order of their last site, a sub-batch whenever a fair part of the share has landed
-            std::vector<size_t> order(it);
-            std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return todo[a].second < todo[b].second; });
-            const int64_t wlo = g->win_lo[(size_t)d];
-            const int64_t min_take = std::max<int64_t>(4 * g->chunk_size, (g->win_hi[(size_t)d] - wlo) / 5);
-            size_t pos = 0;
-            while (pos < order.size()) {
-                const int64_t first_end = todo[order[pos]].second - 1 - wlo;          // resident sites the next item needs
-                int64_t r = 0;
-                for (;;) {
-                    const bool fin = L->finished.load() != 0;
-                    r = L->ready.load();
-                    if (fin && L->rc != WGBSSEG_OK) { rcs[(size_t)d] = L->rc; msgs[(size_t)d] = L->msg; return; }
-                    if (fin) { r = g->win_hi[(size_t)d] - wlo; break; }
-                    if (r >= first_end && r - (todo[order[pos]].first - 1 - wlo) >= min_take) break;
-                    std::this_thread::sleep_for(std::chrono::microseconds(200));
-                }
-                std::vector<size_t> take;
-                while (pos < order.size() && todo[order[pos]].second - 1 - wlo <= r) take.push_back(order[pos++]);
-                if (!run_items(d, take)) return;
-            }
-        };
-        int busy = 0, only = -1;
-        for (int d = 0; d < G; d++) if (!items[(size_t)d].empty()) { busy++; only = d; }
-        if (busy == 1) work(only);
-        else {
-            std::vector<std::thread> th;
-            for (int d = 0; d < G; d++) if (!items[(size_t)d].empty()) th.emplace_back(work, d);
-            for (auto& x : th) x.join();
-        }
-        for (int d = 0; d < G; d++) {
-            if (rcs[(size_t)d] != WGBSSEG_OK) { msg = "share " + std::to_string(d) + ": " + msgs[(size_t)d]; return rcs[(size_t)d]; }
-            for (auto& o : owned[(size_t)d]) res.owned.push_back(std::move(o));
-        }
-        n_batches++;
         return WGBSSEG_OK;
     };
     std::string msg;
     const int rc = wgstitch::segment_regions(g->rs.data() + first_region, g->re.data() + first_region, end_region - first_region, g->chunk_size, run_batch, borders_out,
-                                             borders_cap, borders_off, stats, msg, g->shares[0]->speculate);
+                                             borders_cap, borders_off, stats, msg, g->shares[0].ctx->speculate);
     if (g->streaming && (end_region == (int64_t)g->rs.size() || rc != 0)) {      // every byte has been consumed by now; collect the uploaders
         char eb[512] = {0};
         const int lrc = wgbsseg_group_load_wait(g, eb, sizeof(eb));
@@ -2187,7 +2153,7 @@ int wgbsseg_group_segment_region_range(wgbsseg_group* g, int64_t first_region, i
 int wgbsseg_group_get_timings(const wgbsseg_group* g, int32_t share, wgbsseg_timings* out)
 {
     if (!g || share < 0 || share >= (int32_t)g->shares.size()) return WGBSSEG_E_ARG;
-    return wgbsseg_get_timings(g->shares[(size_t)share], out);
+    return wgbsseg_get_timings(g->shares[(size_t)share].ctx.get(), out);
 }
 
 int wgbsseg_scan_only(wgbsseg_ctx* c, const int64_t* chunk_start0, const int32_t* chunk_len, int64_t n_chunks, int repeat, int want_carry,

@@ -94,7 +94,9 @@ def init_host_group():
 def item_owners(starts, n_chunks, shares):
     """Owner rank of every item of the stitcher's first batch (wgbsseg_first_batch_items: chunks, then junction patches): a
     chunk belongs to the share that the planner gave it to, a patch to the owner of the chunk its first site lies in (its
-    other end stays inside that share's halo: patches planned up front span at most 200 sites)."""
+    other end stays inside that share's halo: patches planned up front span at most 200 sites).  This follows the rule of
+    the native router (wgshare::route, csrc/share_plan.h): the owner of the first site, stepping back over shares that own nothing;
+    the router's further steps - the windows of the neighbouring shares - serve patches that have grown, which are not planned up front."""
     import numpy as np
     lo, hi = np.asarray(shares['own_lo']), np.asarray(shares['own_hi'])
     cs = np.asarray(starts[:n_chunks]) - 1                      # 0-based first sites of the chunks, ascending
