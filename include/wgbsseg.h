@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 260            /* 0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 270            /* 0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -40,6 +40,7 @@ extern "C" {
 #define WGBSSEG_E_LOCI_ORDER   -5      /* (internal since round 4: chunks whose loci do not ascend take the plain path — the reference's loops as written, segmentor.cpp:114-117 — and are no error) */
 #define WGBSSEG_E_CAPACITY     -6      /* borders_out too small */
 #define WGBSSEG_E_STATE        -7      /* betas / loci not set */
+#define WGBSSEG_E_IO           -8      /* a write to the caller's file descriptor failed; the message holds "errno N" */
 
 typedef struct wgbsseg_ctx wgbsseg_ctx;
 
@@ -354,6 +355,48 @@ int wgbsseg_pair_ranges(wgbsseg_ctx* ctx, const int32_t* a, const int32_t* b, in
 int wgbsseg_pair_hist(wgbsseg_ctx* ctx, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov, int32_t bins,
                       const double* edges, uint64_t* counts, char* err, size_t errlen);
 void wgbsseg_pair_hist_limits(int32_t* max_bins, int64_t* run_sites);
+
+/*
+ * One resident sample as BED text, a line per site — what `wgbstools beta2bed` prints (beta2bed.py:11-19 over the lines of
+ * view_beta.sh / view_lbeta.sh), formatted on the device and written to the file descriptor `fd`.  For the resident sites
+ * [start0, end0) in ascending order:
+ *
+ *   base line    name \t loc-1 \t loc+1 \t meth \t cov \n      loc: the site's locus (wgbsseg_set_loci_*), name: of the last
+ *                chromosome i with chrom_cum[i-1] <= site (chrom_cum = cumulative site counts, resident-relative)
+ *   min_cov N    a site with cov < N counts as meth = cov = 0 (N = 1: nothing changes)
+ *   keep_na 0    sites whose cov is 0 after that are dropped
+ *   mean         the line is  name \t loc-1 \t loc+1 \t R \n,  R = printf "%.3g" of the double meth / cov, byte for byte what
+ *                C prints, ties included (csrc/bed_fmt.h); -1 where cov is 0
+ *   mult         NULL, or one count per site of [start0, end0): the line is written that many times, copies adjacent (0: not
+ *                at all) — how `-L` repeats a site per overlapping BED row.  65535 is reserved and refused.
+ *
+ * The text is produced slab by slab (opts->slab_sites sites, 0 = the default of wgbsseg_beta2bed_limits): a length pass and
+ * a scan, then a pass that formats into LDS and copies out with wide stores; slab k+1 is computed while slab k is written
+ * to fd.  Nothing the size of the whole text is allocated.  opts->stage_bytes (0 = the default, the maximum) is the most a
+ * workgroup's text may take to be staged in LDS; a workgroup with more writes straight to global memory (csrc/bed_plan.h).
+ * Both parameters change speed only, never a byte.
+ *
+ * lines_written / bytes_written (either may be NULL): what went to fd.  Works on uint8 rows (wgbsseg_set_betas_*) and uint16
+ * rows (wgbsseg_set_lbetas_host).  Without rows or loci (or loci of another length): WGBSSEG_E_STATE.  WGBSSEG_E_ARG with a
+ * message naming the offender: a sample outside the resident samples, a range outside the resident sites, min_cov < 1, a
+ * chrom_cum that descends or does not end at the resident site count, a name longer than 31 bytes, a multiplicity of 65535,
+ * stage_bytes or slab_sites outside their limits.  WGBSSEG_E_CAPACITY: one slab's text would reach 4 GiB (multiplicities
+ * only): pass a smaller slab_sites.  WGBSSEG_E_IO: write(2) failed; the message holds "errno N".  The kernels' HIP-event
+ * time is what wgbsseg_last_block_sums_ms returns afterwards; wgbsseg_beta2bed_pass_ms splits it into the length + scan
+ * passes and the emit pass (either pointer may be NULL).
+ */
+typedef struct {
+    int32_t min_cov, mean, keep_na;
+    int32_t stage_bytes;       /* 0 = default */
+    int64_t slab_sites;        /* 0 = default */
+} wgbsseg_bed_opts;
+int wgbsseg_beta2bed(wgbsseg_ctx* ctx, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
+                     const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
+                     const wgbsseg_bed_opts* opts, int fd, int64_t* lines_written, int64_t* bytes_written,
+                     char* err, size_t errlen);
+void wgbsseg_beta2bed_pass_ms(const wgbsseg_ctx* ctx, double* length_ms, double* emit_ms);
+/* the default and the largest slab_sites, the largest (= default) stage_bytes, the longest chromosome name; any pointer may be NULL */
+void wgbsseg_beta2bed_limits(int64_t* default_slab, int64_t* max_slab, int32_t* max_stage_bytes, int32_t* max_name);
 
 /*
  * BED regions -> CpG index ranges: the join of `wgbstools convert -L` (convert.py:147-185 chr_thread, :133-145

@@ -20,10 +20,10 @@ if os.environ.get('WGBSSEG_LIB') and os.environ.get('WGBSSEG_ALLOW_LIB_OVERRIDE'
     print('[wgbsseg] WGBSSEG_LIB: loading %s instead of the in-tree library' % LIB_PATH, file=_sys.stderr)
 SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 
-OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE = 0, -1, -2, -3, -4, -5, -6, -7
+OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 260          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 270          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -41,7 +41,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_debug_homog_bins',
            'wgbsseg_bimodal_create', 'wgbsseg_bimodal_feed', 'wgbsseg_bimodal_finish', 'wgbsseg_bimodal_destroy', 'wgbsseg_bimodal_kernel_ms',
            'wgbsseg_debug_bimodal_terms', 'wgbsseg_sample_stats',
-           'wgbsseg_pair_ranges', 'wgbsseg_pair_hist', 'wgbsseg_pair_hist_limits']
+           'wgbsseg_pair_ranges', 'wgbsseg_pair_hist', 'wgbsseg_pair_hist_limits',
+           'wgbsseg_beta2bed', 'wgbsseg_beta2bed_pass_ms', 'wgbsseg_beta2bed_limits']
 
 
 class NativeLibraryError(RuntimeError):
@@ -68,6 +69,11 @@ SAMPLE_STAT_DTYPE = np.dtype([('n_sites', np.uint64), ('meth_sum', np.uint64), (
 
 # wgbsseg_pair_range (include/wgbsseg.h): what Segmenter.pair_ranges returns one of per pair
 PAIR_RANGE_DTYPE = np.dtype([('n', np.uint64), ('a_min', np.float64), ('a_max', np.float64), ('b_min', np.float64), ('b_max', np.float64)])
+
+
+class BedOpts(C.Structure):
+    """wgbsseg_bed_opts (include/wgbsseg.h)"""
+    _fields_ = [('min_cov', C.c_int32), ('mean', C.c_int32), ('keep_na', C.c_int32), ('stage_bytes', C.c_int32), ('slab_sites', C.c_int64)]
 
 
 class Timings(C.Structure):
@@ -187,6 +193,12 @@ def load():
     L.wgbsseg_pair_hist.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_pair_hist_limits.restype = None
     L.wgbsseg_pair_hist_limits.argtypes = [vp, vp]
+    L.wgbsseg_beta2bed.restype = i32
+    L.wgbsseg_beta2bed.argtypes = [vp, i32, i64, i64, vp, vp, C.POINTER(C.c_char_p), i32, C.POINTER(BedOpts), C.c_int, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_beta2bed_pass_ms.restype = None
+    L.wgbsseg_beta2bed_pass_ms.argtypes = [vp, vp, vp]
+    L.wgbsseg_beta2bed_limits.restype = None
+    L.wgbsseg_beta2bed_limits.argtypes = [vp, vp, vp, vp]
     L.wgbsseg_set_site_base.restype = i32
     L.wgbsseg_set_site_base.argtypes = [vp, i64]
     L.wgbsseg_stitch_regions.restype = i32
@@ -497,6 +509,37 @@ class Segmenter:
                                          self._err, ERRLEN), self._err)
         return counts
 
+    def beta2bed(self, fd, sample, chrom_names, chrom_cum, start0=0, end0=None, mult=None, min_cov=1, mean=False, keep_na=False,
+                 slab_sites=0, stage_bytes=0):
+        """wgbsseg_beta2bed: resident sample `sample` as BED text, a line per site of [start0, end0) (`mult`: uint16 copies per
+        site), written to the file descriptor `fd` -> (lines written, bytes written).  A failed write raises OSError with the
+        descriptor's errno (BrokenPipeError for a reader that went away)."""
+        end0 = self.n_sites if end0 is None else int(end0)
+        cum = np.ascontiguousarray(chrom_cum, dtype=np.int64)
+        names = (C.c_char_p * len(chrom_names))(*[str(n).encode() for n in chrom_names])
+        m = None
+        if mult is not None:
+            m = np.ascontiguousarray(mult, dtype=np.uint16)
+            if m.size != max(end0 - int(start0), 0):
+                raise ValueError('beta2bed: mult must hold one count per site of [start0, end0): %d for %d sites' % (m.size, end0 - int(start0)))
+        opts = BedOpts(int(min_cov), int(bool(mean)), int(bool(keep_na)), int(stage_bytes), int(slab_sites))
+        lines, nbytes = C.c_int64(0), C.c_int64(0)
+        rc = self._L.wgbsseg_beta2bed(self._h, int(sample), int(start0), end0, None if m is None else m.ctypes.data, cum.ctypes.data, names,
+                                      len(chrom_names), C.byref(opts), int(fd), C.addressof(lines), C.addressof(nbytes), self._err, ERRLEN)
+        if rc == E_IO:
+            import re
+            found = re.search(r'errno (\d+)', self._err.value.decode(errors='replace'))
+            code = int(found.group(1)) if found else 5
+            raise OSError(code, os.strerror(code))
+        _check(rc, self._err)
+        return int(lines.value), int(nbytes.value)
+
+    def beta2bed_pass_ms(self):
+        """(length + scan passes, emit pass) of the last beta2bed call, HIP-event milliseconds summed over its slabs"""
+        a, b = C.c_double(0), C.c_double(0)
+        self._L.wgbsseg_beta2bed_pass_ms(self._h, C.addressof(a), C.addressof(b))
+        return float(a.value), float(b.value)
+
     def last_block_sums_ms(self):
         return float(self._L.wgbsseg_last_block_sums_ms(self._h))
 
@@ -685,6 +728,14 @@ def pair_hist_limits():
     max_bins, run_sites = C.c_int32(0), C.c_int64(0)
     L.wgbsseg_pair_hist_limits(C.byref(max_bins), C.byref(run_sites))
     return int(max_bins.value), int(run_sites.value)
+
+
+def beta2bed_limits():
+    """wgbsseg_beta2bed_limits -> dict(default_slab, max_slab, max_stage_bytes, max_name)"""
+    L = load()
+    a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    L.wgbsseg_beta2bed_limits(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return dict(default_slab=int(a.value), max_slab=int(b.value), max_stage_bytes=int(c.value), max_name=int(d.value))
 
 
 def _stats_dict(stats):

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <chrono>
 #include <cstdarg>
 #include <cstdio>
@@ -24,6 +25,7 @@
 #include <pthread.h>
 #include <sched.h>
 #include <sys/mman.h>
+#include <unistd.h>
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
 #include <emmintrin.h>
 #endif
@@ -39,6 +41,7 @@
 #include "bimodal_kernels.h"
 #include "stats_kernels.h"
 #include "pair_kernels.h"
+#include "bed_kernels.h"
 #include "plain_dp.h"
 #include "stitch.h"
 #include "add_loci.h"
@@ -138,6 +141,12 @@ struct wgbsseg_ctx {
     DevBuf mk_out, cv_in, cv_out;      // wgbsseg_marker_stats: the statistics and the two sample lists; wgbsseg_convert_regions: the regions' columns | their CpG ranges
     DevBuf st_ranges, st_parts;     // wgbsseg_sample_stats: the range table | the tiles' partial results and the per-sample results
     DevBuf ph_pairs, ph_edges, ph_out;   // wgbsseg_pair_ranges / _pair_hist: the pair list (a | b) | the edges | the ranges or the counts
+    // wgbsseg_beta2bed: the chromosome table (cum | names) | a slab's multiplicities | its workgroup totals (bytes | lines | first byte | slab totals) |
+    // the text of two slabs, on the device and at home | the totals of two slabs at home | the passes' events per slab parity (length: 0-1, emit: 2-3)
+    DevBuf bed_tab, bed_mult, bed_wg, bed_out[2];
+    PinnedBuf bed_home[2], bed_tot;
+    Event bed_ev[2][4];
+    double bed_len_ms = 0.0, bed_emit_ms = 0.0;
     std::vector<int32_t> h_stage_bounds;
     // the short division core of the narrow scoring tiles: verified on the device per pseudo count (k_check_div)
     float divs_pc = -1.0f;     // pseudo count the verdict below is for
@@ -2473,6 +2482,151 @@ void wgbsseg_pair_hist_limits(int32_t* max_bins, int64_t* run_sites)
 {
     if (max_bins) *max_bins = WG_PH_MAX_BINS;
     if (run_sites) *run_sites = WG_PH_RUN;
+}
+
+namespace {
+
+// everything of `n` bytes to fd, whatever write(2) takes at a time; -> 0 or errno
+int write_all(int fd, const char* p, size_t n)
+{
+    while (n) {
+        const ssize_t w = write(fd, p, n);
+        if (w < 0) { if (errno == EINTR) continue; return errno; }
+        p += w; n -= (size_t)w;
+    }
+    return 0;
+}
+
+}  // namespace
+
+int wgbsseg_beta2bed(wgbsseg_ctx* c, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
+                     const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
+                     const wgbsseg_bed_opts* o, int fd, int64_t* lines_written, int64_t* bytes_written,
+                     char* err, size_t errlen)
+{
+    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
+    if (lines_written) *lines_written = 0;
+    if (bytes_written) *bytes_written = 0;
+    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
+    if (!c->loci || c->n_loci != c->n_total) { set_err(err, errlen, "loci not set or length differs from the betas (%lld vs %lld)", (long long)c->n_loci, (long long)c->n_total); return WGBSSEG_E_STATE; }
+    BedPlan plan;
+    std::string msg;
+    int rc = wg_bed_plan(sample, c->n_samples, start0, end0, c->n_total, chrom_cum, chrom_names, n_chroms, o, plan, msg);
+    if (rc == WGBSSEG_OK) rc = wg_bed_check_mult(mult, end0 - start0, start0, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    c->bed_len_ms = c->bed_emit_ms = c->last_block_sums_ms = 0.0;
+    if (plan.n_slabs == 0) return WGBSSEG_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    for (auto& pair : c->bed_ev) for (Event& e : pair) if (!e.h) HIP_TRY(e.create());
+    // the chromosome table
+    std::vector<char> tab((size_t)n_chroms * (8 + WG_BED_NAME_REC), 0);
+    memcpy(tab.data(), chrom_cum, (size_t)n_chroms * 8);
+    for (int32_t i = 0; i < n_chroms; i++) {
+        char* rec = tab.data() + (size_t)n_chroms * 8 + (size_t)i * WG_BED_NAME_REC;
+        const size_t len = strlen(chrom_names[i]);
+        memcpy(rec, chrom_names[i], len);
+        rec[WG_BED_NAME_REC - 1] = (char)len;
+    }
+    const int64_t max_wgs = BedPlan::workgroups(plan.slab_count(0));
+    HIP_TRY(c->bed_tab.ensure(tab.size()));
+    HIP_TRY(c->bed_wg.ensure((size_t)(3 * max_wgs + 2) * 8));
+    if (mult) HIP_TRY(c->bed_mult.ensure((size_t)plan.slab_count(0) * 2));
+    if (!c->bed_tot.ensure(4 * 8)) { set_err(err, errlen, "beta2bed: out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    HIP_TRY(hipMemcpyAsync(c->bed_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->sA));
+    uint64_t* d_bytes = c->bed_wg.as<uint64_t>();
+    uint64_t* d_lines = d_bytes + max_wgs;
+    uint64_t* d_base = d_lines + max_wgs;
+    uint64_t* d_tot = d_base + max_wgs;
+    volatile const uint64_t* h_tot = reinterpret_cast<volatile const uint64_t*>(c->bed_tot.p);
+    wg_bed_args a = {};
+    a.row = c->betas + (size_t)sample * (size_t)c->pitch;
+    a.loci = c->loci;
+    a.mult = mult ? c->bed_mult.as<uint16_t>() : nullptr;
+    a.cum = c->bed_tab.as<int64_t>();
+    a.names = c->bed_tab.as<char>() + (size_t)n_chroms * 8;
+    a.n_chroms = n_chroms; a.min_cov = o->min_cov; a.mean = o->mean ? 1 : 0; a.keep_na = o->keep_na ? 1 : 0;
+    a.stage_bytes = (uint32_t)plan.stage_bytes;
+    const auto slab_args = [&](int64_t k) { wg_bed_args s = a; s.first = plan.slab_first(k); s.n = (int32_t)plan.slab_count(k); return s; };
+    // the length pass and the scan of slab k, its totals on their way home
+    const auto enqueue_length = [&](int64_t k) -> hipError_t {
+        const wg_bed_args s = slab_args(k);
+        const dim3 grid((unsigned)BedPlan::workgroups(s.n));
+        hipError_t e = hipSuccess;
+        if (mult) e = hipMemcpyAsync(c->bed_mult.p, mult + (s.first - start0), (size_t)s.n * 2, hipMemcpyHostToDevice, c->sA);
+        if (e == hipSuccess) e = hipEventRecord(c->bed_ev[k & 1][0], c->sA);
+        if (e != hipSuccess) return e;
+        if (c->elem == 1) hipLaunchKernelGGL(k_bed_len<1>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_bytes, d_lines);
+        else hipLaunchKernelGGL(k_bed_len<2>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_bytes, d_lines);
+        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, c->sA, d_bytes, d_lines, (int64_t)grid.x, d_base, d_tot);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(c->bed_ev[k & 1][1], c->sA);
+        if (e == hipSuccess) e = hipMemcpyAsync(static_cast<uint64_t*>(c->bed_tot.p) + 2 * (k & 1), d_tot, 16, hipMemcpyDeviceToHost, c->sA);
+        return e;
+    };
+    const auto add_ms = [&](double& sum, Event& e0, Event& e1) -> hipError_t {
+        float ms = 0;
+        const hipError_t e = hipEventElapsedTime(&ms, e0, e1);
+        if (e == hipSuccess) sum += ms;
+        return e;
+    };
+    int64_t lines = 0, bytes = 0;
+    uint64_t home_bytes[2] = {0, 0};                             // the text of slab k at home, k & 1
+    int io = 0;
+    HIP_TRY(enqueue_length(0));
+    for (int64_t k = 0; k <= plan.n_slabs && !io; k++) {
+        HIP_TRY(hipStreamSynchronize(c->sA));                    // slab k's totals and slab k-1's text are home
+        if (k > 0 && home_bytes[(k - 1) & 1]) HIP_TRY(add_ms(c->bed_emit_ms, c->bed_ev[(k - 1) & 1][2], c->bed_ev[(k - 1) & 1][3]));
+        if (k < plan.n_slabs) {
+            const int par = (int)(k & 1);
+            HIP_TRY(add_ms(c->bed_len_ms, c->bed_ev[par][0], c->bed_ev[par][1]));
+            const uint64_t tot = h_tot[2 * par];
+            lines += (int64_t)h_tot[2 * par + 1];
+            rc = wg_bed_check_slab_bytes(tot, k, plan.slab_sites, msg);
+            if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+            home_bytes[par] = tot;
+            if (tot) {
+                const size_t first_size = (size_t)plan.slab_bytes_bound(0);     // (what every slab needs without multiplicities: no regrowth slab by slab)
+                HIP_TRY(c->bed_out[par].ensure((tot > first_size ? (size_t)tot : first_size) + 16));
+                if (!c->bed_home[par].ensure(tot > first_size ? (size_t)tot : first_size)) { set_err(err, errlen, "beta2bed: out of page-locked host memory (%llu bytes)", (unsigned long long)tot); return WGBSSEG_E_NOMEM; }
+                const wg_bed_args s = slab_args(k);
+                const dim3 grid((unsigned)BedPlan::workgroups(s.n));
+                HIP_TRY(hipEventRecord(c->bed_ev[par][2], c->sA));
+                if (c->elem == 1) hipLaunchKernelGGL(k_bed_emit<1>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_base, c->bed_out[par].as<char>());
+                else hipLaunchKernelGGL(k_bed_emit<2>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_base, c->bed_out[par].as<char>());
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(c->bed_ev[par][3], c->sA));
+                HIP_TRY(hipMemcpyAsync(c->bed_home[par].p, c->bed_out[par].p, (size_t)tot, hipMemcpyDeviceToHost, c->sA));
+            }
+            if (k + 1 < plan.n_slabs) HIP_TRY(enqueue_length(k + 1));
+        }
+        if (k > 0 && home_bytes[(k - 1) & 1]) {                  // the device works on slab k (and the lengths of k+1) meanwhile
+            io = write_all(fd, static_cast<const char*>(c->bed_home[(k - 1) & 1].p), (size_t)home_bytes[(k - 1) & 1]);
+            if (!io) bytes += (int64_t)home_bytes[(k - 1) & 1];
+        }
+    }
+    c->last_block_sums_ms = c->bed_len_ms + c->bed_emit_ms;
+    if (bytes_written) *bytes_written = bytes;
+    if (io) {
+        (void)hipStreamSynchronize(c->sA);                       // (what is still in flight lands in buffers the context keeps)
+        set_err(err, errlen, "beta2bed: write failed (errno %d): %s", io, strerror(io));
+        return WGBSSEG_E_IO;
+    }
+    if (lines_written) *lines_written = lines;
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_beta2bed_pass_ms(const wgbsseg_ctx* c, double* length_ms, double* emit_ms)
+{
+    if (length_ms) *length_ms = c ? c->bed_len_ms : 0.0;
+    if (emit_ms) *emit_ms = c ? c->bed_emit_ms : 0.0;
+}
+
+void wgbsseg_beta2bed_limits(int64_t* default_slab, int64_t* max_slab, int32_t* max_stage_bytes, int32_t* max_name)
+{
+    if (default_slab) *default_slab = WG_BED_DEFAULT_SLAB;
+    if (max_slab) *max_slab = WG_BED_MAX_SLAB;
+    if (max_stage_bytes) *max_stage_bytes = WG_BED_STAGE_BYTES;
+    if (max_name) *max_name = WG_BED_MAX_NAME;
 }
 
 int wgbsseg_add_loci(const uint32_t* loci, int64_t n_sites, const int64_t* chrom_cum, const char* const* chrom_names,
