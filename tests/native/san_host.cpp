@@ -1,5 +1,6 @@
 // Sanitizer harness for the host-side C++ of the library (TEST INFRASTRUCTURE): csrc/block_plan.h (the plan of a block reduction),
-// csrc/share_plan.h (the plan of a share group, its router and the rule of its streaming upload), csrc/stitch.h (chunk grid, junction rehearsal, pairwise trees on the thread pool, flattening) and csrc/add_loci.h (BED rows), driven by a toy chunk engine that is a pure
+// csrc/share_plan.h (the plan of a share group, its router and the rule of its streaming upload), csrc/bimodal_plan.h, csrc/homog_plan.h and
+// csrc/stats_plan.h (the plans of test_bimodal, homog and sample_stats), csrc/stitch.h (chunk grid, junction rehearsal, pairwise trees on the thread pool, flattening) and csrc/add_loci.h (BED rows), driven by a toy chunk engine that is a pure
 // function of the site range — as the real DP is — so that junction patches share borders with their chunks or, where the toy
 // makes them disagree, force the patch to double.  Built by tests/test_sanitizers_cpu.py three times (plain, ASan + UBSan,
 // TSan); every build must print the same checksum lines.
@@ -22,6 +23,9 @@
 #include "table_io.h"
 #include "block_plan.h"
 #include "share_plan.h"
+#include "bimodal_plan.h"
+#include "homog_plan.h"
+#include "stats_plan.h"
 
 static uint64_t mix(uint64_t x) { x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33; return x; }
 
@@ -310,12 +314,150 @@ static void share_plan_line()
            n_plans, n_idle, n_chunks_routed, n_routed, n_unroutable, n_hand, n_refused, n_items, n_subs, bad, (unsigned long long)h);
 }
 
+// The plans of the pat engines and of sample_stats (bimodal_plan.h, homog_plan.h, stats_plan.h) over the fixed tables of tests/test_patplan_cpu.py
+// (blocks that share an endCpG, nested ones, a startCpG within 150 sites of site 1, one block alone; ranges on every residue of a 16-byte vector, empty
+// ones, none, one tile of vectors and one more) and over seeded random ones; bimodal: the feed's walk - retire, drop, append one read per chunk - with
+// every table read where the engine reads it, and the scratch layout of each retired group; the refusals.  One line each: counts and a checksum.
+static void pat_plan_lines()
+{
+    uint64_t h = 1469598103934665603ULL;
+    auto fold = [&](uint64_t v) { h = (h ^ v) * 1099511628211ULL; };
+    auto fold_msg = [&](int rc, const std::string& m) { fold((uint64_t)(int64_t)rc); for (char ch : m) fold((uint64_t)(unsigned char)ch); };
+    typedef std::vector<int64_t> V;
+    std::vector<std::pair<V, V>> tables{{{400}, {420}}, {{300, 10, 250, 500}, {320, 320, 320, 501}}, {{100, 200, 210, 205, 900}, {1000, 300, 220, 206, 901}},
+                                        {{1, 150, 151, 152, 700}, {5, 160, 400, 153, 800}}, {{5, 2147483646}, {9, 2147483647}}};
+    for (uint64_t k = 0; k < 200; k++) {
+        const int64_t n_sites = 30 + (int64_t)(mix(k * 3 + 1) % 3000), nb = 1 + (int64_t)(mix(k * 3 + 2) % 40);
+        V s((size_t)nb), e((size_t)nb);
+        for (int64_t j = 0; j < nb; j++) { s[(size_t)j] = 1 + (int64_t)(mix(k * 1000 + (uint64_t)j) % (uint64_t)n_sites); e[(size_t)j] = s[(size_t)j] + 1 + (int64_t)(mix(k * 2000 + (uint64_t)j) % (k % 3 ? 30 : 1500)); }
+        if (nb > 2) e[1] = e[0] > s[1] ? e[0] : e[1];
+        tables.push_back({s, e});
+    }
+    // ---- bimodal
+    long n_ok = 0, n_refused = 0, n_retired = 0, bad = 0;
+    for (auto& t : tables) {
+        BimodalPlan p;
+        std::string msg;
+        const int64_t nb = (int64_t)t.first.size();
+        if (plan_bimodal(t.first.data(), t.second.data(), nb, 1, n_ok % 3 == 0 ? -1 : 16, p, msg) != WGBSSEG_OK) { bad++; continue; }
+        n_ok++;
+        for (int64_t j = 0; j < nb; j++) { fold((uint64_t)p.by_end[(size_t)j]); fold((uint64_t)p.lo_after[(size_t)j]); }
+        int64_t pending = 0;
+        long long last = WG_BIM_NONE;
+        const long long hi = t.second[(size_t)p.by_end[(size_t)nb - 1]] + 2, step = hi > 100000 ? hi / 997 : 1 + (long long)(mix((uint64_t)nb) % 7);
+        for (long long start = 1;; start += step) {                                  // one read per chunk, starts ascending past the last endCpG
+            const int64_t p1 = start > hi ? nb : p.retire_upto(pending, last);
+            bad += p1 < pending || p1 > nb;
+            if (p1 > pending) {
+                std::vector<wg_bim_meta> meta((size_t)(p1 - pending));
+                std::vector<long long> off(meta.size());
+                for (size_t g = 0; g < meta.size(); g++) meta[g] = {0, 0, 0, (long long)(mix((uint64_t)(pending + (int64_t)g)) % 600), (long long)(g % 3), 0};
+                size_t used = 0;
+                bad += wg_bim_scratch_layout(meta.data(), p.by_end.data() + pending, p1 - pending, p.lds_cols, off.data(), used, msg) != WGBSSEG_OK;
+                for (long long o : off) fold((uint64_t)o);
+                fold((uint64_t)used);
+                n_retired += (long)(p1 - pending);
+            }
+            pending = p1;
+            fold((uint64_t)p.drop_below(pending));
+            if (start > hi) break;
+            last = start;
+        }
+        bad += pending != nb;
+    }
+    {
+        const int64_t s[2] = {5, 0}, e[2] = {9, 4};
+        BimodalPlan p;
+        std::string msg;
+        for (int k = 0; k < 4; k++) {
+            const int rc = k == 0 ? plan_bimodal(s, e, 0, 1, -1, p, msg) : k == 1 ? plan_bimodal(nullptr, e, 2, 1, -1, p, msg) : k == 2 ? plan_bimodal(s, e, 2, 0, -1, p, msg) : plan_bimodal(s, e, 2, 1, -1, p, msg);
+            n_refused += rc == WGBSSEG_E_ARG && !msg.empty();
+            fold_msg(rc, msg);
+        }
+        const wg_bim_meta m[2] = {{0, 0, 0, 300, 5, 0}, {0, 0, 0, 300, 1ll << 31, 0}};
+        const int32_t ids[2] = {3, 8};
+        long long off[2];
+        size_t used = 0;
+        const int rc = wg_bim_scratch_layout(m, ids, 2, 16, off, used, msg);
+        n_refused += rc == WGBSSEG_E_CAPACITY;
+        fold_msg(rc, msg);
+        for (int64_t n : {(int64_t)1, (int64_t)5, (int64_t)6, (int64_t)4096, (int64_t)1 << 40}) { const BimodalChunkBound ub(n); fold(ub.lines); fold(ub.words); }
+    }
+    printf("bimodal_plan: %ld plans, %ld blocks retired, %ld refusals, %ld mismatches, checksum %016llx\n", n_ok, n_retired, n_refused, bad, (unsigned long long)h);
+    // ---- homog: the same tables in (startCpG, endCpG) order
+    h = 1469598103934665603ULL; n_ok = n_refused = bad = 0;
+    const float edges[4] = {0.0f, 0.25f, 0.75f, 1.0f}, flat[4] = {0.0f, 0.5f, 0.5f, 1.0f};
+    for (auto& t : tables) {
+        std::vector<std::pair<int64_t, int64_t>> rows;
+        for (size_t j = 0; j < t.first.size(); j++) rows.push_back({t.first[j], t.second[j]});
+        std::sort(rows.begin(), rows.end());
+        V s, e;
+        for (auto& r : rows) { s.push_back(r.first); e.push_back(r.second); }
+        HomogPlan p;
+        std::string msg;
+        if (plan_homog(s.data(), e.data(), (int64_t)s.size(), edges, 3, 1, p, msg) != WGBSSEG_OK) { bad++; continue; }
+        n_ok++;
+        for (size_t j = 0; j < s.size(); j++) { fold((uint64_t)p.s32[j]); fold((uint64_t)p.e32[j]); fold((uint64_t)p.pmax[j]); bad += p.pmax[j] < p.e32[j] || (j && p.pmax[j] < p.pmax[j - 1]); }
+        fold((uint64_t)p.last_end);
+    }
+    {
+        const int64_t s[2] = {5, 3}, e[2] = {9, 4}, z[2] = {0, 3}, r[2] = {5, 6}, re[2] = {5, 1ll << 31};
+        HomogPlan p;
+        std::string msg;
+        for (int k = 0; k < 8; k++) {
+            const int rc = k == 0 ? plan_homog(s, e, 0, edges, 3, 1, p, msg) : k == 1 ? plan_homog(s, e, 1, nullptr, 3, 1, p, msg) : k == 2 ? plan_homog(s, e, 1, edges, 9, 1, p, msg)
+                         : k == 3 ? plan_homog(s, e, 1, flat, 3, 1, p, msg) : k == 4 ? plan_homog(s, e, 1, edges, 3, 0, p, msg) : k == 5 ? plan_homog(z, e, 2, edges, 3, 1, p, msg)
+                         : k == 6 ? plan_homog(r, re, 2, edges, 3, 1, p, msg) : plan_homog(s, e, 2, edges, 3, 1, p, msg);
+            n_refused += rc == WGBSSEG_E_ARG && !msg.empty();
+            fold_msg(rc, msg);
+        }
+    }
+    printf("homog_plan: %ld plans, %ld refusals, %ld mismatches, checksum %016llx\n", n_ok, n_refused, bad, (unsigned long long)h);
+    // ---- sample_stats: both row widths
+    h = 1469598103934665603ULL; n_ok = n_refused = bad = 0;
+    std::vector<std::pair<V, V>> ranges{{{}, {}}, {{0, 5, 5, 1000}, {0, 5, 5, 1000}}, {{0, 4}, {4, 8}}, {{0}, {WG_ST_TILE * 8}}, {{0}, {WG_ST_TILE * 8 + 1}}, {{3, 90000}, {3 + WG_ST_TILE * 4 - 4, 90001}}};
+    for (int64_t a = 0; a < 16; a++) for (int64_t b = a; b <= 33; b++) ranges.push_back({{a, b, b}, {b, b, 34}});
+    for (uint64_t k = 0; k < 200; k++) {
+        V cuts;
+        for (uint64_t j = 0; j < 2 * (mix(k + 77) % 25); j++) cuts.push_back((int64_t)(mix(k * 100 + j) % 40001));
+        std::sort(cuts.begin(), cuts.end());
+        V a, b;
+        for (size_t j = 0; j + 1 < cuts.size(); j += 2) { a.push_back(cuts[j]); b.push_back(cuts[j + 1]); }
+        ranges.push_back({a, b});
+    }
+    for (auto& t : ranges)
+        for (int elem = 1; elem <= 2; elem++) {
+            StatsPlan p;
+            std::string msg;
+            if (plan_sample_stats(t.first.data(), t.second.data(), (int64_t)t.first.size(), 1 << 20, elem, 3, p, msg) != WGBSSEG_OK) { bad++; continue; }
+            n_ok++;
+            const StatsPlan::View<const int64_t> v = p.view((const int64_t*)p.upload.data());
+            for (int64_t i = 0; i < p.n_ranges; i++) { fold((uint64_t)v.x0[i]); fold((uint64_t)v.x1[i]); fold((uint64_t)v.cumv[i]); bad += v.cumv[i + 1] < v.cumv[i]; }
+            bad += v.cumv[p.n_ranges] != p.n_vec || p.upload.size() != (size_t)p.n_ranges * 3 + 1;
+            fold((uint64_t)p.n_sites); fold((uint64_t)p.n_vec); fold((uint64_t)p.n_tiles);
+        }
+    {
+        const int64_t a[2] = {0, 3}, b[2] = {4, 9}, neg[1] = {-1}, big[1] = {(1ll << 20) + 1};
+        StatsPlan p;
+        std::string msg;
+        for (int k = 0; k < 6; k++) {
+            const int rc = k == 0 ? plan_sample_stats(a, b, -1, 1 << 20, 1, 3, p, msg) : k == 1 ? plan_sample_stats(nullptr, b, 2, 1 << 20, 1, 3, p, msg)
+                         : k == 2 ? plan_sample_stats(neg, b, 1, 1 << 20, 1, 3, p, msg) : k == 3 ? plan_sample_stats(a, big, 1, 1 << 20, 2, 3, p, msg)
+                         : k == 4 ? plan_sample_stats(a, b, 2, 1 << 20, 1, 3, p, msg) : plan_sample_stats(a, b, 1, 1 << 20, 1, 65536, p, msg);
+            n_refused += rc == WGBSSEG_E_ARG && !msg.empty();
+            fold_msg(rc, msg);
+        }
+    }
+    printf("stats_plan: %ld plans, %ld refusals, %ld mismatches, checksum %016llx\n", n_ok, n_refused, bad, (unsigned long long)h);
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 3) { fprintf(stderr, "usage: san_host <threads> <out.bed>\n"); return 2; }
     setenv("WGBSSEG_STITCH_THREADS", argv[1], 1);
     block_plan_line();
     share_plan_line();
+    pat_plan_lines();
     std::vector<int64_t> s, e;
     for (int rep = 0; rep < 3; rep++) {                                      // the pool is reused across calls
         std::vector<int64_t> s1, e1;

@@ -223,12 +223,13 @@ def test_column_terms_match_the_host_twin():
     assert not any(bad.values()), (bad, first)
 
 
-@pytest.mark.parametrize('chunk', ['whole', 4096, 300])
+@pytest.mark.parametrize('chunk', ['whole', 4096, 300, 1])
 @pytest.mark.parametrize('cols', [-1, 0, 16])
 @pytest.mark.parametrize('name', sorted(BK.cases()))
 def test_corner_cases_match_restatement(name, cols, chunk):
     """each hand-built corner (tests/test_bimodal_cpu.py checks that the case reaches it), on the default tables, with every block
-    on global memory and with LDS tables of 16 columns; the text fed whole and in chunks of about 4 KB and 300 B"""
+    on global memory and with LDS tables of 16 columns; the text fed whole, in chunks of about 4 KB and 300 B, and one line per
+    call (chunk 1: a retire and a drop between every two reads)"""
     c = BK.cases()[name]
     s, e = np.array(c['s']), np.array(c['e'])
     with _lib.Bimodal(s, e, c['strict'], c['min_len'], max_lds_cols=cols) as b:

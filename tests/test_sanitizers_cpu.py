@@ -1,5 +1,5 @@
 """Sanitizer builds of the host-side native code (the reference has none; its `segmentor` has a real UB at max_bp == 0):
-csrc/block_plan.h (the plan of a block reduction), csrc/share_plan.h (the plan of a share group, its router, its take rule), csrc/stitch.h + csrc/add_loci.h (chunk grid, junction stitching on the thread pool, BED rows)
+csrc/block_plan.h (the plan of a block reduction), csrc/share_plan.h (the plan of a share group, its router, its take rule), csrc/bimodal_plan.h + csrc/homog_plan.h + csrc/stats_plan.h (the plans of test_bimodal, homog and sample_stats), csrc/stitch.h + csrc/add_loci.h (chunk grid, junction stitching on the thread pool, BED rows)
 and the oracle's C restatement of the
 chunk DP, each compiled plain, with AddressSanitizer + UndefinedBehaviorSanitizer, and with ThreadSanitizer, and run on
 deterministic toy inputs: every build must finish clean and print the same lines."""
@@ -67,6 +67,13 @@ def test_stitching_and_bed_rows_under_sanitizers(tmp_path):
     # 64 shares over at most 62 chunks and the zero weights leave shares idle; the +-50 ranges outgrow the halo of 10; the middle share of three takes
     # two items per chunk and four junction ranges, in more than one sub-batch per walk and (min_take 1: one per distinct last site) fewer than items per walk
     assert idle >= len(worlds) * 4 * 2 and routed > 0 and unroutable > 0 and items > 4 and items % 2 == 0 and 3 < subs < 3 * items
+    # the plans of the pat engines and of sample_stats: 5 fixed and 200 seeded block tables (test_bimodal: every block of every table retired once, by
+    # the feed's walk or at the end), 6 + 424 + 200 range lists for both row widths; every refusal refused
+    pat = {l.split(':')[0]: l for l in ref[0].splitlines() if l.split(':')[0] in ('bimodal_plan', 'homog_plan', 'stats_plan')}
+    m = re.match(r'bimodal_plan: 205 plans, (\d+) blocks retired, 5 refusals, 0 mismatches, checksum ', pat['bimodal_plan'])
+    assert m and int(m.group(1)) > 205 * 5
+    assert pat['homog_plan'].startswith('homog_plan: 205 plans, 8 refusals, 0 mismatches, checksum ')
+    assert pat['stats_plan'].startswith('stats_plan: %d plans, 6 refusals, 0 mismatches, checksum ' % (2 * (6 + sum(34 - a for a in range(16)) + 200)))
     assert 'sitetable: ' in ref[0] and 'mismatches 0, concurrent misses 0' in ref[0]
     assert 'parse_blocks: rc 0 rows 40000 na 413' in ref[0] and 'parse_blocks on a float field: rc 1' in ref[0]
     assert ref[0].count('write_table pass') == 2 and 'DIFFERS' not in ref[0] and 'write_bedgraph: rc 0' in ref[0]

@@ -13,8 +13,8 @@
 //           next chunk.  Reads starting before the lowest max(1, s1 - 150) of the blocks still pending are then dropped
 //           (k_bim_drop_find / k_bim_drop_copy), so the table holds the live window, not the file.
 //   EM      k_bim_em: one wavefront per block.  The four log2 tables of the block's columns (32 B per column) and the
-//           per-cluster C / T column counts (16 B per column) live in LDS up to WG_BIM_LDS_COLS columns, in global scratch
-//           beyond (the host sizes it from k_bim_gather's column counts).  Lanes take one pat line each; a line stands for
+//           per-cluster C / T column counts (16 B per column; WG_BIM_COL_BYTES in all) live in LDS up to WG_BIM_LDS_COLS columns,
+//           in global scratch beyond (the host sizes it from k_bim_gather's column counts: wg_bim_scratch_layout).  Lanes take one pat line each; a line stands for
 //           `count` identical rows, so its log-likelihoods are computed once.  The column counts are integer atomics
 //           (exact in any order).  Every sum the stopping test depends on is taken in the reference's order by the whole
 //           wavefront in lock-step from shuffled values: ll0 over columns left to right, each cluster's new_ll over rows in
@@ -29,28 +29,10 @@
 //            l_p = log2(p / (p_c + p_t)); the first pass uses p_c = {0.9, 0.1}, p_t = 1 - p_c.
 #pragma once
 #include "pat_kernels.h"
+#include "bimodal_plan.h"      // WG_BIM_LDS_COLS, WG_BIM_COL_BYTES, WG_BIM_MAX_ITERS, WG_BIM_CTX, WG_BIM_NONE, wg_bim_state, wg_bim_meta
 
 #define WG_BIM_WAVE 64
-#define WG_BIM_LDS_COLS 256           // LDS path: 256 columns x 48 B = 12 KiB per wavefront (13 wavefronts per CU by LDS)
-#define WG_BIM_MAX_ITERS 100000       // the reference has no cap: a strictly rising sequence over finitely many assignments ends
-#define WG_BIM_CTX 150                // MAX_PAT_LEN (utils_wgbs.py:38): how far before s1 the reference's tabix query starts
-#define WG_BIM_NONE ((long long)INT64_MIN)
-
-// device-side state of a bimodal run (one per accumulator)
-struct wg_bim_state {
-    long long R, W;                   // live reads / pattern words in the current table
-    long long R0;                     // R before the last chunk was appended
-    long long last_start;             // start of the last read seen (WG_BIM_NONE: none yet)
-    long long head, whead;            // reads / words dropped by the last k_bim_drop_find
-    unsigned long long bad, neg, desc;      // lowest byte offsets: malformed line, negative count, descending start (~0: none)
-    unsigned long long em_cap;        // a block that reached WG_BIM_MAX_ITERS (its index + 1; 0: none)
-};
-
-// per retired block, from k_bim_gather
-struct wg_bim_meta {
-    long long ra, rb;                 // table rows with start in [max(1, s1 - 150), s2 - 1]
-    long long first_ind, ncols, rows, lines;
-};
+static_assert(WG_BIM_COL_BYTES == 4 * sizeof(double) + 4 * sizeof(uint32_t), "k_bim_em's lp | cn tables per column are what the host lays out in scratch");
 
 // the reference's acceptance of a read for block [s1, s2) (read_pat_vis :35-56): false when skipped; else its clipped start / length
 __device__ __forceinline__ bool wg_bim_accept(long long st, long long len, long long s1, long long s2, int strict, int min_len,

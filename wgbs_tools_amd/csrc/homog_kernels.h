@@ -35,11 +35,10 @@
 // device memory (prev_in / prev_out: two slots alternating per chunk).
 #pragma once
 #include "pat_kernels.h"
+#include "homog_plan.h"      // WG_HOMOG_MAX_BINS, WG_HOMOG_NO_SITE
 
-#define WG_HOMOG_MAX_BINS 8
 #define WG_HOMOG_WIN 512
 #define WG_HOMOG_CELLS 2048
-#define WG_HOMOG_NO_SITE ((long long)INT64_MIN)
 
 // the bin of (nrC, nrT) (update_m2, homog.cpp:154-183); -1 when meth < range[0]
 __device__ __forceinline__ int wg_homog_bin(int nrc, int nrt, const float* range, int nb)

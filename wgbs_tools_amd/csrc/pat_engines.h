@@ -1,0 +1,549 @@
+// pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_bimodal), the feed they share
+// and their extern "C" entry points.  Part of wgbsseg.hip, which includes it once set_err, HIP_TRY, check_device and the owners are
+// in scope; what an engine decides on the host is in homog_plan.h and bimodal_plan.h, this file stages, launches and fetches.
+#pragma once
+
+// The pat-text feed of an engine (wgbsseg_patbeta / _homog / _bimodal): one device and stream; text chunks through two page-locked
+// staging buffers and two device buffers, so that the caller's decompression of chunk k+1 overlaps the copy and the kernels of
+// chunk k; the input offset of the next chunk; and the device time of the launches the engine brackets with span_begin / span_end.
+// Teardown: an engine's buffers — its own and the feed's — must not go while the stream may still use them.  Members go in reverse order of
+// declaration and an engine's `feed` comes first, so declaration order alone would free the engine's buffers before the feed had a say: every
+// engine's destructor calls drain() instead (explicit, one line each), and so does the feed's own for the buffers it holds itself.
+struct PatFeed {
+    int device = 0;
+    Stream st;                                                    // (declared first: goes last)
+    PinnedBuf stage[2];
+    DevBuf text[2];
+    Event ev[2];                                                  // after the work on slot k's text
+    bool busy[2] = {false, false};
+    int k = 0;                                                    // the slot of the next chunk
+    unsigned long long fed = 0;                                   // bytes fed so far
+    double span_ms = 0.0;                                         // the spans read so far
+    std::deque<std::pair<Event, Event>> spans;                    // recorded, in stream order, not read yet
+    std::vector<Event> spare;                                     // the events of read spans, for the next ones
+
+    int open(int dev, char* err, size_t errlen)
+    {
+        const int rc = check_device(dev, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        device = dev;
+        HIP_TRY(st.create());
+        for (auto& e : ev) HIP_TRY(e.create(false));
+        return WGBSSEG_OK;
+    }
+    void drain()                                                  // the stream has passed everything queued on it, the spans are read: buffers may go
+    {
+        (void)hipSetDevice(device);
+        if (st) (void)hipStreamSynchronize(st);
+        collect();
+    }
+    ~PatFeed() { drain(); }
+    // the checks of a feed call: -1 when refused (err set), 0 for an empty chunk, else the chunk's number of tiles
+    static int64_t tiles(const char* name, const void* engine, const char* text, int64_t n_bytes, char* err, size_t errlen)
+    {
+        if (!engine || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to %s_feed", name); return -1; }
+        if (n_bytes == 0) return 0;
+        if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "%s_feed: a chunk must end with a complete line", name); return -1; }
+        const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;     // one workgroup per tile of text
+        if (gx > 0x7fffffff) { set_err(err, errlen, "%s_feed: chunk too large", name); return -1; }
+        return gx;
+    }
+    // waits until the chunk before last (same slot) has been consumed, then queues the copy of this one; *dev: its device copy
+    int stage_chunk(const char* host, int64_t n_bytes, const char** dev, char* err, size_t errlen)
+    {
+        if (busy[k]) { HIP_TRY(hipEventSynchronize(ev[k])); collect(); }
+        if (!stage[k].ensure((size_t)n_bytes)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+        HIP_TRY(text[k].ensure((size_t)n_bytes));
+        memcpy(stage[k].p, host, (size_t)n_bytes);
+        HIP_TRY(hipMemcpyAsync(text[k].p, stage[k].p, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+        *dev = text[k].as<char>();
+        return WGBSSEG_OK;
+    }
+    // the chunk's work has been queued: the slot is busy until the stream passes here
+    hipError_t chunk_queued(int64_t n_bytes)
+    {
+        const hipError_t e = hipEventRecord(ev[k], st);
+        busy[k] = true;
+        k ^= 1;
+        fed += (unsigned long long)n_bytes;
+        return e;
+    }
+    hipError_t span_begin()
+    {
+        Event e[2];
+        for (auto& x : e) {
+            if (!spare.empty()) { x = std::move(spare.back()); spare.pop_back(); continue; }
+            const hipError_t r = x.create();
+            if (r != hipSuccess) return r;
+        }
+        spans.emplace_back(std::move(e[0]), std::move(e[1]));
+        return hipEventRecord(spans.back().first, st);
+    }
+    hipError_t span_end() { return hipEventRecord(spans.back().second, st); }
+    // A feed call of an engine whose chunk is one launch: the checks, the chunk's copy, `before` (untimed stream work in front of the
+    // launch), then launch(tiles, device text) as one timed span.  Neither is called for a chunk that is refused or empty.
+    template <class Engine, class Before, class Launch>
+    static int one_launch(const char* name, Engine* e, const char* host, int64_t n_bytes, char* err, size_t errlen, Before&& before, Launch&& launch)
+    {
+        const int64_t gx = tiles(name, e, host, n_bytes, err, errlen);
+        if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
+        PatFeed& f = e->feed;
+        HIP_TRY(hipSetDevice(f.device));
+        const char* dtext = nullptr;
+        const int rc = f.stage_chunk(host, n_bytes, &dtext, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        HIP_TRY(before());
+        HIP_TRY(f.span_begin());
+        launch((unsigned)gx, dtext);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(f.span_end());
+        HIP_TRY(f.chunk_queued(n_bytes));
+        return WGBSSEG_OK;
+    }
+    // adds the spans the stream has passed to span_ms (in order: the first one still running ends the walk)
+    void collect()
+    {
+        while (!spans.empty()) {
+            float ms = 0.f;
+            const hipError_t e = hipEventElapsedTime(&ms, spans.front().first, spans.front().second);
+            if (e == hipErrorNotReady) break;
+            if (e == hipSuccess) span_ms += (double)ms;
+            spare.push_back(std::move(spans.front().first)); spare.push_back(std::move(spans.front().second));
+            spans.pop_front();
+        }
+    }
+    double kernel_ms()                                            // waits for the stream; -1 on a HIP error
+    {
+        if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1.0;
+        collect();
+        return span_ms;
+    }
+};
+
+// the refusals of the input that the pat engines share, "<prefix> <what> at byte offset <off> ..."; false when off is ~0 (none)
+enum class PatRefusal { bad_line, unsorted };
+static bool pat_refused(PatRefusal why, unsigned long long off, const char* prefix, char* err, size_t errlen)
+{
+    if (off == ~0ULL) return false;
+    if (why == PatRefusal::bad_line)
+        set_err(err, errlen, "%s invalid line at byte offset %llu of the input (too few columns, or a site / count that is not a number)", prefix, off);
+    else
+        set_err(err, errlen, "%s the pat file is not sorted: the read at byte offset %llu of the input starts before the read before it", prefix, off);
+    return true;
+}
+
+// pat -> beta accumulator: counts on one device; k_pat_count is timed.
+struct wgbsseg_patbeta {
+    PatFeed feed;
+    int64_t start = 1, end = 1;
+    DevBuf meth, cov, outb, bad;
+    ~wgbsseg_patbeta() { feed.drain(); }
+};
+
+extern "C" {
+
+int wgbsseg_patbeta_create(int device, int64_t start_cpg, int64_t end_cpg, wgbsseg_patbeta** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    if (start_cpg < 1 || end_cpg <= start_cpg || end_cpg - start_cpg > 0x7fffffff) { set_err(err, errlen, "patbeta: bad CpG range [%lld, %lld)", (long long)start_cpg, (long long)end_cpg); return WGBSSEG_E_ARG; }
+    std::unique_ptr<wgbsseg_patbeta> p(new (std::nothrow) wgbsseg_patbeta());      // (a failing call below frees what has been made)
+    if (!p) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    const int rc = p->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    p->start = start_cpg; p->end = end_cpg;
+    const size_t nb = (size_t)(end_cpg - start_cpg) * 4;
+    HIP_TRY(p->meth.ensure(nb)); HIP_TRY(p->cov.ensure(nb)); HIP_TRY(p->bad.ensure(8));
+    HIP_TRY(hipMemsetAsync(p->meth.p, 0, nb, p->feed.st));       // (the reference leaves its arrays uninitialised: stdin2beta.cpp:48-49)
+    HIP_TRY(hipMemsetAsync(p->cov.p, 0, nb, p->feed.st));
+    HIP_TRY(hipMemsetAsync(p->bad.p, 0xff, 8, p->feed.st));
+    *out = p.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_patbeta_destroy(wgbsseg_patbeta* p) { delete p; }
+
+int wgbsseg_patbeta_feed(wgbsseg_patbeta* p, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    return PatFeed::one_launch("patbeta", p, text, n_bytes, err, errlen, [] { return hipSuccess; }, [&](unsigned gx, const char* dtext) {
+        hipLaunchKernelGGL(k_pat_count, dim3(gx), dim3(WG_BLOCK), 0, p->feed.st, dtext, n_bytes, p->start, p->end,
+                           p->meth.as<int32_t>(), p->cov.as<int32_t>(), p->bad.as<unsigned long long>(), p->feed.fed);
+    });
+}
+
+int wgbsseg_patbeta_finish(wgbsseg_patbeta* p, int32_t lbeta, void* out, char* err, size_t errlen)
+{
+    if (!p || !out) { set_err(err, errlen, "bad arguments to patbeta_finish"); return WGBSSEG_E_ARG; }
+    const hipStream_t st = p->feed.st;
+    HIP_TRY(hipSetDevice(p->feed.device));
+    const int64_t n = p->end - p->start;
+    const size_t ob = (size_t)n * (lbeta ? 4 : 2);
+    HIP_TRY(p->outb.ensure(ob));
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, p->bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (pat_refused(PatRefusal::bad_line, bad, "failed calculating beta:", err, errlen)) return WGBSSEG_E_ARG;
+    hipLaunchKernelGGL(k_pat_trim, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, p->meth.as<int32_t>(), p->cov.as<int32_t>(), n,
+                       (int)lbeta, p->outb.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, p->outb.p, ob, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_patbeta_kernel_ms(wgbsseg_patbeta* p)
+{
+    return p ? p->feed.kernel_ms() : -1.0;
+}
+
+}  // extern "C"
+
+// `wgbstools homog` accumulator: (block, bin) read counts on one device; k_homog_count is timed.
+struct wgbsseg_homog {
+    PatFeed feed;
+    int64_t n_blocks = 0, last_end = 0;
+    int n_bins = 0, min_cpgs = 0, inclusive = 0;
+    DevBuf bstart, bend, bpmax, range, counts, bad, desc, prev;
+    unsigned long long chunks = 0;
+    ~wgbsseg_homog() { feed.drain(); }
+};
+
+extern "C" {
+
+// plan (homog_plan.h) -> the tables and the edges on the device, the counters cleared
+int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, const float* range, int32_t n_bins,
+                         int32_t min_cpgs, int32_t inclusive, wgbsseg_homog** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    HomogPlan plan;
+    std::string msg;
+    int rc = plan_homog(start_cpg, end_cpg, n_blocks, range, n_bins, min_cpgs, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    std::unique_ptr<wgbsseg_homog> h(new (std::nothrow) wgbsseg_homog());      // (a failing call below frees what has been made)
+    if (!h) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    rc = h->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    h->n_blocks = n_blocks; h->last_end = plan.last_end;
+    h->n_bins = n_bins; h->min_cpgs = min_cpgs; h->inclusive = inclusive ? 1 : 0;
+    const hipStream_t st = h->feed.st;
+    const size_t nb4 = (size_t)n_blocks * 4, cb = (size_t)n_blocks * (size_t)n_bins * 4;
+    HIP_TRY(h->bstart.ensure(nb4)); HIP_TRY(h->bend.ensure(nb4)); HIP_TRY(h->bpmax.ensure(nb4));
+    HIP_TRY(h->range.ensure(sizeof(float) * (size_t)(n_bins + 1))); HIP_TRY(h->counts.ensure(cb));
+    HIP_TRY(h->bad.ensure(8)); HIP_TRY(h->desc.ensure(8)); HIP_TRY(h->prev.ensure(16));
+    HIP_TRY(hipMemcpy(h->bstart.p, plan.s32.data(), nb4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->bend.p, plan.e32.data(), nb4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->bpmax.p, plan.pmax.data(), nb4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->range.p, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice));
+    const long long none[2] = {WG_HOMOG_NO_SITE, WG_HOMOG_NO_SITE};
+    HIP_TRY(hipMemcpy(h->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(h->counts.p, 0, cb, st));
+    HIP_TRY(hipMemsetAsync(h->bad.p, 0xff, 8, st));
+    HIP_TRY(hipMemsetAsync(h->desc.p, 0xff, 8, st));
+    *out = h.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_homog_destroy(wgbsseg_homog* h) { delete h; }
+
+int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
+    long long *in = nullptr, *out = nullptr;
+    return PatFeed::one_launch("homog", h, text, n_bytes, err, errlen,
+        [&] {
+            out = h->prev.as<long long>() + (h->chunks & 1); in = h->prev.as<long long>() + ((h->chunks & 1) ^ 1);
+            return hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, h->feed.st);
+        },
+        [&](unsigned gx, const char* dtext) {
+            hipLaunchKernelGGL(k_homog_count, dim3(gx), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes,
+                               h->bstart.as<int32_t>(), h->bend.as<int32_t>(), h->bpmax.as<int32_t>(), h->n_blocks, h->last_end,
+                               h->range.as<float>(), h->n_bins, h->min_cpgs, h->inclusive, h->counts.as<int32_t>(),
+                               h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), in, out, h->feed.fed);
+            h->chunks += 1;                                       // (the slots swap for the next chunk)
+        });
+}
+
+int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t errlen)
+{
+    if (!h || !counts) { set_err(err, errlen, "bad arguments to homog_finish"); return WGBSSEG_E_ARG; }
+    const hipStream_t st = h->feed.st;
+    HIP_TRY(hipSetDevice(h->feed.device));
+    unsigned long long bad = 0, desc = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&desc, h->desc.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (pat_refused(PatRefusal::bad_line, bad, "failed calculating homog:", err, errlen)) return WGBSSEG_E_ARG;
+    if (pat_refused(PatRefusal::unsorted, desc, "failed calculating homog:", err, errlen)) return WGBSSEG_E_ARG;
+    HIP_TRY(hipMemcpyAsync(counts, h->counts.p, (size_t)h->n_blocks * (size_t)h->n_bins * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_homog_kernel_ms(wgbsseg_homog* h)
+{
+    return h ? h->feed.kernel_ms() : -1.0;
+}
+
+int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_total, int8_t* out)
+{
+    if (!range || !out || n_bins < 1 || n_bins > WG_HOMOG_MAX_BINS || max_total < 0 || max_total > 65535) return WGBSSEG_E_ARG;
+    char err[256];
+    const size_t errlen = sizeof(err);
+    const int64_t n = (int64_t)(max_total + 1) * (max_total + 2) / 2;
+    DevBuf d_range, d_out;
+    HIP_TRY(d_range.ensure(sizeof(float) * (size_t)(n_bins + 1)));
+    HIP_TRY(d_out.ensure((size_t)n));
+    HIP_TRY(hipMemcpy(d_range.p, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_homog_bins, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, 0, d_range.as<float>(), (int)n_bins, (int)max_total, d_out.as<int8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out.p, (size_t)n, hipMemcpyDeviceToHost));
+    return WGBSSEG_OK;
+}
+
+int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t count, uint64_t* out)
+{
+    if (!a || !b || !out || count < 1 || count > (1ll << 28)) return WGBSSEG_E_ARG;
+    char err[256];
+    const size_t errlen = sizeof(err);
+    DevBuf d_ab, d_out;
+    HIP_TRY(d_ab.ensure(2 * sizeof(uint32_t) * (size_t)count));
+    HIP_TRY(d_out.ensure(6 * sizeof(uint64_t) * (size_t)count));
+    uint32_t* const ab = d_ab.as<uint32_t>();
+    HIP_TRY(hipMemcpy(ab, a, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ab + count, b, sizeof(uint32_t) * (size_t)count, hipMemcpyHostToDevice));
+    const unsigned blocks = (unsigned)std::min<int64_t>((count + WG_BLOCK - 1) / WG_BLOCK, 16384);
+    hipLaunchKernelGGL(k_bim_debug_terms, dim3(blocks), dim3(WG_BLOCK), 0, 0, ab, ab + count, count, d_out.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out.p, 6 * sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost));
+    return WGBSSEG_OK;
+}
+
+}  // extern "C"
+
+// `wgbstools test_bimodal` accumulator on one device: the plan of the blocks (bimodal_plan.h), the read table of the live window (two
+// copies: dropping moves the live rows from one to the other), and the per-block results.  A feed() first waits for the work of the
+// previous chunk (the caller inflated this chunk meanwhile), retires the blocks that chunk completed, drops the reads no pending block
+// can reach, and queues the parse of this chunk; the EM of the retired blocks runs while the caller inflates the next one.  Every
+// launch is timed.
+struct wgbsseg_bimodal {
+    struct Table { DevBuf start, len, cnt, woff, words; };
+    PatFeed feed;
+    BimodalPlan plan;
+    int strict = 0, min_len = 1;
+    int64_t pending = 0;                          // plan.by_end[pending..] have not been retired
+    DevBuf bs1, bs2, ids, meta, scr_off, scratch, res_f, res_i, state, tile_cnt, tile_base, pos;
+    Table tab[2];
+    int cur = 0;
+    size_t cap_rows = 0, cap_words = 0;
+    PinnedBuf host_state, host_meta, host_off;
+    bool stop = false;                            // an input error was seen: nothing more is computed
+    wg_bim_state* hs() const { return reinterpret_cast<wg_bim_state*>(host_state.p); }
+    ~wgbsseg_bimodal() { feed.drain(); }
+};
+
+static int bim_sync_state(wgbsseg_bimodal* b, char* err, size_t errlen)
+{
+    HIP_TRY(hipMemcpyAsync(b->host_state.p, b->state.p, sizeof(wg_bim_state), hipMemcpyDeviceToHost, b->feed.st));
+    HIP_TRY(hipStreamSynchronize(b->feed.st));
+    b->feed.collect();
+    const wg_bim_state* s = b->hs();
+    if (s->bad != ~0ULL || s->neg != ~0ULL || s->desc != ~0ULL || s->em_cap) b->stop = true;
+    return WGBSSEG_OK;
+}
+
+// both tables hold at least `rows` reads and `words` words; the live rows of the current one are kept (the stream is idle)
+static int bim_reserve(wgbsseg_bimodal* b, size_t rows, size_t words, char* err, size_t errlen)
+{
+    if (rows <= b->cap_rows && words <= b->cap_words) return WGBSSEG_OK;
+    const size_t nr = std::max(rows, 2 * b->cap_rows), nw = std::max(words, 2 * b->cap_words);
+    const size_t R = (size_t)b->hs()->R, W = (size_t)b->hs()->W;
+    for (int t = 0; t < 2; t++) {
+        wgbsseg_bimodal::Table fresh;
+        HIP_TRY(fresh.start.ensure(nr * 4)); HIP_TRY(fresh.len.ensure(nr * 4)); HIP_TRY(fresh.cnt.ensure(nr * 4));
+        HIP_TRY(fresh.woff.ensure(nr * 8)); HIP_TRY(fresh.words.ensure(nw * 4));
+        wgbsseg_bimodal::Table& old = b->tab[t];
+        if (t == b->cur && R) {
+            HIP_TRY(hipMemcpy(fresh.start.p, old.start.p, R * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(fresh.len.p, old.len.p, R * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(fresh.cnt.p, old.cnt.p, R * 4, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(fresh.woff.p, old.woff.p, R * 8, hipMemcpyDeviceToDevice));
+        }
+        if (t == b->cur && W) HIP_TRY(hipMemcpy(fresh.words.p, old.words.p, W * 4, hipMemcpyDeviceToDevice));
+        old = std::move(fresh);                                 // (the old table's buffers go here)
+    }
+    b->cap_rows = nr; b->cap_words = nw;
+    return WGBSSEG_OK;
+}
+
+// the EM of by_end[pending .. p1): their rows and columns, scratch for the wide ones, then k_bim_em (queued, not waited for)
+static int bim_retire(wgbsseg_bimodal* b, int64_t p1, char* err, size_t errlen)
+{
+    const int64_t n = p1 - b->pending;
+    if (n <= 0 || b->stop) return WGBSSEG_OK;
+    wgbsseg_bimodal::Table& T = b->tab[b->cur];
+    const int32_t* ids = b->plan.by_end.data() + b->pending;
+    HIP_TRY(hipMemcpyAsync(b->ids.as<int32_t>(), ids, (size_t)n * 4, hipMemcpyHostToDevice, b->feed.st));
+    HIP_TRY(b->feed.span_begin());
+    hipLaunchKernelGGL(k_bim_gather, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->feed.st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
+                       b->state.as<wg_bim_state>(), b->bs1.as<int32_t>(), b->bs2.as<int32_t>(), b->ids.as<int32_t>(), b->strict, b->min_len,
+                       b->meta.as<wg_bim_meta>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(b->feed.span_end());
+    if (!b->host_meta.ensure((size_t)n * sizeof(wg_bim_meta))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    HIP_TRY(hipMemcpyAsync(b->host_meta.p, b->meta.p, (size_t)n * sizeof(wg_bim_meta), hipMemcpyDeviceToHost, b->feed.st));
+    HIP_TRY(hipStreamSynchronize(b->feed.st));
+    if (!b->host_off.ensure((size_t)n * 8)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    long long* off = reinterpret_cast<long long*>(b->host_off.p);     // (read by the copy below after this returns: the next use waits for the stream)
+    size_t used = 0;
+    std::string msg;
+    const int rc = wg_bim_scratch_layout(reinterpret_cast<const wg_bim_meta*>(b->host_meta.p), ids, n, b->plan.lds_cols, off, used, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    if (used) HIP_TRY(b->scratch.ensure(used));
+    HIP_TRY(hipMemcpyAsync(b->scr_off.p, off, (size_t)n * 8, hipMemcpyHostToDevice, b->feed.st));
+    HIP_TRY(b->feed.span_begin());
+    hipLaunchKernelGGL(k_bim_em, dim3((unsigned)n), dim3(WG_BIM_WAVE), 0, b->feed.st, T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(),
+                       T.woff.as<long long>(), T.words.as<uint32_t>(), b->bs1.as<int32_t>(), b->bs2.as<int32_t>(), b->ids.as<int32_t>(),
+                       b->meta.as<wg_bim_meta>(), b->scr_off.as<long long>(), b->scratch.as<unsigned char>(), b->plan.lds_cols, b->strict, b->min_len,
+                       b->res_f.as<double>(), b->res_i.as<long long>(), b->state.as<wg_bim_state>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(b->feed.span_end());
+    b->pending = p1;
+    return WGBSSEG_OK;
+}
+
+// the reads no pending block can reach go: the live rows of the s.R reads / s.W words move into the other table, which becomes the current one
+static int bim_drop(wgbsseg_bimodal* b, const wg_bim_state& s, char* err, size_t errlen)
+{
+    PatFeed& f = b->feed;
+    wgbsseg_bimodal::Table &A = b->tab[b->cur], &B = b->tab[b->cur ^ 1];
+    HIP_TRY(f.span_begin());
+    hipLaunchKernelGGL(k_bim_drop_find, dim3(1), dim3(1), 0, f.st, A.start.as<int32_t>(), A.woff.as<long long>(), b->state.as<wg_bim_state>(),
+                       b->plan.drop_below(b->pending));
+    const long long big = std::max<long long>(s.R, s.W);
+    hipLaunchKernelGGL(k_bim_drop_copy, dim3((unsigned)((big + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, f.st,
+                       A.start.as<int32_t>(), A.len.as<int32_t>(), A.cnt.as<int32_t>(), A.woff.as<long long>(), A.words.as<uint32_t>(),
+                       B.start.as<int32_t>(), B.len.as<int32_t>(), B.cnt.as<int32_t>(), B.woff.as<long long>(), B.words.as<uint32_t>(),
+                       b->state.as<wg_bim_state>(), (long long)s.R, (long long)s.W);
+    hipLaunchKernelGGL(k_bim_drop_done, dim3(1), dim3(1), 0, f.st, b->state.as<wg_bim_state>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(f.span_end());
+    b->cur ^= 1;
+    return WGBSSEG_OK;
+}
+
+// this chunk behind the table's reads: copy, count, scan, fill, order (s: the state before it, ub: the bounds the tables were reserved for)
+static int bim_parse_chunk(wgbsseg_bimodal* b, const wg_bim_state& s, const char* text, int64_t n_bytes, int64_t gx, const BimodalChunkBound& ub,
+                           char* err, size_t errlen)
+{
+    PatFeed& f = b->feed;
+    HIP_TRY(b->tile_cnt.ensure((size_t)gx * 8)); HIP_TRY(b->tile_base.ensure((size_t)gx * 16)); HIP_TRY(b->pos.ensure(ub.lines * 8));
+    const char* dtext = nullptr;
+    const int rc = f.stage_chunk(text, n_bytes, &dtext, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    wgbsseg_bimodal::Table& T = b->tab[b->cur];
+    HIP_TRY(f.span_begin());
+    hipLaunchKernelGGL(k_bim_tile_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, b->tile_cnt.as<uint32_t>(),
+                       b->state.as<wg_bim_state>(), f.fed);
+    hipLaunchKernelGGL(k_bim_tile_scan, dim3(1), dim3(WG_BLOCK), 0, f.st, b->tile_cnt.as<uint32_t>(), gx, b->tile_base.as<long long>(),
+                       b->state.as<wg_bim_state>());
+    hipLaunchKernelGGL(k_bim_fill, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, b->tile_base.as<long long>(),
+                       T.start.as<int32_t>(), T.len.as<int32_t>(), T.cnt.as<int32_t>(), T.woff.as<long long>(), T.words.as<uint32_t>(),
+                       b->pos.as<long long>(), b->state.as<wg_bim_state>(), f.fed);
+    hipLaunchKernelGGL(k_bim_order, dim3((unsigned)((ub.lines + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, f.st, T.start.as<int32_t>(),
+                       b->pos.as<long long>(), b->state.as<wg_bim_state>(), s.last_start, (int64_t)ub.lines);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(f.span_end());
+    HIP_TRY(f.chunk_queued(n_bytes));
+    return WGBSSEG_OK;
+}
+
+extern "C" {
+
+// plan (bimodal_plan.h) -> the blocks and a fresh state on the device
+int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, int32_t strict, int32_t min_len,
+                           int32_t max_lds_cols, wgbsseg_bimodal** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    BimodalPlan plan;
+    std::string msg;
+    int rc = plan_bimodal(start_cpg, end_cpg, n_blocks, min_len, max_lds_cols, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    std::unique_ptr<wgbsseg_bimodal> b(new (std::nothrow) wgbsseg_bimodal());      // (a failing call below frees what has been made)
+    if (!b) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    rc = b->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    b->plan = std::move(plan); b->strict = strict ? 1 : 0; b->min_len = min_len;
+    const size_t nb = (size_t)n_blocks;
+    HIP_TRY(b->bs1.ensure(nb * 4)); HIP_TRY(b->bs2.ensure(nb * 4)); HIP_TRY(b->ids.ensure(nb * 4));
+    HIP_TRY(b->meta.ensure(nb * sizeof(wg_bim_meta))); HIP_TRY(b->scr_off.ensure(nb * 8));
+    HIP_TRY(b->res_f.ensure(nb * 24)); HIP_TRY(b->res_i.ensure(nb * 24)); HIP_TRY(b->state.ensure(sizeof(wg_bim_state)));
+    HIP_TRY(hipMemcpy(b->bs1.p, b->plan.s1.data(), nb * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->bs2.p, b->plan.s2.data(), nb * 4, hipMemcpyHostToDevice));
+    if (!b->host_state.ensure(sizeof(wg_bim_state))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    wg_bim_state s0;
+    s0.R = s0.W = s0.R0 = 0; s0.last_start = WG_BIM_NONE; s0.head = s0.whead = 0;
+    s0.bad = s0.neg = s0.desc = ~0ULL; s0.em_cap = 0;
+    *b->hs() = s0;
+    HIP_TRY(hipMemcpy(b->state.p, &s0, sizeof(s0), hipMemcpyHostToDevice));
+    *out = b.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b) { delete b; }
+
+// sync (the previous chunk is parsed and checked) -> reserve -> retire -> drop -> parse; every host decision is the plan's
+int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    const int64_t gx = PatFeed::tiles("bimodal", b, text, n_bytes, err, errlen);
+    if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
+    HIP_TRY(hipSetDevice(b->feed.device));
+    int rc = bim_sync_state(b, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (b->stop) { b->feed.fed += (unsigned long long)n_bytes; return WGBSSEG_OK; }     // finish() reports the error
+    const wg_bim_state s = *b->hs();
+    const BimodalChunkBound ub(n_bytes);
+    rc = bim_reserve(b, (size_t)s.R + ub.lines, (size_t)s.W + ub.words, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    rc = bim_retire(b, b->plan.retire_upto(b->pending, s.last_start), err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (s.R > 0) rc = bim_drop(b, s, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    return bim_parse_chunk(b, s, text, n_bytes, gx, ub, err, errlen);
+}
+
+int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char* err, size_t errlen)
+{
+    if (!b || !ll || !counts) { set_err(err, errlen, "bad arguments to bimodal_finish"); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(b->feed.device));
+    int rc = bim_sync_state(b, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (!b->stop) {
+        rc = bim_retire(b, b->plan.n_blocks, err, errlen);        // every read has been seen
+        if (rc != WGBSSEG_OK) return rc;
+        rc = bim_sync_state(b, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+    }
+    const wg_bim_state* s = b->hs();
+    if (pat_refused(PatRefusal::bad_line, s->bad, "test_bimodal:", err, errlen)) return WGBSSEG_E_ARG;
+    if (s->neg != ~0ULL) {
+        set_err(err, errlen, "test_bimodal: negative read count at byte offset %llu of the input", s->neg);
+        return WGBSSEG_E_ARG;
+    }
+    if (pat_refused(PatRefusal::unsorted, s->desc, "test_bimodal:", err, errlen)) return WGBSSEG_E_ARG;
+    if (s->em_cap) {
+        set_err(err, errlen, "test_bimodal: the EM of block %llu (row of the blocks) did not settle within %d iterations", s->em_cap, WG_BIM_MAX_ITERS);
+        return WGBSSEG_E_CAPACITY;
+    }
+    HIP_TRY(hipMemcpy(ll, b->res_f.p, (size_t)b->plan.n_blocks * 24, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counts, b->res_i.p, (size_t)b->plan.n_blocks * 24, hipMemcpyDeviceToHost));
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_bimodal_kernel_ms(wgbsseg_bimodal* b)
+{
+    return b ? b->feed.kernel_ms() : -1.0;
+}
+
+}  // extern "C"

@@ -16,11 +16,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "stats_plan.h"      // WG_ST_BLOCK, WG_ST_VPT, WG_ST_TILE
 #include "wave_prims.h"
-
-#define WG_ST_BLOCK 256
-#define WG_ST_VPT 4                                 // 16-byte vectors per thread, all loaded before the first is used
-#define WG_ST_TILE (WG_ST_BLOCK * WG_ST_VPT)        // vectors per workgroup: 16 KB of one row
 
 // what one workgroup leaves for the fold (and the fold's running sums)
 struct wg_stat_part {
