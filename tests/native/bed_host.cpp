@@ -1,6 +1,6 @@
 // Host twin of the beta2bed kernels' text rule and the call's host plan (TEST INFRASTRUCTURE): csrc/bed_fmt.h — the "%.3g" of
 // meth / cov from the two counts, the decimal digits — and csrc/bed_plan.h — the argument checks, the line bound, the staging
-// rule, the slabs — compiled for the CPU as they are, so that tests/test_beta2bed_cpu.py can hold them against Python's own
+// rule, the slabs, the chromosome and workgroup tables, the text buffers' capacity, the slab parity — compiled for the CPU as they are, so that tests/test_beta2bed_cpu.py can hold them against Python's own
 // '%.3g' and against the fixture without a GPU.
 #include <cstring>
 #include "../../wgbs_tools_amd/csrc/bed_plan.h"
@@ -60,6 +60,33 @@ int bed_check_slab_bytes(uint64_t bytes, int64_t slab, int64_t slab_sites, char*
     snprintf(msg, msglen, "%s", m.c_str());
     return rc;
 }
+
+// wg_bed_pack_chroms into out (cap bytes) -> the table's size; offs = {cum, names} of wg_bed_chrom_table
+int64_t bed_chrom_table(const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms, char* out, int64_t cap, int64_t* offs)
+{
+    const BedChromTable t = wg_bed_chrom_table(n_chroms);
+    const std::vector<char> tab = wg_bed_pack_chroms(chrom_cum, chrom_names, n_chroms);
+    offs[0] = (int64_t)t.cum; offs[1] = (int64_t)t.names;
+    if (tab.size() != t.size || (int64_t)tab.size() > cap) return -1;
+    memcpy(out, tab.data(), tab.size());
+    return (int64_t)tab.size();
+}
+
+// wg_bed_wg_table(max_wgs): out = {bytes, lines, base, tot_bytes, tot_lines, words, size in bytes}
+void bed_wg_table(int64_t max_wgs, int64_t* out)
+{
+    const BedWgTable t = wg_bed_wg_table(max_wgs);
+    out[0] = t.bytes; out[1] = t.lines; out[2] = t.base; out[3] = t.tot_bytes; out[4] = t.tot_lines; out[5] = t.words; out[6] = (int64_t)t.size();
+}
+
+// wg_bed_text_capacity: out = {home, device}
+void bed_text_capacity(uint64_t tot, int64_t first_bound, uint64_t* out)
+{
+    const BedTextCap c = wg_bed_text_capacity(tot, first_bound);
+    out[0] = c.home; out[1] = c.device;
+}
+
+int bed_parity(int64_t k) { return wg_bed_parity(k); }
 
 int64_t bed_line_bound(int64_t name_len) { return wg_bed_line_bound(name_len); }
 int bed_staged(uint32_t wg_bytes, uint32_t stage_bytes) { return wg_bed_staged(wg_bytes, stage_bytes) ? 1 : 0; }

@@ -1,9 +1,11 @@
 // Sanitizer harness for the host-only part of beta2bed (TEST INFRASTRUCTURE): csrc/bed_fmt.h — every uint8 pair and a sweep of
 // uint16 pairs through the "%.3g" rule, against the C library's own printf — and csrc/bed_plan.h — the argument checks on
-// fixed inputs, every array heap-allocated at its exact size so that a read past an end is seen.
+// fixed inputs, every array heap-allocated at its exact size so that a read past an end is seen; the chromosome table packed
+// from exact-size names (the longest one last), the workgroup table's layout, the text buffers' capacity, the slab parity.
 // tests/test_beta2bed_cpu.py builds it plain and with AddressSanitizer + UndefinedBehaviorSanitizer and compares the lines.
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "bed_plan.h"
 
@@ -25,6 +27,26 @@ static void plan_case(const char* what, int32_t sample, int32_t n_samples, int64
     const int rc = wg_bed_plan(sample, n_samples, start0, end0, n_total, cum.data(), names.data(), (int32_t)cum.size(), null_opts ? nullptr : &o, p, msg);
     if (rc == WGBSSEG_OK) printf("%s: accepted: %lld slabs of %lld, stage %d, longest name %d\n", what, (long long)p.n_slabs, (long long)p.slab_sites, (int)p.stage_bytes, (int)p.max_name);
     else printf("%s: refused (%d): %s\n", what, rc, msg.c_str());
+}
+
+// the packed chromosome table of `names` (each copied into a heap array of exactly its length + 1): its size, offsets and a checksum
+static void table_case(const char* what, const std::vector<std::string>& names)
+{
+    std::vector<std::vector<char>> held;
+    std::vector<const char*> ptr;
+    std::vector<int64_t> cum;
+    for (const std::string& n : names) {
+        held.emplace_back(n.c_str(), n.c_str() + n.size() + 1);
+        cum.push_back((int64_t)(cum.size() + 1) * 1000);
+    }
+    for (const auto& h : held) ptr.push_back(h.data());
+    const int32_t n = (int32_t)names.size();
+    const BedChromTable t = wg_bed_chrom_table(n);
+    const std::vector<char> tab = wg_bed_pack_chroms(cum.data(), ptr.data(), n);
+    unsigned long sum = 0;
+    for (char c : tab) sum = sum * 31 + (unsigned char)c;
+    const char* last = tab.data() + t.names + (size_t)(n - 1) * WG_BED_NAME_REC;
+    printf("%s: %zu bytes (cum %zu, names %zu), last record %d bytes, checksum %lu\n", what, tab.size(), t.cum, t.names, (int)last[WG_BED_NAME_REC - 1], sum);
 }
 
 int main()
@@ -67,5 +89,22 @@ int main()
     printf("slab bytes: %d", wg_bed_check_slab_bytes(WG_BED_MAX_SLAB_BYTES - 1, 3, 1000, msg));
     const int rc2 = wg_bed_check_slab_bytes(WG_BED_MAX_SLAB_BYTES, 3, 1000, msg);
     printf(" %d %s\n", rc2, msg.c_str());
+
+    table_case("table of 1", {"c"});
+    table_case("table of 4", {"chr1", "MT", "chrX", top_name});
+    std::vector<std::string> many;
+    for (int i = 0; i < WG_BED_LDS_CHROMS + 1; i++) many.push_back(i % 2 ? "c" + std::to_string(i) : std::string(WG_BED_MAX_NAME - i % 3, 'x'));
+    many.back() = top_name;
+    table_case("table of 65", many);
+    for (int64_t wgs : {1ll, 2ll, 4096ll}) {
+        const BedWgTable t = wg_bed_wg_table(wgs);
+        printf("wg table of %lld: %lld %lld %lld %lld %lld, %lld words, %zu bytes\n", (long long)wgs, (long long)t.bytes, (long long)t.lines, (long long)t.base,
+               (long long)t.tot_bytes, (long long)t.tot_lines, (long long)t.words, t.size());
+    }
+    for (uint64_t tot : {0ull, 9999ull, 10000ull, 10001ull, (unsigned long long)WG_BED_MAX_SLAB_BYTES - 1}) {
+        const BedTextCap c = wg_bed_text_capacity(tot, 10000);
+        printf("capacity for %llu of 10000: %zu at home, %zu on the device\n", (unsigned long long)tot, c.home, c.device);
+    }
+    printf("parity: %d %d %d %d\n", wg_bed_parity(0), wg_bed_parity(1), wg_bed_parity(2), wg_bed_parity(4097));
     return bad ? 1 : 0;
 }

@@ -1,6 +1,7 @@
 """`wgbstools beta2bed` without a GPU: the dispatcher and the flags; the "%.3g" rule of csrc/bed_fmt.h, compiled for the host
 (tests/native/bed_host.cpp), against Python's own '%.3g' on every uint8 pair and on the tie world; the host plan csrc/bed_plan.h
-(refusals, the line bound against the fixture's longest line, the slab arithmetic); the -L multiplicity builder against the
+(refusals, the line bound against the fixture's longest line, the slab arithmetic, the chromosome and workgroup tables, the
+text buffers' capacity, the slab parity); the -L multiplicity builder against the
 row-by-row rule of tests/bed_ref.py; tests/bed_ref.py's restatement against the text the reference printed
 (tests/golden/bed_cases.json); the sanitizer run of the host-only code as a stand-alone program."""
 import ctypes as C
@@ -54,6 +55,11 @@ def host():
                            C.c_char_p, C.c_size_t]
     L.bed_constants.argtypes = [C.c_void_p]
     L.bed_staged.argtypes = [C.c_uint32, C.c_uint32]
+    L.bed_chrom_table.restype = C.c_int64
+    L.bed_chrom_table.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
+    L.bed_wg_table.argtypes = [C.c_int64, C.c_void_p]
+    L.bed_text_capacity.argtypes = [C.c_uint64, C.c_int64, C.c_void_p]
+    L.bed_parity.argtypes = [C.c_int64]
     return L
 
 
@@ -248,6 +254,51 @@ def test_slab_arithmetic(host, slab_sites):
     assert _plan(host, start0=7, end0=7)[2][1] == 0
 
 
+@pytest.mark.parametrize('n_chroms', [1, 64, 65])
+def test_chromosome_table_bytes(host, n_chroms):
+    """the table as the device reads it: the cumulative counts, then a 32-byte record per name, zero-padded, its length in byte 31"""
+    k = _constants(host)
+    names = [('c' if i % 2 else 'x' * k['max_name']) for i in range(n_chroms)]          # lengths 1 and 31
+    names[-1] = 'y' * k['max_name']
+    if n_chroms > 1:
+        names[0] = 'z'
+    cum = np.cumsum(np.arange(n_chroms) % 7 + 1).astype(np.int64)
+    rec = k['max_name'] + 1
+    want = cum.tobytes() + b''.join(n.encode() + bytes(rec - 1 - len(n)) + bytes([len(n)]) for n in names)
+    assert len(want) == n_chroms * (8 + rec)
+    out = np.full(len(want) + 64, 0xAA, dtype=np.uint8)
+    offs = np.zeros(2, dtype=np.int64)
+    arr = (C.c_char_p * n_chroms)(*[n.encode() for n in names])
+    size = host.bed_chrom_table(cum.ctypes.data, arr, n_chroms, out.ctypes.data, out.size, offs.ctypes.data)
+    assert size == len(want) and out[:size].tobytes() == want and (out[size:] == 0xAA).all()
+    assert offs.tolist() == [0, 8 * n_chroms]
+
+
+@pytest.mark.parametrize('max_wgs', [1, 2, 4096])
+def test_workgroup_table_layout(host, max_wgs):
+    """bytes | lines | base, max_wgs words each, then the two totals: in this order, disjoint, nothing between or behind them"""
+    out = np.zeros(7, dtype=np.int64)
+    host.bed_wg_table(max_wgs, out.ctypes.data)
+    b, l, base, tb, tl, words, size = out.tolist()
+    parts = [(b, max_wgs), (l, max_wgs), (base, max_wgs), (tb, 1), (tl, 1)]
+    at = 0
+    for first, n in parts:
+        assert first == at
+        at += n
+    assert words == at == 3 * max_wgs + 2 and size == 8 * words
+
+
+def test_text_capacity_and_parity(host):
+    out = np.zeros(2, dtype=np.uint64)
+    for bound in (1, 40 * 256, 66 * (1 << 20)):
+        for tot in (0, bound - 1, bound, bound + 1):
+            host.bed_text_capacity(tot, bound, out.ctypes.data)
+            assert out.tolist() == [max(tot, bound), max(tot, bound) + 16], (tot, bound)
+    host.bed_text_capacity(2 ** 32 - 1, 1000, out.ctypes.data)
+    assert out.tolist() == [2 ** 32 - 1, 2 ** 32 + 15]
+    assert [host.bed_parity(k) for k in (0, 1, 2, 3, 4096, 4097, 2 ** 40 + 1)] == [0, 1, 0, 1, 0, 1, 1]
+
+
 # ---- -L: the multiplicities ----
 def test_multiplicities_equal_the_row_by_row_rule(tmp_path, worlds):
     w = worlds['small']
@@ -326,3 +377,8 @@ def test_formatter_and_plan_under_sanitizers(tmp_path):
     assert lines[0] == 'g3 mismatches: 0' and lines[1] == 'digits: 1 10 20'
     assert sum(': refused (-1): ' in ln for ln in lines) == 13 and sum(': accepted: ' in ln for ln in lines) == 3
     assert 'mult: -1 beta2bed: site 1039 has multiplicity 65535' in outs[0] and 'slab bytes: 0 -6 beta2bed: slab 3' in outs[0]
+    tables = [ln for ln in lines if ln.startswith('table of ')]
+    assert [ln.split(',')[0] + ln.split(',')[2] for ln in tables] == ['table of 1: 40 bytes (cum 0 last record 1 bytes', 'table of 4: 160 bytes (cum 0 last record 31 bytes',
+                                                                        'table of 65: 2600 bytes (cum 0 last record 31 bytes']
+    assert 'wg table of 4096: 0 4096 8192 12288 12289, 12290 words, 98320 bytes' in lines
+    assert 'capacity for 10001 of 10000: 10001 at home, 10017 on the device' in lines and lines[-1] == 'parity: 0 1 0 1'

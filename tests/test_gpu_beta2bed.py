@@ -1,8 +1,9 @@
 """`wgbstools beta2bed` on the GPU (k_bed_len, k_bed_scan, k_bed_emit behind wgbsseg_beta2bed): every case of
 tests/bed_cases.py through the command line against what the reference printed (tests/golden/bed_cases.json), byte for byte
 or by sha1 and counts; the small world again through the ABI in slabs of 64, 256 and 1000 sites and the default; the
-direct-to-global path, forced through the plan's stage_bytes and reached by high multiplicities; bit-identical repeats; the
-refusals that need a device context."""
+direct-to-global path, forced through the plan's stage_bytes and reached by high multiplicities; slabs without text inside the
+two-slab pipeline; bit-identical repeats; the refusals that need a device context; a failed write with slabs in flight and the
+next call on the same context."""
 import errno
 import gzip
 import hashlib
@@ -122,6 +123,28 @@ def test_slabs_give_the_single_slab_bytes(seg, worlds, tmp_path, slab_sites, fil
         assert got == want and (lines, nbytes) == (want.count(b'\n'), len(want)), (a, b)
 
 
+@pytest.mark.parametrize('file_name', ['small.beta', 'small.lbeta'])
+@pytest.mark.parametrize('gap', [(256, 768), (0, 256), (2816, 3000)])
+def test_empty_slabs_inside_the_pipeline(seg, worlds, tmp_path, gap, file_name):
+    """slabs of 256 sites whose multiplicities are all zero — two in the middle, the first, the last — write nothing, between
+    slabs that do write: the two-slab pipeline skips their emit pass and their write and keeps its place"""
+    w = worlds['small']
+    rows = _load(seg, w, file_name)
+    n, slab = len(rows), 256
+    assert n == 3000 and gap[0] % slab == 0 and (gap[1] % slab == 0 or gap[1] == n)
+    mult = np.ones(n, dtype=np.uint16)
+    mult[gap[0]:gap[1]] = 0
+    for o in (dict(keep_na=True), dict(mean=True, min_cov=2)):
+        text = lambda a, b: BR.text_of(w['names'], w['sizes'], w['loci'], rows, a, b, mult[a:b], **o)
+        want = text(0, n)
+        # the gap is empty, the slabs next to it are not
+        assert text(*gap) == b'' and (gap[0] == 0 or text(gap[0] - slab, gap[0])) and (gap[1] == n or text(gap[1], min(gap[1] + slab, n)))
+        got, lines, nbytes = _emit(seg, w, tmp_path, mult=mult, slab_sites=slab, **o)
+        assert got == want, (o, gap)
+        assert (lines, nbytes) == (want.count(b'\n'), len(want))
+        assert sum(seg.beta2bed_pass_ms()) == seg.last_block_sums_ms()
+
+
 # ---- the staging rule and the direct path ----
 def _deep_mult(w):
     return BR.multiplicity_by_rows(w['names'], w['sizes'], w['loci'], BC.small_beds(w)['deep.bed']).astype(np.uint16)
@@ -233,3 +256,21 @@ def test_a_reader_that_went_away_is_a_broken_pipe(seg, worlds):
         os.close(wr)
     lim = _lib.beta2bed_limits()
     assert lim['default_slab'] == 1 << 20 and lim['max_name'] == 31 and lim['max_stage_bytes'] == 256 * 66
+
+
+def test_a_failed_write_with_slabs_in_flight_leaves_the_context_usable(seg, worlds, tmp_path):
+    """slabs of 256 sites: when the write of slab 0 fails, the text of slab 1 and the lengths of slab 2 are queued; they land in
+    buffers the context keeps, and the next call on the same context writes what a single-slab call writes"""
+    w = worlds['small']
+    rows = _load(seg, w, 'small.beta')
+    r, wr = os.pipe()
+    os.close(r)
+    try:
+        with pytest.raises(BrokenPipeError) as e:
+            seg.beta2bed(wr, 0, w['names'], np.cumsum(w['sizes']), keep_na=True, slab_sites=256)
+        assert e.value.errno == errno.EPIPE
+    finally:
+        os.close(wr)
+    got, lines, nbytes = _emit(seg, w, tmp_path, keep_na=True, slab_sites=256)
+    assert (got, lines, nbytes) == _emit(seg, w, tmp_path, keep_na=True, slab_sites=len(rows)) and lines == len(rows)
+    assert got == BR.text_of(w['names'], w['sizes'], w['loci'], rows, 0, len(rows), keep_na=True)

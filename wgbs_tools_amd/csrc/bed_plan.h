@@ -1,5 +1,5 @@
 // bed_plan.h — the host plan of the per-site BED export (wgbsseg_beta2bed, `wgbstools beta2bed`) and what host and device agree
-// on: the workgroup size, the longest line, the staging rule, the slabs.  No HIP here (like pair_plan.h and block_plan.h): g++
+// on: the workgroup size, the longest line, the staging rule, the slabs, the tables' layouts.  No HIP here (like pair_plan.h and block_plan.h): g++
 // compiles it alone, tests/native/bed_host.cpp hands it to the tests and tests/native/san_bed.cpp runs it under the sanitizers.
 //
 // A line is  name \t loc-1 \t loc+1 \t meth \t cov \n  or, with `mean`,  name \t loc-1 \t loc+1 \t R \n  (R: bed_fmt.h).  loc is a
@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 #include "../../include/wgbsseg.h"
 #include "bed_fmt.h"
 
@@ -31,6 +32,7 @@
 #define WG_BED_MAX_SLAB (1 << 24)
 #define WG_BED_MULT_TOO_MANY 65535             // reserved multiplicity: "more overlapping rows than a uint16 counts"
 #define WG_BED_MAX_SLAB_BYTES (1ull << 32)     // a slab's text must stay below this (only multiplicities can reach it)
+#define WG_BED_TEXT_SLACK 16                   // what the device's text buffer has beyond the text: k_bed_emit copies out in 16-byte vectors
 
 static_assert(WG_BED_MAX_NAME < WG_BED_NAME_REC, "the record's last byte is the length");
 static_assert(WG_BED_LINE_TAIL >= 1 + 10 + 1 + 10 + 1 + WG_G3_MAX_LEN + 1, "the mean line is the shorter one");
@@ -67,6 +69,44 @@ struct BedPlan {
     // what a slab's text can take without multiplicities: the first size of its two buffers
     int64_t slab_bytes_bound(int64_t k) const { return slab_count(k) * wg_bed_line_bound(max_name); }
 };
+
+// Two slabs are in flight, slab k in the buffers and between the events of parity k & 1: this function is the only place that says so.
+constexpr int wg_bed_parity(int64_t k) { return (int)(k & 1); }
+
+// The text buffers of a slab whose text has `tot` bytes, of a call whose first slab is bounded by `first_bound` (BedPlan::slab_bytes_bound(0):
+// what every slab needs without multiplicities, so no regrowth slab by slab): the page-locked one at home and the device's.
+struct BedTextCap { size_t home, device; };
+inline BedTextCap wg_bed_text_capacity(uint64_t tot, int64_t first_bound)
+{
+    const size_t n = tot > (uint64_t)first_bound ? (size_t)tot : (size_t)first_bound;
+    return {n, n + WG_BED_TEXT_SLACK};
+}
+
+// The workgroup table of a slab of up to max_wgs workgroups, in 64-bit words: k_bed_len's bytes and lines per workgroup, k_bed_scan's
+// first byte of every workgroup and, behind them, the slab's two totals (bytes, lines), which travel home together.
+struct BedWgTable {
+    int64_t bytes, lines, base, tot_bytes, tot_lines, words;
+    size_t size() const { return (size_t)words * 8; }
+};
+constexpr BedWgTable wg_bed_wg_table(int64_t max_wgs) { return {0, max_wgs, 2 * max_wgs, 3 * max_wgs, 3 * max_wgs + 1, 3 * max_wgs + 2}; }
+
+// The chromosome table as the device reads it (wg_bed_args::cum, ::names), for a table wg_bed_plan has accepted: n_chroms cumulative
+// counts, then n_chroms records of WG_BED_NAME_REC bytes, the name zero-padded and its length in the last byte.  Byte offsets.
+struct BedChromTable { size_t cum, names, size; };
+constexpr BedChromTable wg_bed_chrom_table(int32_t n_chroms) { return {0, (size_t)n_chroms * 8, (size_t)n_chroms * (8 + WG_BED_NAME_REC)}; }
+inline std::vector<char> wg_bed_pack_chroms(const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms)
+{
+    const BedChromTable t = wg_bed_chrom_table(n_chroms);
+    std::vector<char> tab(t.size, 0);
+    memcpy(tab.data() + t.cum, chrom_cum, (size_t)n_chroms * 8);
+    for (int32_t i = 0; i < n_chroms; i++) {
+        char* rec = tab.data() + t.names + (size_t)i * WG_BED_NAME_REC;
+        const size_t len = strlen(chrom_names[i]);
+        memcpy(rec, chrom_names[i], len);
+        rec[WG_BED_NAME_REC - 1] = (char)len;
+    }
+    return tab;
+}
 
 // The arguments of wgbsseg_beta2bed against n_samples resident rows of n_total sites.  WGBSSEG_OK and a filled plan, or
 // WGBSSEG_E_ARG and a message naming the offender.

@@ -21,6 +21,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <pthread.h>
 #include <sched.h>
@@ -80,6 +81,18 @@ struct NearCpus { std::vector<unsigned long> bits; bool valid = false; };      /
 // The events of a batch: stream A: it begins, its tables are up, windows done, statistics copied, tile plan done; the scan stream: k_validate, k_scan
 // (jobs with wide tiles only), the pass is done (its verdict may be copied); stream B: traceback + border lists, results on the host.
 enum BatchEvent { EV_BEGIN, EV_WINDOWS, EV_SCAN_END, EV_PLAN, EV_TRACE0, EV_TRACE1, EV_HOME, EV_STATS, EV_VALIDATE0, EV_VALIDATE1, EV_SCAN0, EV_SCAN1, EV_UPLOADED, EV_COUNT };
+
+// What wgbsseg_beta2bed keeps between calls (row_engines.h, BedRun): the chromosome table (bed_plan.h: wg_bed_pack_chroms) | a slab's
+// multiplicities | its workgroup table (bed_plan.h: BedWgTable) | the text of two slabs, on the device and at home | the totals of two slabs
+// at home | per slab parity the events around the length pass and scan and around the emit pass | the two passes' times of the last call.
+// Members go in reverse order of declaration: events, then page-locked memory, then device memory, as when they were the context's own.
+// The context's destructor has synchronised the device by then, so nothing here needs a teardown rule of its own.
+struct BedScratch {
+    DevBuf tab, mult, wg, out[2];
+    PinnedBuf home[2], tot;
+    struct PassEvents { Event len0, len1, emit0, emit1; } ev[2];
+    double len_ms = 0.0, emit_ms = 0.0;
+};
 
 struct wgbsseg_ctx {
     int device = 0;
@@ -141,12 +154,7 @@ struct wgbsseg_ctx {
     DevBuf mk_out, cv_in, cv_out;      // wgbsseg_marker_stats: the statistics and the two sample lists; wgbsseg_convert_regions: the regions' columns | their CpG ranges
     DevBuf st_ranges, st_parts;     // wgbsseg_sample_stats: the range table | the tiles' partial results and the per-sample results
     DevBuf ph_pairs, ph_edges, ph_out;   // wgbsseg_pair_ranges / _pair_hist: the pair list (a | b) | the edges | the ranges or the counts
-    // wgbsseg_beta2bed: the chromosome table (cum | names) | a slab's multiplicities | its workgroup totals (bytes | lines | first byte | slab totals) |
-    // the text of two slabs, on the device and at home | the totals of two slabs at home | the passes' events per slab parity (length: 0-1, emit: 2-3)
-    DevBuf bed_tab, bed_mult, bed_wg, bed_out[2];
-    PinnedBuf bed_home[2], bed_tot;
-    Event bed_ev[2][4];
-    double bed_len_ms = 0.0, bed_emit_ms = 0.0;
+    BedScratch bed;                      // wgbsseg_beta2bed
     std::vector<int32_t> h_stage_bounds;
     // the short division core of the narrow scoring tiles: verified on the device per pseudo count (k_check_div)
     float divs_pc = -1.0f;     // pseudo count the verdict below is for
@@ -2222,393 +2230,10 @@ int wgbsseg_prefix_sums(wgbsseg_ctx* c, int64_t start0, int64_t len, uint32_t* o
 
 }  // extern "C"
 
-namespace {
+#include "row_engines.h"      // the calls on the resident rows (block_sums, marker_stats, sample_stats, the pair calls, beta2bed, convert_regions)
 
-// The timed tail of an auxiliary call (block_sums, marker_stats, sample_stats, convert_regions): begin() in front of its launches on stream A;
-// end() behind them brings the results home, waits, and leaves the launches' device time where wgbsseg_last_block_sums_ms reads it.
-struct AuxClock {
-    wgbsseg_ctx* c;
-    struct Fetch { void* dst; const void* src; size_t bytes; };
-    hipError_t begin() const { return hipEventRecord(c->ev[0], c->sA); }
-    hipError_t end(std::initializer_list<Fetch> home) const
-    {
-        hipError_t e = hipEventRecord(c->ev[1], c->sA);
-        for (const Fetch& f : home) if (e == hipSuccess) e = hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, c->sA);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->sA);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[0], c->ev[1]);
-        if (e == hipSuccess) c->last_block_sums_ms = ms;
-        return e;
-    }
-};
-
-using BlockSumTables = BlockSumPlan::View<const int32_t>;      // a plan's tables on the device (bs_plan)
-
-// uint8 rows, a table ordered by first and last site: the descriptors of every block once (prep), the streamed pass, and a wavefront
-// per (block, sample) for the blocks the ring cannot serve
-int launch_block_sums_streaming(wgbsseg_ctx* c, const BlockSumPlan& p, const BlockSumTables& d, int mode, uint32_t min_cov, char* err, size_t errlen)
-{
-    const int64_t n_blocks = p.n_blocks;
-    int32_t* dd1 = c->bs_desc.as<int32_t>();
-    int32_t* dd0 = dd1 + n_blocks;
-    int32_t* drr = dd0 + n_blocks;
-    hipLaunchKernelGGL(k_block_sums_prep, dim3((unsigned)((n_blocks + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, c->sA, d.x0, d.x1, d.perm, n_blocks, p.n_tiles, dd1, dd0, drr);
-    HIP_TRY(hipGetLastError());
-    const unsigned gy = (unsigned)((c->n_samples + 3) / 4);
-    const dim3 grid((unsigned)((p.n_tiles + WG_BSR_RUN - 1) / WG_BSR_RUN), gy);
-#define WG_LAUNCH_BSR(M) hipLaunchKernelGGL(k_block_sums_run<M>, grid, dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, dd1, dd0, drr, d.tile_first, \
-                                            p.n_tiles, n_blocks, (int)c->n_samples, min_cov, c->bs_out.p)
-    if (mode == 0) WG_LAUNCH_BSR(0); else if (mode == 1) WG_LAUNCH_BSR(1); else if (mode == 2) WG_LAUNCH_BSR(2); else WG_LAUNCH_BSR(3);
-#undef WG_LAUNCH_BSR
-    HIP_TRY(hipGetLastError());
-    if (p.n_direct)
-        hipLaunchKernelGGL(k_block_sums_direct, dim3((unsigned)p.n_direct, gy), dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, d.x0, d.x1, d.perm,
-                           d.direct, p.n_direct, n_blocks, (int)c->n_samples, mode, min_cov, c->bs_out.p);
-    HIP_TRY(hipGetLastError());
-    return WGBSSEG_OK;
-}
-
-// every other table and uint16 rows: tiles of WG_BS_TILE sites, 4 x spw samples per workgroup
-template <int ELEM>
-int launch_block_sums_general(wgbsseg_ctx* c, const BlockSumPlan& p, const BlockSumTables& d, int spw, unsigned gy, int mode, uint32_t min_cov, char* err, size_t errlen)
-{
-    const int64_t gx = (p.n_tiles + WG_BS_RUN - 1) / WG_BS_RUN;
-    hipLaunchKernelGGL(k_block_sums<ELEM>, dim3((unsigned)gx, gy), dim3(WG_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total,
-                       d.x0, d.x1, d.perm, d.tile_first, p.n_tiles, p.n_blocks, (int)c->n_samples, spw, mode, min_cov, c->bs_out.p);
-    HIP_TRY(hipGetLastError());
-    return WGBSSEG_OK;
-}
-
-// what both pair calls begin with: the checks of pair_plan.h, then the pair list on the device (a | b)
-int pair_list_up(wgbsseg_ctx* c, const char* who, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov, char* err, size_t errlen)
-{
-    std::string msg;
-    if (!wg_pair_check_list(who, a, b, n_pairs, min_cov, c->n_samples, c->n_total, msg)) { set_err(err, errlen, "%s", msg.c_str()); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->ph_pairs.ensure((size_t)n_pairs * 8));
-    HIP_TRY(hipMemcpyAsync(c->ph_pairs.p, a, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->sA));
-    HIP_TRY(hipMemcpyAsync(c->ph_pairs.as<int32_t>() + n_pairs, b, (size_t)n_pairs * 4, hipMemcpyHostToDevice, c->sA));
-    return WGBSSEG_OK;
-}
-
-}  // namespace
-
+// the text tables: loci and CpG columns, block and BED files parsed and written on the host (add_loci.h, table_io.h)
 extern "C" {
-
-// plan (block_plan.h) -> upload -> launches -> fetch
-int wgbsseg_block_sums(wgbsseg_ctx* c, const int64_t* start0, const int64_t* end0, int64_t n_blocks, int32_t mode,
-                       uint32_t min_cov, void* out, char* err, size_t errlen)
-{
-    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
-    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
-    if (n_blocks > 0 && !out) { set_err(err, errlen, "bad arguments to block_sums"); return WGBSSEG_E_ARG; }
-    BlockSumPlan p;
-    std::string msg;
-    int rc = plan_block_sums(start0, end0, n_blocks, c->n_total, c->elem, mode, c->bs_general, p, msg);      // (bs_general: WGBSSEG_BLOCK_SUMS_GENERAL=1, tests)
-    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
-    if (n_blocks == 0) return WGBSSEG_OK;
-    // samples per wavefront of the general kernel (it keeps two tiles of each in registers, one being reduced, one in flight)
-    const int spw = (c->elem == 1 && c->n_samples > 4) ? 2 : 1;
-    const unsigned gy = (unsigned)((c->n_samples + 4 * spw - 1) / (4 * spw));
-    if (gy > 65535) { set_err(err, errlen, "too many samples for one block_sums call"); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t esz = mode == 0 ? 8 : (mode == 1 ? 2 : (mode == 2 ? 4 : 8));
-    const size_t obytes = (size_t)c->n_samples * (size_t)n_blocks * esz;
-    c->table_blocks = 0;                                         // bs_out is about to change
-    HIP_TRY(c->bs_plan.ensure(p.upload.size() * 4));
-    HIP_TRY(c->bs_out.ensure(obytes));
-    if (p.monotone) HIP_TRY(c->bs_desc.ensure((size_t)n_blocks * 12));
-    HIP_TRY(hipMemcpyAsync(c->bs_plan.p, p.upload.data(), p.upload.size() * 4, hipMemcpyHostToDevice, c->sA));
-    const BlockSumTables d = p.view(c->bs_plan.as<const int32_t>());
-    const AuxClock clock{c};
-    HIP_TRY(clock.begin());
-    if (p.monotone) rc = launch_block_sums_streaming(c, p, d, mode, min_cov, err, errlen);
-    else if (c->elem == 1) rc = launch_block_sums_general<1>(c, p, d, spw, gy, mode, min_cov, err, errlen);
-    else rc = launch_block_sums_general<2>(c, p, d, spw, gy, mode, min_cov, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    HIP_TRY(clock.end({{out, c->bs_out.p, obytes}}));
-    c->last_valid = false;
-    c->table_blocks = mode == 3 ? n_blocks : 0;
-    return WGBSSEG_OK;
-}
-
-int wgbsseg_marker_stats(wgbsseg_ctx* c, const int32_t* tg, int32_t n_tg, const int32_t* bg, int32_t n_bg, int64_t n_blocks, double* out,
-                         char* err, size_t errlen)
-{
-    if (!c || !tg || !bg || n_tg < 1 || n_bg < 1 || !out || n_blocks < 1) { set_err(err, errlen, "bad arguments to marker_stats"); return WGBSSEG_E_ARG; }
-    if (c->table_blocks != n_blocks) { set_err(err, errlen, "marker_stats: the last wgbsseg_block_sums call was not a mode-3 reduction over these %lld blocks", (long long)n_blocks); return WGBSSEG_E_STATE; }
-    for (int i = 0; i < n_tg; i++) if (tg[i] < 0 || tg[i] >= c->n_samples) { set_err(err, errlen, "marker_stats: no sample %d", (int)tg[i]); return WGBSSEG_E_ARG; }
-    for (int i = 0; i < n_bg; i++) if (bg[i] < 0 || bg[i] >= c->n_samples) { set_err(err, errlen, "marker_stats: no sample %d", (int)bg[i]); return WGBSSEG_E_ARG; }
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(c->mk_out.ensure((size_t)n_blocks * 64 + (size_t)(n_tg + n_bg) * 4));
-    double* dout = c->mk_out.as<double>();
-    int32_t* dtg = reinterpret_cast<int32_t*>(dout + n_blocks * 8);
-    int32_t* dbg = dtg + n_tg;
-    HIP_TRY(hipMemcpyAsync(dtg, tg, (size_t)n_tg * 4, hipMemcpyHostToDevice, c->sA));
-    HIP_TRY(hipMemcpyAsync(dbg, bg, (size_t)n_bg * 4, hipMemcpyHostToDevice, c->sA));
-    const AuxClock clock{c};
-    HIP_TRY(clock.begin());
-    hipLaunchKernelGGL(k_marker_stats, dim3((unsigned)(((n_blocks + 1) / 2 + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, c->sA, c->bs_out.as<double>(), n_blocks,      // (two blocks per thread)
-                       dtg, (int)n_tg, dbg, (int)n_bg, dout);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(clock.end({{out, dout, (size_t)n_blocks * 64}}));
-    return WGBSSEG_OK;
-}
-
-double wgbsseg_last_block_sums_ms(const wgbsseg_ctx* c) { return c ? c->last_block_sums_ms : 0.0; }
-
-static_assert(sizeof(wgbsseg_sample_stat) == sizeof(wg_sample_stat) && sizeof(wg_sample_stat) == 72, "wgbsseg_sample_stat is the kernels' wg_sample_stat");
-
-// plan (stats_plan.h) -> upload -> two launches -> fetch
-int wgbsseg_sample_stats(wgbsseg_ctx* c, const int64_t* start0, const int64_t* end0, int64_t n_ranges, int32_t depth_at,
-                         wgbsseg_sample_stat* out, char* err, size_t errlen)
-{
-    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
-    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
-    if (!out) { set_err(err, errlen, "bad arguments to sample_stats"); return WGBSSEG_E_ARG; }
-    StatsPlan p;
-    std::string msg;
-    const int rc = plan_sample_stats(start0, end0, n_ranges, c->n_total, c->elem, c->n_samples, p, msg);
-    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
-    if (p.n_vec == 0) {                                          // nothing to read: no ranges, or empty ones only
-        memset(out, 0, sizeof(*out) * (size_t)c->n_samples);
-        c->last_block_sums_ms = 0.0;
-        return WGBSSEG_OK;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t part_bytes = (size_t)p.n_tiles * (size_t)c->n_samples * sizeof(wg_stat_part);
-    HIP_TRY(c->st_ranges.ensure(p.upload.size() * 8));
-    HIP_TRY(c->st_parts.ensure(part_bytes + (size_t)c->n_samples * sizeof(wg_sample_stat)));
-    HIP_TRY(hipMemcpyAsync(c->st_ranges.p, p.upload.data(), p.upload.size() * 8, hipMemcpyHostToDevice, c->sA));
-    const StatsPlan::View<const int64_t> d = p.view(c->st_ranges.as<const int64_t>());
-    wg_stat_part* dparts = c->st_parts.as<wg_stat_part>();
-    wg_sample_stat* dout = reinterpret_cast<wg_sample_stat*>(c->st_parts.as<uint8_t>() + part_bytes);
-    const dim3 grid((unsigned)p.n_tiles, (unsigned)c->n_samples);
-    const AuxClock clock{c};
-    HIP_TRY(clock.begin());
-    if (c->elem == 1)
-        hipLaunchKernelGGL(k_sample_stats<1>, grid, dim3(WG_ST_BLOCK), 0, c->sA, c->betas, c->pitch, d.x0, d.x1, d.cumv, n_ranges, p.n_vec, depth_at, dparts, p.n_tiles);
-    else
-        hipLaunchKernelGGL(k_sample_stats<2>, grid, dim3(WG_ST_BLOCK), 0, c->sA, c->betas, c->pitch, d.x0, d.x1, d.cumv, n_ranges, p.n_vec, depth_at, dparts, p.n_tiles);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_sample_stats_fold, dim3((unsigned)c->n_samples), dim3(WG_ST_BLOCK), 0, c->sA, dparts, p.n_tiles, (uint64_t)p.n_sites, dout);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(clock.end({{out, dout, sizeof(*out) * (size_t)c->n_samples}}));
-    return WGBSSEG_OK;
-}
-
-static_assert(sizeof(wgbsseg_pair_range) == sizeof(wg_pair_range) && sizeof(wg_pair_range) == 40, "wgbsseg_pair_range is the kernels' wg_pair_range");
-
-int wgbsseg_pair_ranges(wgbsseg_ctx* c, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov,
-                        wgbsseg_pair_range* out, char* err, size_t errlen)
-{
-    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
-    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
-    if (!out) { set_err(err, errlen, "pair_ranges: out is NULL"); return WGBSSEG_E_ARG; }
-    const int rc = pair_list_up(c, "pair_ranges", a, b, n_pairs, min_cov, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    const wgbsseg_pair_range start = {0, 0, 0, 0, 0};
-    std::vector<wg_pair_range> init((size_t)n_pairs, wg_pair_range{0, ~0ull, 0, ~0ull, 0});
-    HIP_TRY(c->ph_out.ensure(init.size() * sizeof(wg_pair_range)));
-    wg_pair_range* dout = c->ph_out.as<wg_pair_range>();
-    HIP_TRY(hipMemcpyAsync(dout, init.data(), init.size() * sizeof(wg_pair_range), hipMemcpyHostToDevice, c->sA));
-    const int32_t* dpa = c->ph_pairs.as<int32_t>();
-    const dim3 grid((unsigned)((c->n_total + WG_PH_RUN - 1) / WG_PH_RUN * n_pairs));
-    const AuxClock clock{c};
-    HIP_TRY(clock.begin());
-    if (c->elem == 1)
-        hipLaunchKernelGGL(k_pair_ranges<1>, grid, dim3(WG_PH_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, dpa, dpa + n_pairs, (int32_t)n_pairs, min_cov, dout);
-    else
-        hipLaunchKernelGGL(k_pair_ranges<2>, grid, dim3(WG_PH_BLOCK), 0, c->sA, c->betas, c->pitch, c->n_total, dpa, dpa + n_pairs, (int32_t)n_pairs, min_cov, dout);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(clock.end({{out, dout, sizeof(*out) * (size_t)n_pairs}}));
-    for (int64_t i = 0; i < n_pairs; i++) if (out[i].n == 0) out[i] = start;      // (the bit patterns min and max began with are no doubles to hand out)
-    return WGBSSEG_OK;
-}
-
-int wgbsseg_pair_hist(wgbsseg_ctx* c, const int32_t* a, const int32_t* b, int64_t n_pairs, int32_t min_cov, int32_t bins,
-                      const double* edges, uint64_t* counts, char* err, size_t errlen)
-{
-    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
-    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
-    if (!counts) { set_err(err, errlen, "pair_hist: counts is NULL"); return WGBSSEG_E_ARG; }
-    std::string msg;
-    if (!wg_pair_check_bins(bins, msg)) { set_err(err, errlen, "%s", msg.c_str()); return WGBSSEG_E_ARG; }
-    if (n_pairs >= 1 && !wg_pair_check_edges(edges, n_pairs, bins, msg)) { set_err(err, errlen, "%s", msg.c_str()); return WGBSSEG_E_ARG; }
-    const int rc = pair_list_up(c, "pair_hist", a, b, n_pairs, min_cov, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    const size_t ebytes = (size_t)n_pairs * 2 * (size_t)(bins + 1) * 8, cbytes = (size_t)n_pairs * (size_t)bins * (size_t)bins * 8;
-    HIP_TRY(c->ph_edges.ensure(ebytes));
-    HIP_TRY(c->ph_out.ensure(cbytes));
-    HIP_TRY(hipMemcpyAsync(c->ph_edges.p, edges, ebytes, hipMemcpyHostToDevice, c->sA));
-    unsigned long long* dcounts = c->ph_out.as<unsigned long long>();
-    const int32_t* dpa = c->ph_pairs.as<int32_t>();
-    const dim3 grid((unsigned)((c->n_total + WG_PH_RUN - 1) / WG_PH_RUN * n_pairs));
-    const size_t lds = (size_t)wg_ph_lds_bytes(bins);
-    const bool corners = env_flag("WGBSSEG_PAIR_CORNERS", false);     // (read per call: env.h; off: measured 5 % slower on the benchmark rows)
-    const AuxClock clock{c};
-    HIP_TRY(clock.begin());
-    HIP_TRY(hipMemsetAsync(dcounts, 0, cbytes, c->sA));
-#define WG_LAUNCH_PH(E, C) hipLaunchKernelGGL((k_pair_hist<E, C>), grid, dim3(WG_PH_BLOCK), lds, c->sA, c->betas, c->pitch, c->n_total, dpa, dpa + n_pairs, \
-                                              (int32_t)n_pairs, min_cov, bins, c->ph_edges.as<const double>(), dcounts)
-    if (c->elem == 1) { if (corners) WG_LAUNCH_PH(1, true); else WG_LAUNCH_PH(1, false); }
-    else { if (corners) WG_LAUNCH_PH(2, true); else WG_LAUNCH_PH(2, false); }
-#undef WG_LAUNCH_PH
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(clock.end({{counts, dcounts, cbytes}}));
-    return WGBSSEG_OK;
-}
-
-void wgbsseg_pair_hist_limits(int32_t* max_bins, int64_t* run_sites)
-{
-    if (max_bins) *max_bins = WG_PH_MAX_BINS;
-    if (run_sites) *run_sites = WG_PH_RUN;
-}
-
-namespace {
-
-// everything of `n` bytes to fd, whatever write(2) takes at a time; -> 0 or errno
-int write_all(int fd, const char* p, size_t n)
-{
-    while (n) {
-        const ssize_t w = write(fd, p, n);
-        if (w < 0) { if (errno == EINTR) continue; return errno; }
-        p += w; n -= (size_t)w;
-    }
-    return 0;
-}
-
-}  // namespace
-
-int wgbsseg_beta2bed(wgbsseg_ctx* c, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
-                     const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
-                     const wgbsseg_bed_opts* o, int fd, int64_t* lines_written, int64_t* bytes_written,
-                     char* err, size_t errlen)
-{
-    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
-    if (lines_written) *lines_written = 0;
-    if (bytes_written) *bytes_written = 0;
-    if (!c->betas) { set_err(err, errlen, "betas not set"); return WGBSSEG_E_STATE; }
-    if (!c->loci || c->n_loci != c->n_total) { set_err(err, errlen, "loci not set or length differs from the betas (%lld vs %lld)", (long long)c->n_loci, (long long)c->n_total); return WGBSSEG_E_STATE; }
-    BedPlan plan;
-    std::string msg;
-    int rc = wg_bed_plan(sample, c->n_samples, start0, end0, c->n_total, chrom_cum, chrom_names, n_chroms, o, plan, msg);
-    if (rc == WGBSSEG_OK) rc = wg_bed_check_mult(mult, end0 - start0, start0, msg);
-    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
-    c->bed_len_ms = c->bed_emit_ms = c->last_block_sums_ms = 0.0;
-    if (plan.n_slabs == 0) return WGBSSEG_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    for (auto& pair : c->bed_ev) for (Event& e : pair) if (!e.h) HIP_TRY(e.create());
-    // the chromosome table
-    std::vector<char> tab((size_t)n_chroms * (8 + WG_BED_NAME_REC), 0);
-    memcpy(tab.data(), chrom_cum, (size_t)n_chroms * 8);
-    for (int32_t i = 0; i < n_chroms; i++) {
-        char* rec = tab.data() + (size_t)n_chroms * 8 + (size_t)i * WG_BED_NAME_REC;
-        const size_t len = strlen(chrom_names[i]);
-        memcpy(rec, chrom_names[i], len);
-        rec[WG_BED_NAME_REC - 1] = (char)len;
-    }
-    const int64_t max_wgs = BedPlan::workgroups(plan.slab_count(0));
-    HIP_TRY(c->bed_tab.ensure(tab.size()));
-    HIP_TRY(c->bed_wg.ensure((size_t)(3 * max_wgs + 2) * 8));
-    if (mult) HIP_TRY(c->bed_mult.ensure((size_t)plan.slab_count(0) * 2));
-    if (!c->bed_tot.ensure(4 * 8)) { set_err(err, errlen, "beta2bed: out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
-    HIP_TRY(hipMemcpyAsync(c->bed_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice, c->sA));
-    uint64_t* d_bytes = c->bed_wg.as<uint64_t>();
-    uint64_t* d_lines = d_bytes + max_wgs;
-    uint64_t* d_base = d_lines + max_wgs;
-    uint64_t* d_tot = d_base + max_wgs;
-    volatile const uint64_t* h_tot = reinterpret_cast<volatile const uint64_t*>(c->bed_tot.p);
-    wg_bed_args a = {};
-    a.row = c->betas + (size_t)sample * (size_t)c->pitch;
-    a.loci = c->loci;
-    a.mult = mult ? c->bed_mult.as<uint16_t>() : nullptr;
-    a.cum = c->bed_tab.as<int64_t>();
-    a.names = c->bed_tab.as<char>() + (size_t)n_chroms * 8;
-    a.n_chroms = n_chroms; a.min_cov = o->min_cov; a.mean = o->mean ? 1 : 0; a.keep_na = o->keep_na ? 1 : 0;
-    a.stage_bytes = (uint32_t)plan.stage_bytes;
-    const auto slab_args = [&](int64_t k) { wg_bed_args s = a; s.first = plan.slab_first(k); s.n = (int32_t)plan.slab_count(k); return s; };
-    // the length pass and the scan of slab k, its totals on their way home
-    const auto enqueue_length = [&](int64_t k) -> hipError_t {
-        const wg_bed_args s = slab_args(k);
-        const dim3 grid((unsigned)BedPlan::workgroups(s.n));
-        hipError_t e = hipSuccess;
-        if (mult) e = hipMemcpyAsync(c->bed_mult.p, mult + (s.first - start0), (size_t)s.n * 2, hipMemcpyHostToDevice, c->sA);
-        if (e == hipSuccess) e = hipEventRecord(c->bed_ev[k & 1][0], c->sA);
-        if (e != hipSuccess) return e;
-        if (c->elem == 1) hipLaunchKernelGGL(k_bed_len<1>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_bytes, d_lines);
-        else hipLaunchKernelGGL(k_bed_len<2>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_bytes, d_lines);
-        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, c->sA, d_bytes, d_lines, (int64_t)grid.x, d_base, d_tot);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(c->bed_ev[k & 1][1], c->sA);
-        if (e == hipSuccess) e = hipMemcpyAsync(static_cast<uint64_t*>(c->bed_tot.p) + 2 * (k & 1), d_tot, 16, hipMemcpyDeviceToHost, c->sA);
-        return e;
-    };
-    const auto add_ms = [&](double& sum, Event& e0, Event& e1) -> hipError_t {
-        float ms = 0;
-        const hipError_t e = hipEventElapsedTime(&ms, e0, e1);
-        if (e == hipSuccess) sum += ms;
-        return e;
-    };
-    int64_t lines = 0, bytes = 0;
-    uint64_t home_bytes[2] = {0, 0};                             // the text of slab k at home, k & 1
-    int io = 0;
-    HIP_TRY(enqueue_length(0));
-    for (int64_t k = 0; k <= plan.n_slabs && !io; k++) {
-        HIP_TRY(hipStreamSynchronize(c->sA));                    // slab k's totals and slab k-1's text are home
-        if (k > 0 && home_bytes[(k - 1) & 1]) HIP_TRY(add_ms(c->bed_emit_ms, c->bed_ev[(k - 1) & 1][2], c->bed_ev[(k - 1) & 1][3]));
-        if (k < plan.n_slabs) {
-            const int par = (int)(k & 1);
-            HIP_TRY(add_ms(c->bed_len_ms, c->bed_ev[par][0], c->bed_ev[par][1]));
-            const uint64_t tot = h_tot[2 * par];
-            lines += (int64_t)h_tot[2 * par + 1];
-            rc = wg_bed_check_slab_bytes(tot, k, plan.slab_sites, msg);
-            if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
-            home_bytes[par] = tot;
-            if (tot) {
-                const size_t first_size = (size_t)plan.slab_bytes_bound(0);     // (what every slab needs without multiplicities: no regrowth slab by slab)
-                HIP_TRY(c->bed_out[par].ensure((tot > first_size ? (size_t)tot : first_size) + 16));
-                if (!c->bed_home[par].ensure(tot > first_size ? (size_t)tot : first_size)) { set_err(err, errlen, "beta2bed: out of page-locked host memory (%llu bytes)", (unsigned long long)tot); return WGBSSEG_E_NOMEM; }
-                const wg_bed_args s = slab_args(k);
-                const dim3 grid((unsigned)BedPlan::workgroups(s.n));
-                HIP_TRY(hipEventRecord(c->bed_ev[par][2], c->sA));
-                if (c->elem == 1) hipLaunchKernelGGL(k_bed_emit<1>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_base, c->bed_out[par].as<char>());
-                else hipLaunchKernelGGL(k_bed_emit<2>, grid, dim3(WG_BED_BLOCK), 0, c->sA, s, d_base, c->bed_out[par].as<char>());
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(c->bed_ev[par][3], c->sA));
-                HIP_TRY(hipMemcpyAsync(c->bed_home[par].p, c->bed_out[par].p, (size_t)tot, hipMemcpyDeviceToHost, c->sA));
-            }
-            if (k + 1 < plan.n_slabs) HIP_TRY(enqueue_length(k + 1));
-        }
-        if (k > 0 && home_bytes[(k - 1) & 1]) {                  // the device works on slab k (and the lengths of k+1) meanwhile
-            io = write_all(fd, static_cast<const char*>(c->bed_home[(k - 1) & 1].p), (size_t)home_bytes[(k - 1) & 1]);
-            if (!io) bytes += (int64_t)home_bytes[(k - 1) & 1];
-        }
-    }
-    c->last_block_sums_ms = c->bed_len_ms + c->bed_emit_ms;
-    if (bytes_written) *bytes_written = bytes;
-    if (io) {
-        (void)hipStreamSynchronize(c->sA);                       // (what is still in flight lands in buffers the context keeps)
-        set_err(err, errlen, "beta2bed: write failed (errno %d): %s", io, strerror(io));
-        return WGBSSEG_E_IO;
-    }
-    if (lines_written) *lines_written = lines;
-    return WGBSSEG_OK;
-}
-
-void wgbsseg_beta2bed_pass_ms(const wgbsseg_ctx* c, double* length_ms, double* emit_ms)
-{
-    if (length_ms) *length_ms = c ? c->bed_len_ms : 0.0;
-    if (emit_ms) *emit_ms = c ? c->bed_emit_ms : 0.0;
-}
-
-void wgbsseg_beta2bed_limits(int64_t* default_slab, int64_t* max_slab, int32_t* max_stage_bytes, int32_t* max_name)
-{
-    if (default_slab) *default_slab = WG_BED_DEFAULT_SLAB;
-    if (max_slab) *max_slab = WG_BED_MAX_SLAB;
-    if (max_stage_bytes) *max_stage_bytes = WG_BED_STAGE_BYTES;
-    if (max_name) *max_name = WG_BED_MAX_NAME;
-}
 
 int wgbsseg_add_loci(const uint32_t* loci, int64_t n_sites, const int64_t* chrom_cum, const char* const* chrom_names,
                      int32_t n_chroms, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks,
@@ -2800,39 +2425,6 @@ int64_t wgbsseg_format_fixed(const double* v, int64_t n, int32_t digits, char* o
         *p++ = '\n';
     }
     return (int64_t)(p - out);
-}
-
-int wgbsseg_convert_regions(wgbsseg_ctx* c, const int64_t* chrom_lo, const int64_t* chrom_hi, const int64_t* chrom_bp, const int64_t* start,
-                            const int64_t* end, const uint8_t* slow, int64_t n, int64_t* start_cpg, int64_t* end_cpg, char* err, size_t errlen)
-{
-    if (!c) { set_err(err, errlen, "ctx is NULL"); return WGBSSEG_E_ARG; }
-    if (!c->loci) { set_err(err, errlen, "loci not set"); return WGBSSEG_E_STATE; }
-    if (n < 0 || (n && (!chrom_lo || !chrom_hi || !chrom_bp || !start || !end || !slow || !start_cpg || !end_cpg))) { set_err(err, errlen, "bad arguments to convert_regions"); return WGBSSEG_E_ARG; }
-    if (n == 0) return WGBSSEG_OK;
-    for (int64_t i = 0; i < n; i++)
-        if (chrom_lo[i] < 0 || chrom_hi[i] < chrom_lo[i] || chrom_hi[i] > c->n_loci) {
-            set_err(err, errlen, "region %lld: chromosome slice [%lld, %lld) is outside the %lld resident loci", (long long)i, (long long)chrom_lo[i], (long long)chrom_hi[i], (long long)c->n_loci);
-            return WGBSSEG_E_ARG;
-        }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t nb = (size_t)n * 8;
-    HIP_TRY(c->cv_in.ensure(5 * nb + (size_t)n));
-    HIP_TRY(c->cv_out.ensure(2 * nb));
-    char* d = c->cv_in.as<char>();
-    const int64_t* srcs[5] = {chrom_lo, chrom_hi, chrom_bp, start, end};
-    for (int k = 0; k < 5; k++) HIP_TRY(hipMemcpyAsync(d + k * nb, srcs[k], nb, hipMemcpyHostToDevice, c->sA));
-    HIP_TRY(hipMemcpyAsync(d + 5 * nb, slow, (size_t)n, hipMemcpyHostToDevice, c->sA));
-    int64_t* o = c->cv_out.as<int64_t>();
-    const int64_t gx = (n + WG_BLOCK - 1) / WG_BLOCK;
-    if (gx > 0x7fffffff) { set_err(err, errlen, "too many regions for one convert call"); return WGBSSEG_E_ARG; }
-    const AuxClock clock{c};
-    HIP_TRY(clock.begin());
-    hipLaunchKernelGGL(k_convert, dim3((unsigned)gx), dim3(WG_BLOCK), 0, c->sA, c->loci, reinterpret_cast<const int64_t*>(d),
-                       reinterpret_cast<const int64_t*>(d + nb), reinterpret_cast<const int64_t*>(d + 2 * nb), reinterpret_cast<const int64_t*>(d + 3 * nb),
-                       reinterpret_cast<const int64_t*>(d + 4 * nb), reinterpret_cast<const uint8_t*>(d + 5 * nb), n, o, o + n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(clock.end({{start_cpg, o, nb}, {end_cpg, o + n, nb}}));
-    return WGBSSEG_OK;
 }
 
 }  // extern "C"
