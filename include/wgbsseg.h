@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 270            /* 0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 280            /* 0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -397,6 +397,49 @@ int wgbsseg_beta2bed(wgbsseg_ctx* ctx, int32_t sample, int64_t start0, int64_t e
 void wgbsseg_beta2bed_pass_ms(const wgbsseg_ctx* ctx, double* length_ms, double* emit_ms);
 /* the default and the largest slab_sites, the largest (= default) stage_bytes, the longest chromosome name; any pointer may be NULL */
 void wgbsseg_beta2bed_limits(int64_t* default_slab, int64_t* max_slab, int32_t* max_stage_bytes, int32_t* max_name);
+
+/*
+ * The probe table: the counts of chosen sites in chosen resident samples — what `wgbstools beta_to_450k` prints for the sites
+ * of the Illumina 450K / EPIC arrays.  Row r is the resident site site0[r] (0-based; any order, repeats allowed), column j the
+ * resident sample samples[j] (repeats allowed).
+ *
+ * wgbsseg_site_counts: out[r][j] = {meth, cov} of that site in that sample, a HOST buffer of n_rows * n_cols * 2 uint16.
+ *
+ * wgbsseg_site_table: the table as CSV text, formatted on the device and written to the file descriptor `fd`; row r is
+ *
+ *     label_r , v , v , ... v \n        label_r = the bytes labels[label_off[r] .. label_off[r + 1]), copied as they are (the
+ *                                       caller has quoted them where CSV asks for it); label_off has n_rows + 1 entries
+ *     v                                 NA where cov < opts->min_cov; else printf "%.3f" of the double meth / cov, byte for byte
+ *                                       what C prints, ties included (csrc/bed_fmt.h).  min_cov 0 lets cov = 0 through:
+ *                                       0 / 0 is NA, meth / 0 with meth > 0 is inf.  meth > cov is a value like any other.
+ *
+ * The text is produced slab by slab (opts->slab_rows rows; 0 = the default: default_slab_rows of wgbsseg_site_table_limits,
+ * fewer for wide rows, csrc/array_plan.h): one pass gathers the slab's counts into a compact table, a length pass and a scan
+ * place every field, an emit pass formats into LDS and copies out with wide stores; slab k+1 is computed while slab k is
+ * written to fd, through the buffers wgbsseg_beta2bed uses.  Nothing the size of the whole text is allocated.  slab_rows
+ * changes speed only, never a byte.  lines_written / bytes_written (either may be NULL): what went to fd.
+ *
+ * Both work on uint8 rows (wgbsseg_set_betas_*) and uint16 rows (wgbsseg_set_lbetas_host); without rows: WGBSSEG_E_STATE.
+ * WGBSSEG_E_ARG with a message naming the offender: NULL pointers, n_rows < 0, n_cols < 1 or above max_cols, a sample outside
+ * the resident samples, a site outside the resident sites (the row is named), min_cov < 0, a label_off that descends, a label
+ * longer than max_label bytes, slab_rows outside its limits.  n_rows = 0 writes nothing and returns 0.  WGBSSEG_E_IO:
+ * write(2) failed; the message holds "errno N"; the context stays usable.  The kernels' HIP-event time is what
+ * wgbsseg_last_block_sums_ms returns afterwards; wgbsseg_site_table_pass_ms splits it into the gather pass, the length + scan
+ * passes and the emit pass (any pointer may be NULL).
+ */
+int wgbsseg_site_counts(wgbsseg_ctx* ctx, const int64_t* site0, int64_t n_rows, const int32_t* samples, int32_t n_cols,
+                        uint16_t* out, char* err, size_t errlen);
+typedef struct {
+    int32_t min_cov;
+    int32_t reserved;          /* 0 */
+    int64_t slab_rows;         /* 0 = default */
+} wgbsseg_site_table_opts;
+int wgbsseg_site_table(wgbsseg_ctx* ctx, const int64_t* site0, int64_t n_rows, const int32_t* samples, int32_t n_cols,
+                       const char* labels, const int64_t* label_off, const wgbsseg_site_table_opts* opts, int fd,
+                       int64_t* lines_written, int64_t* bytes_written, char* err, size_t errlen);
+void wgbsseg_site_table_pass_ms(const wgbsseg_ctx* ctx, double* gather_ms, double* length_ms, double* emit_ms);
+/* the largest default and the largest slab_rows, the longest label, the most columns; any pointer may be NULL */
+void wgbsseg_site_table_limits(int64_t* default_slab_rows, int64_t* max_slab_rows, int32_t* max_label, int32_t* max_cols);
 
 /*
  * BED regions -> CpG index ranges: the join of `wgbstools convert -L` (convert.py:147-185 chr_thread, :133-145

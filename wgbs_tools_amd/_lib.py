@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 270          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 280          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -42,7 +42,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_bimodal_create', 'wgbsseg_bimodal_feed', 'wgbsseg_bimodal_finish', 'wgbsseg_bimodal_destroy', 'wgbsseg_bimodal_kernel_ms',
            'wgbsseg_debug_bimodal_terms', 'wgbsseg_sample_stats',
            'wgbsseg_pair_ranges', 'wgbsseg_pair_hist', 'wgbsseg_pair_hist_limits',
-           'wgbsseg_beta2bed', 'wgbsseg_beta2bed_pass_ms', 'wgbsseg_beta2bed_limits']
+           'wgbsseg_beta2bed', 'wgbsseg_beta2bed_pass_ms', 'wgbsseg_beta2bed_limits',
+           'wgbsseg_site_counts', 'wgbsseg_site_table', 'wgbsseg_site_table_pass_ms', 'wgbsseg_site_table_limits']
 
 
 class NativeLibraryError(RuntimeError):
@@ -74,6 +75,11 @@ PAIR_RANGE_DTYPE = np.dtype([('n', np.uint64), ('a_min', np.float64), ('a_max', 
 class BedOpts(C.Structure):
     """wgbsseg_bed_opts (include/wgbsseg.h)"""
     _fields_ = [('min_cov', C.c_int32), ('mean', C.c_int32), ('keep_na', C.c_int32), ('stage_bytes', C.c_int32), ('slab_sites', C.c_int64)]
+
+
+class SiteTableOpts(C.Structure):
+    """wgbsseg_site_table_opts (include/wgbsseg.h)"""
+    _fields_ = [('min_cov', C.c_int32), ('reserved', C.c_int32), ('slab_rows', C.c_int64)]
 
 
 class Timings(C.Structure):
@@ -199,6 +205,14 @@ def load():
     L.wgbsseg_beta2bed_pass_ms.argtypes = [vp, vp, vp]
     L.wgbsseg_beta2bed_limits.restype = None
     L.wgbsseg_beta2bed_limits.argtypes = [vp, vp, vp, vp]
+    L.wgbsseg_site_counts.restype = i32
+    L.wgbsseg_site_counts.argtypes = [vp, vp, i64, vp, i32, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_site_table.restype = i32
+    L.wgbsseg_site_table.argtypes = [vp, vp, i64, vp, i32, vp, vp, C.POINTER(SiteTableOpts), C.c_int, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_site_table_pass_ms.restype = None
+    L.wgbsseg_site_table_pass_ms.argtypes = [vp, vp, vp, vp]
+    L.wgbsseg_site_table_limits.restype = None
+    L.wgbsseg_site_table_limits.argtypes = [vp, vp, vp, vp]
     L.wgbsseg_set_site_base.restype = i32
     L.wgbsseg_set_site_base.argtypes = [vp, i64]
     L.wgbsseg_stitch_regions.restype = i32
@@ -540,6 +554,46 @@ class Segmenter:
         self._L.wgbsseg_beta2bed_pass_ms(self._h, C.addressof(a), C.addressof(b))
         return float(a.value), float(b.value)
 
+    def site_counts(self, site0, samples):
+        """wgbsseg_site_counts: the counts of the resident sites `site0` (0-based, any order, repeats allowed) in the resident samples
+        `samples` -> uint16 [len(site0)][len(samples)][2] (meth, cov)"""
+        s = np.ascontiguousarray(site0, dtype=np.int64).ravel()
+        cols = np.ascontiguousarray(samples, dtype=np.int32).ravel()
+        out = np.zeros((s.size, cols.size, 2), dtype=np.uint16)
+        _check(self._L.wgbsseg_site_counts(self._h, s.ctypes.data, s.size, cols.ctypes.data, cols.size, out.ctypes.data, self._err, ERRLEN), self._err)
+        return out
+
+    def site_table(self, fd, site0, samples, labels, min_cov=3, slab_rows=0):
+        """wgbsseg_site_table: a CSV line per site of `site0` — its label (bytes, already quoted where CSV asks for it), then per sample
+        of `samples` the '%.3f' of meth / cov, or NA where cov < min_cov — written to the file descriptor `fd` -> (lines written,
+        bytes written).  A failed write raises OSError with the descriptor's errno (BrokenPipeError for a reader that went away)."""
+        s = np.ascontiguousarray(site0, dtype=np.int64).ravel()
+        cols = np.ascontiguousarray(samples, dtype=np.int32).ravel()
+        labels = [x if isinstance(x, bytes) else str(x).encode() for x in labels]
+        if len(labels) != s.size:
+            raise ValueError('site_table: %d labels for %d sites' % (len(labels), s.size))
+        off = np.zeros(s.size + 1, dtype=np.int64)
+        if labels:
+            np.cumsum(np.fromiter(map(len, labels), dtype=np.int64, count=len(labels)), out=off[1:])
+        blob = b''.join(labels)
+        opts = SiteTableOpts(int(min_cov), 0, int(slab_rows))
+        lines, nbytes = C.c_int64(0), C.c_int64(0)
+        rc = self._L.wgbsseg_site_table(self._h, s.ctypes.data, s.size, cols.ctypes.data, cols.size, blob, off.ctypes.data, C.byref(opts), int(fd),
+                                        C.addressof(lines), C.addressof(nbytes), self._err, ERRLEN)
+        if rc == E_IO:
+            import re
+            found = re.search(r'errno (\d+)', self._err.value.decode(errors='replace'))
+            code = int(found.group(1)) if found else 5
+            raise OSError(code, os.strerror(code))
+        _check(rc, self._err)
+        return int(lines.value), int(nbytes.value)
+
+    def site_table_pass_ms(self):
+        """(gather pass, length + scan passes, emit pass) of the last site_table call, HIP-event milliseconds summed over its slabs"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._L.wgbsseg_site_table_pass_ms(self._h, C.addressof(a), C.addressof(b), C.addressof(c))
+        return float(a.value), float(b.value), float(c.value)
+
     def last_block_sums_ms(self):
         return float(self._L.wgbsseg_last_block_sums_ms(self._h))
 
@@ -736,6 +790,14 @@ def beta2bed_limits():
     a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
     L.wgbsseg_beta2bed_limits(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
     return dict(default_slab=int(a.value), max_slab=int(b.value), max_stage_bytes=int(c.value), max_name=int(d.value))
+
+
+def site_table_limits():
+    """wgbsseg_site_table_limits -> dict(default_slab_rows, max_slab_rows, max_label, max_cols)"""
+    L = load()
+    a, b, c, d = C.c_int64(0), C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    L.wgbsseg_site_table_limits(C.byref(a), C.byref(b), C.byref(c), C.byref(d))
+    return dict(default_slab_rows=int(a.value), max_slab_rows=int(b.value), max_label=int(c.value), max_cols=int(d.value))
 
 
 def _stats_dict(stats):

@@ -1,6 +1,7 @@
 // bed_fmt.h — the text of `wgbstools beta2bed`'s columns, one rule for host and device: decimal digits of an integer, and awk's
 // printf "%.3g" of the double meth / cov (beta2bed.py:18) from the two counts alone, byte for byte, ties included.
-// No HIP needed: g++ compiles it alone (tests/native/bed_host.cpp is the CPU suite's twin of what the kernels run).
+// Below it, by the same argument, printf "%.3f" of that double for `wgbstools beta_to_450k` (wg_fmt_f3).
+// No HIP needed: g++ compiles it alone (tests/native/bed_host.cpp and array_host.cpp are the CPU suite's twins of what the kernels run).
 //
 // "%.3g" prints the EXACT value of the double v = fl(m / c), rounded to three significant decimal digits, half to even.  v differs
 // from the rational m / c by less than one ulp, so the three digits come from the integers: q, r = divmod(m * 10^(2 - e), c) with
@@ -101,4 +102,39 @@ WG_HD uint64_t wg_fmt_g3(uint32_t m, uint32_t c, int* len)
 #undef WG_G3_PUT
     *len = n;
     return out;
+}
+
+// "%.3f" of the double m / c for counts m >= 0, c > 0 below 2^16 (`wgbstools beta_to_450k`): the value in thousandths, rounded as C
+// rounds the EXACT value of v = fl(m / c), half to even.  q, r = divmod(1000 m, c); r decides unless 2 r == c, the exact rational tie,
+// where — as in wg_fmt_g3 — the side is the sign of fma(v, c, -m) and zero goes half to even on q.  The text is q / 1000, a point and
+// the three digits of q % 1000: wg_f3_len / wg_f3_put, at most WG_F3_MAX_LEN bytes.
+#define WG_F3_MAX_LEN 9                // "65535.000"
+
+WG_HD uint32_t wg_fmt_f3(uint32_t m, uint32_t c)
+{
+    const uint32_t num = 1000u * m;                              // below 2^26
+    uint32_t q = num / c;
+    const uint32_t r2 = 2u * (num - q * c);
+    bool up = r2 > c;
+    if (r2 == c) {
+        const double v = (double)m / (double)c;
+        const double s = fma(v, (double)c, -(double)m);
+        up = s > 0.0 || (s == 0.0 && (q & 1u));
+    }
+    return up ? q + 1 : q;
+}
+
+WG_HD int wg_f3_len(uint32_t q) { return wg_dec_len(q / 1000u) + 4; }
+
+// the text of q thousandths at dst (its wg_f3_len(q) bytes); -> their number
+template <class P>
+WG_HD int wg_f3_put(P dst, uint32_t q)
+{
+    const int n = wg_dec_put(dst, q / 1000u);
+    const uint32_t f = q % 1000u;
+    dst[n] = '.';
+    dst[n + 1] = (char)('0' + f / 100u);
+    dst[n + 2] = (char)('0' + f / 10u % 10u);
+    dst[n + 3] = (char)('0' + f % 10u);
+    return n + 4;
 }

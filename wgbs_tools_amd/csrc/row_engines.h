@@ -1,7 +1,7 @@
 // row_engines.h — the calls that work on the context's resident rows (wgbsseg_block_sums, _marker_stats, _sample_stats, _pair_ranges,
-// _pair_hist, _beta2bed, _convert_regions), the helpers they share and their extern "C" entry points.  Part of wgbsseg.hip, which includes
+// _pair_hist, _beta2bed, _convert_regions, _site_counts, _site_table), the helpers they share and their extern "C" entry points.  Part of wgbsseg.hip, which includes
 // it once set_err, HIP_TRY, the owners and the context are in scope; what a call decides on the host is in block_plan.h, stats_plan.h,
-// pair_plan.h and bed_plan.h, this file stages, launches and fetches.
+// pair_plan.h, bed_plan.h and array_plan.h, this file stages, launches and fetches.
 #pragma once
 
 namespace {
@@ -490,6 +490,245 @@ int wgbsseg_convert_regions(wgbsseg_ctx* c, const int64_t* chrom_lo, const int64
     HIP_TRY(hipGetLastError());
     HIP_TRY(clock.end({{start_cpg, o, nb}, {end_cpg, o + n, nb}}));
     return WGBSSEG_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the gather pass of `rows` rows from row `first` of the call's sites on: queued on stream A (array_kernels.h)
+void launch_site_gather(wgbsseg_ctx* c, int64_t first, int64_t rows, int32_t n_cols, uint32_t* cells)
+{
+    wg_gather_args g;
+    g.betas = c->betas; g.pitch = c->pitch;
+    g.site0 = c->site.site0.as<int64_t>() + first;
+    g.samples = c->site.samples.as<int32_t>();
+    g.n_cells = rows * (int64_t)n_cols; g.n_cols = n_cols;
+    const dim3 grid((unsigned)SitePlan::workgroups(g.n_cells));
+    by_elem(c->elem, [&](auto E) { hipLaunchKernelGGL(k_site_gather<decltype(E)::value>, grid, dim3(WG_SITE_BLOCK), 0, c->sA, g, cells); });
+}
+
+// what both probe-table calls begin with: the checks of array_plan.h, then the sites and the samples on the device
+int site_lists_up(wgbsseg_ctx* c, const char* who, const int64_t* site0, int64_t n_rows, const int32_t* samples, int32_t n_cols, char* err, size_t errlen)
+{
+    std::string msg;
+    const int rc = wg_site_check_gather(who, site0, n_rows, samples, n_cols, c->n_samples, c->n_total, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    if (n_rows == 0) return WGBSSEG_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->site.site0.ensure((size_t)n_rows * 8));
+    HIP_TRY(c->site.samples.ensure((size_t)n_cols * 4));
+    HIP_TRY(hipMemcpyAsync(c->site.site0.p, site0, (size_t)n_rows * 8, hipMemcpyHostToDevice, c->sA));
+    HIP_TRY(hipMemcpyAsync(c->site.samples.p, samples, (size_t)n_cols * 4, hipMemcpyHostToDevice, c->sA));
+    return WGBSSEG_OK;
+}
+
+// One site_table call in flight: its plan (array_plan.h), what its launches share, what it has counted and written.  Two slabs are in
+// flight as in BedRun, in BedScratch's buffers and between its events and SiteScratch's; wgbsseg_site_table runs the steps in the order of its loop.
+struct SiteRun {
+    wgbsseg_ctx* c = nullptr;
+    SitePlan plan;
+    int fd = -1;                         // where the text goes
+    char* err = nullptr; size_t errlen = 0;
+    wg_site_args base = {};              // the launch arguments every slab shares
+    BedWgTable wg = {};                  // where the workgroup table keeps what (bed_plan.h)
+    int64_t lines = 0, bytes = 0;        // lines counted | bytes written so far
+    uint64_t home_bytes[2] = {0, 0};     // per parity: the text of the slab that last took it, in bytes
+
+    wg_site_args slab_args(int64_t k) const { wg_site_args s = base; s.first_row = plan.slab_first(k); s.n_fields = (int32_t)plan.fields(plan.slab_count(k)); return s; }
+    uint64_t* wg_at(int64_t word) const { return c->bed.wg.as<uint64_t>() + word; }
+    hipError_t add_ms(double& sum, const Event& e0, const Event& e1) const
+    {
+        float ms = 0;
+        const hipError_t e = hipEventElapsedTime(&ms, e0, e1);
+        if (e == hipSuccess) sum += ms;
+        return e;
+    }
+
+    int tables_up(const char* labels, const int64_t* label_off);   // events and buffers are there, the labels are queued, `base` is filled
+    hipError_t queue_lengths(int64_t k);   // queues slab k's gather pass (g0 .. g1), its length pass and scan (len0 .. len1) and its totals' way home
+    int wait_home(int64_t k);              // waits for the stream: slab k's totals and slab k-1's text are home; reads slab k-1's emit time
+    int take_totals(int64_t k);            // reads slab k's gather and length times and its totals: lines counted, bytes kept for its parity
+    int queue_emit(int64_t k);             // queues slab k's emit pass (emit0 .. emit1) and its text's way home
+    int write_home(int64_t k);             // writes slab k's text, which is home, to fd; -> 0 or errno
+    int finish(int io, int64_t* lines_written, int64_t* bytes_written);   // the call's time and counts; after a failed write, waits for what is still queued
+};
+
+int SiteRun::tables_up(const char* labels, const int64_t* label_off)
+{
+    BedScratch& s = c->bed;
+    SiteScratch& t = c->site;
+    for (auto& ev : s.ev) for (Event* e : {&ev.len0, &ev.len1, &ev.emit0, &ev.emit1}) if (!e->h) HIP_TRY(e->create());
+    for (auto& ev : t.ev) for (Event* e : {&ev.g0, &ev.g1}) if (!e->h) HIP_TRY(e->create());
+    wg = wg_bed_wg_table(SitePlan::workgroups(plan.fields(plan.slab_count(0))));
+    const size_t label_bytes = (size_t)(label_off[plan.n_rows] - label_off[0]);
+    HIP_TRY(s.wg.ensure(wg.size()));
+    HIP_TRY(t.cells.ensure((size_t)plan.cells(plan.slab_count(0)) * 4));
+    HIP_TRY(t.labels.ensure(label_bytes ? label_bytes : 1));
+    HIP_TRY(t.label_off.ensure((size_t)(plan.n_rows + 1) * 8));
+    if (!s.tot.ensure(2 * 2 * 8)) { set_err(err, errlen, "site_table: out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    if (label_bytes) HIP_TRY(hipMemcpyAsync(t.labels.p, labels + label_off[0], label_bytes, hipMemcpyHostToDevice, c->sA));
+    HIP_TRY(hipMemcpyAsync(t.label_off.p, label_off, (size_t)(plan.n_rows + 1) * 8, hipMemcpyHostToDevice, c->sA));
+    base.cells = t.cells.as<uint32_t>();
+    base.labels = t.labels.as<char>();
+    base.label_off = t.label_off.as<int64_t>();
+    base.label_base = label_off[0];
+    base.n_cols = plan.n_cols; base.min_cov = (uint32_t)plan.min_cov;
+    return WGBSSEG_OK;
+}
+
+hipError_t SiteRun::queue_lengths(int64_t k)
+{
+    BedScratch& s = c->bed;
+    const int par = wg_bed_parity(k);
+    const wg_site_args a = slab_args(k);
+    const dim3 grid((unsigned)SitePlan::workgroups(a.n_fields));
+    hipError_t e = hipEventRecord(c->site.ev[par].g0, c->sA);
+    if (e != hipSuccess) return e;
+    launch_site_gather(c, a.first_row, plan.slab_count(k), plan.n_cols, c->site.cells.as<uint32_t>());
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(c->site.ev[par].g1, c->sA);
+    if (e == hipSuccess) e = hipEventRecord(s.ev[par].len0, c->sA);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_site_len, grid, dim3(WG_SITE_BLOCK), 0, c->sA, a, wg_at(wg.bytes), wg_at(wg.lines));
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, c->sA, wg_at(wg.bytes), wg_at(wg.lines), (int64_t)grid.x, wg_at(wg.base), wg_at(wg.tot_bytes));
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(s.ev[par].len1, c->sA);
+    if (e == hipSuccess) e = hipMemcpyAsync(static_cast<uint64_t*>(s.tot.p) + 2 * par, wg_at(wg.tot_bytes), 16, hipMemcpyDeviceToHost, c->sA);
+    return e;
+}
+
+int SiteRun::wait_home(int64_t k)
+{
+    HIP_TRY(hipStreamSynchronize(c->sA));
+    if (k == 0) return WGBSSEG_OK;
+    const int before = wg_bed_parity(k - 1);
+    if (home_bytes[before]) HIP_TRY(add_ms(c->site.emit_ms, c->bed.ev[before].emit0, c->bed.ev[before].emit1));
+    return WGBSSEG_OK;
+}
+
+int SiteRun::take_totals(int64_t k)
+{
+    const int par = wg_bed_parity(k);
+    HIP_TRY(add_ms(c->site.gather_ms, c->site.ev[par].g0, c->site.ev[par].g1));
+    HIP_TRY(add_ms(c->site.len_ms, c->bed.ev[par].len0, c->bed.ev[par].len1));
+    volatile const uint64_t* tot = static_cast<volatile const uint64_t*>(c->bed.tot.p) + 2 * par;      // (bytes, lines)
+    lines += (int64_t)tot[1];
+    home_bytes[par] = tot[0];
+    return WGBSSEG_OK;
+}
+
+int SiteRun::queue_emit(int64_t k)
+{
+    BedScratch& s = c->bed;
+    const int par = wg_bed_parity(k);
+    const uint64_t tot = home_bytes[par];
+    if (!tot) return WGBSSEG_OK;
+    const BedTextCap cap = wg_bed_text_capacity(tot, plan.slab_bytes_bound(0));
+    HIP_TRY(s.out[par].ensure(cap.device));
+    if (!s.home[par].ensure(cap.home)) { set_err(err, errlen, "site_table: out of page-locked host memory (%llu bytes)", (unsigned long long)tot); return WGBSSEG_E_NOMEM; }
+    const wg_site_args a = slab_args(k);
+    const dim3 grid((unsigned)SitePlan::workgroups(a.n_fields));
+    HIP_TRY(hipEventRecord(s.ev[par].emit0, c->sA));
+    hipLaunchKernelGGL(k_site_emit, grid, dim3(WG_SITE_BLOCK), 0, c->sA, a, wg_at(wg.base), s.out[par].as<char>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s.ev[par].emit1, c->sA));
+    HIP_TRY(hipMemcpyAsync(s.home[par].p, s.out[par].p, (size_t)tot, hipMemcpyDeviceToHost, c->sA));
+    return WGBSSEG_OK;
+}
+
+int SiteRun::write_home(int64_t k)
+{
+    const int par = wg_bed_parity(k);
+    if (!home_bytes[par]) return 0;
+    const int io = write_all(fd, static_cast<const char*>(c->bed.home[par].p), (size_t)home_bytes[par]);
+    if (!io) bytes += (int64_t)home_bytes[par];
+    return io;
+}
+
+int SiteRun::finish(int io, int64_t* lines_written, int64_t* bytes_written)
+{
+    c->last_block_sums_ms = c->site.gather_ms + c->site.len_ms + c->site.emit_ms;
+    if (bytes_written) *bytes_written = bytes;
+    if (io) {
+        (void)hipStreamSynchronize(c->sA);                       // (what is still in flight lands in buffers the context keeps)
+        set_err(err, errlen, "site_table: write failed (errno %d): %s", io, strerror(io));
+        return WGBSSEG_E_IO;
+    }
+    if (lines_written) *lines_written = lines;
+    return WGBSSEG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// checks (array_plan.h) -> the lists up -> one gather launch over every row -> fetch
+int wgbsseg_site_counts(wgbsseg_ctx* c, const int64_t* site0, int64_t n_rows, const int32_t* samples, int32_t n_cols, uint16_t* out, char* err, size_t errlen)
+{
+    if (const int rc = need_rows(c, err, errlen)) return rc;
+    if (n_rows > 0 && !out) { set_err(err, errlen, "site_counts: out is NULL"); return WGBSSEG_E_ARG; }
+    const int rc = site_lists_up(c, "site_counts", site0, n_rows, samples, n_cols, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    c->last_block_sums_ms = 0.0;
+    if (n_rows == 0) return WGBSSEG_OK;
+    const size_t obytes = (size_t)n_rows * (size_t)n_cols * 4;
+    if (SitePlan::workgroups((int64_t)(obytes / 4)) > 0x7fffffff) { set_err(err, errlen, "site_counts: %lld rows x %d columns are too many cells for one call", (long long)n_rows, (int)n_cols); return WGBSSEG_E_ARG; }
+    HIP_TRY(c->site.cells.ensure(obytes));
+    const AuxClock clock{c};
+    HIP_TRY(clock.begin());
+    launch_site_gather(c, 0, n_rows, n_cols, c->site.cells.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(clock.end({{out, c->site.cells.p, obytes}}));      // (a cell is its {meth, cov} as two uint16)
+    return WGBSSEG_OK;
+}
+
+// state checks -> plan (array_plan.h) -> the slab pipeline: while the device emits slab k and gathers and measures slab k+1, the host writes slab k-1
+int wgbsseg_site_table(wgbsseg_ctx* c, const int64_t* site0, int64_t n_rows, const int32_t* samples, int32_t n_cols, const char* labels,
+                       const int64_t* label_off, const wgbsseg_site_table_opts* o, int fd, int64_t* lines_written, int64_t* bytes_written,
+                       char* err, size_t errlen)
+{
+    if (c && lines_written) *lines_written = 0;
+    if (c && bytes_written) *bytes_written = 0;
+    if (const int rc = need_rows(c, err, errlen)) return rc;
+    SiteRun run;
+    run.c = c; run.fd = fd; run.err = err; run.errlen = errlen;
+    std::string msg;
+    int rc = wg_site_check_gather("site_table", site0, n_rows, samples, n_cols, c->n_samples, c->n_total, msg);
+    if (rc == WGBSSEG_OK) rc = wg_site_plan(n_rows, n_cols, labels, label_off, o, run.plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    c->site.gather_ms = c->site.len_ms = c->site.emit_ms = c->last_block_sums_ms = 0.0;
+    const int64_t n = run.plan.n_slabs;
+    if (n == 0) return WGBSSEG_OK;
+    rc = site_lists_up(c, "site_table", site0, n_rows, samples, n_cols, err, errlen);
+    if (rc == WGBSSEG_OK) rc = run.tables_up(labels, label_off);
+    if (rc != WGBSSEG_OK) return rc;
+    HIP_TRY(run.queue_lengths(0));
+    int io = 0;
+    for (int64_t k = 0; k <= n && !io; k++) {
+        rc = run.wait_home(k);                                   // slab k's totals and slab k-1's text arrive
+        if (rc == WGBSSEG_OK && k < n) rc = run.take_totals(k);
+        if (rc == WGBSSEG_OK && k < n) rc = run.queue_emit(k);   // slab k is emitted ...
+        if (rc != WGBSSEG_OK) return rc;
+        if (k + 1 < n) HIP_TRY(run.queue_lengths(k + 1));        // ... and slab k+1 gathered and measured behind it: one cell table serves both
+        if (k > 0) io = run.write_home(k - 1);                   // slab k-1 is written while the device works
+    }
+    return run.finish(io, lines_written, bytes_written);
+}
+
+void wgbsseg_site_table_pass_ms(const wgbsseg_ctx* c, double* gather_ms, double* length_ms, double* emit_ms)
+{
+    if (gather_ms) *gather_ms = c ? c->site.gather_ms : 0.0;
+    if (length_ms) *length_ms = c ? c->site.len_ms : 0.0;
+    if (emit_ms) *emit_ms = c ? c->site.emit_ms : 0.0;
+}
+
+void wgbsseg_site_table_limits(int64_t* default_slab_rows, int64_t* max_slab_rows, int32_t* max_label, int32_t* max_cols)
+{
+    if (default_slab_rows) *default_slab_rows = WG_SITE_DEFAULT_SLAB_ROWS;
+    if (max_slab_rows) *max_slab_rows = WG_SITE_MAX_SLAB_ROWS;
+    if (max_label) *max_label = WG_SITE_MAX_LABEL;
+    if (max_cols) *max_cols = WG_SITE_MAX_COLS;
 }
 
 }  // extern "C"

@@ -43,6 +43,7 @@
 #include "stats_kernels.h"
 #include "pair_kernels.h"
 #include "bed_kernels.h"
+#include "array_kernels.h"
 #include "plain_dp.h"
 #include "stitch.h"
 #include "add_loci.h"
@@ -92,6 +93,16 @@ struct BedScratch {
     PinnedBuf home[2], tot;
     struct PassEvents { Event len0, len1, emit0, emit1; } ev[2];
     double len_ms = 0.0, emit_ms = 0.0;
+};
+
+// What wgbsseg_site_counts and wgbsseg_site_table keep between calls (row_engines.h, SiteRun) beyond BedScratch's workgroup table, text buffers,
+// totals and pass events, which the probe table shares with beta2bed: the rows' sites | the columns' samples | the label bytes | their
+// offsets | the compact cell table of one slab (site_counts: of the whole call) | per slab parity the events around the gather pass |
+// the three passes' times of the last call.
+struct SiteScratch {
+    DevBuf site0, samples, labels, label_off, cells;
+    struct GatherEvents { Event g0, g1; } ev[2];
+    double gather_ms = 0.0, len_ms = 0.0, emit_ms = 0.0;
 };
 
 struct wgbsseg_ctx {
@@ -155,6 +166,7 @@ struct wgbsseg_ctx {
     DevBuf st_ranges, st_parts;     // wgbsseg_sample_stats: the range table | the tiles' partial results and the per-sample results
     DevBuf ph_pairs, ph_edges, ph_out;   // wgbsseg_pair_ranges / _pair_hist: the pair list (a | b) | the edges | the ranges or the counts
     BedScratch bed;                      // wgbsseg_beta2bed
+    SiteScratch site;                    // wgbsseg_site_counts, wgbsseg_site_table
     std::vector<int32_t> h_stage_bounds;
     // the short division core of the narrow scoring tiles: verified on the device per pseudo count (k_check_div)
     float divs_pc = -1.0f;     // pseudo count the verdict below is for
@@ -2230,7 +2242,7 @@ int wgbsseg_prefix_sums(wgbsseg_ctx* c, int64_t start0, int64_t len, uint32_t* o
 
 }  // extern "C"
 
-#include "row_engines.h"      // the calls on the resident rows (block_sums, marker_stats, sample_stats, the pair calls, beta2bed, convert_regions)
+#include "row_engines.h"      // the calls on the resident rows (block_sums, marker_stats, sample_stats, the pair calls, beta2bed, the probe table, convert_regions)
 
 // the text tables: loci and CpG columns, block and BED files parsed and written on the host (add_loci.h, table_io.h)
 extern "C" {

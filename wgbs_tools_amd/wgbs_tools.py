@@ -4,8 +4,9 @@ MI355X-native hot path — and the steps either side of it that work on the same
 indexes, what feeds `segment -L`), `pat2beta` (the producer of the beta files), `beta_to_blocks`, `beta_to_table` and `find_markers` (the reductions over the blocks it writes) `homog` (the
 reads' U / X / M counts over those blocks), `test_bimodal` (the per-block two-allele test over the same reads),
 `beta_cov` / `beta_stats` (the per-sample coverage and methylation summary read before choosing what goes into `segment`),
-`compare_betas` (the 2-D histogram of every pair of those files: which samples agree) and `beta2bed` (a file's sites as BED
-text, formatted on the device);
+`compare_betas` (the 2-D histogram of every pair of those files: which samples agree), `beta2bed` (a file's sites as BED
+text, formatted on the device) and `beta_to_450k` (the files' values at the Illumina 450K / EPIC probes as one CSV table, gathered
+and formatted on the device);
 every other reference subcommand is out of scope and says so."""
 import sys
 
@@ -13,12 +14,12 @@ from .genome import IllegalArgumentError, eprint
 
 VERSION = '0.2.0-mi355x'
 COMMANDS = ['segment', 'convert', 'pat2beta', 'beta_to_blocks', 'beta_to_table', 'find_markers', 'homog', 'test_bimodal',
-            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed']
+            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k']
 # reference command list (wgbs_tools.py:11-48), for the "not in this build" message
 REFERENCE_ONLY = ['view', 'merge', 'cview', 'index',
                   'beta2bw', 'bam2pat', 'mbias', 'init_genome', 'set_default_ref', 'vis', 'pat_fig',
                   'dmb', 'mix_pat', 'bed2beta',
-                  'split_by_allele', 'split_by_meth', 'frag_len', 'add_cpg_counts', 'beta_to_450k']
+                  'split_by_allele', 'split_by_meth', 'frag_len', 'add_cpg_counts']
 
 
 def print_help():
