@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 280            /* 0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 290            /* 0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -610,6 +610,32 @@ int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char
 void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b);
 double wgbsseg_bimodal_kernel_ms(wgbsseg_bimodal* b);
 int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t count, uint64_t* out);
+
+/*
+ * BGZF bytes as they lie in a .pat.gz, inflated on the device (the second way to feed the three engines above; an engine takes text or
+ * BGZF bytes, not both).  feed_bgzf(): `bytes` = any number of whole BGZF members (gzip members of at most 64 KB of text whose extra
+ * field holds the 'BC' subfield), possibly followed by the beginning of one more; *consumed = the bytes of the whole members, the
+ * caller hands the rest in again in front of what follows in the file.  The members are inflated by one kernel launch, one member per
+ * wavefront, into the text buffer the engine's kernels read; the text behind the call's last newline is kept on the host and put in
+ * front of the next call's text, so lines may straddle members and calls, and byte offsets in finish()'s refusals are those of the
+ * inflated text, as with feed().  finish() first feeds a last line that has no newline.  Refused at once, naming the file offset: a
+ * member that is gzip but not BGZF, a BSIZE smaller than the member's header and trailer, ISIZE > 65536, and a corrupt member among
+ * those the host inflates to find the last newline.  A corrupt member met on the device is reported by finish(), before any refusal
+ * of the text: "Invalid gzip data: BGZF member at file offset N: <what>".  A stream is accepted where zlib's raw inflate accepts it and
+ * its text is ISIZE bytes long; CRC32 is not checked.
+ * inflate_ms(): device time (HIP events) of the inflate launches so far; waits for them.  < 0: error.
+ * wgbsseg_bgzf_inflate: the whole members of `bytes` inflated on `device` into out[0 .. *out_len) (WGBSSEG_E_CAPACITY when out_cap is
+ * too small; *consumed as above); WGBSSEG_E_ARG with the message above for the first corrupt member (its text reads '\n' from where
+ * the decoder stopped).
+ */
+int wgbsseg_patbeta_feed_bgzf(wgbsseg_patbeta* pb, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen);
+int wgbsseg_homog_feed_bgzf(wgbsseg_homog* h, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen);
+int wgbsseg_bimodal_feed_bgzf(wgbsseg_bimodal* b, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen);
+double wgbsseg_patbeta_inflate_ms(wgbsseg_patbeta* pb);
+double wgbsseg_homog_inflate_ms(wgbsseg_homog* h);
+double wgbsseg_bimodal_inflate_ms(wgbsseg_bimodal* b);
+int wgbsseg_bgzf_inflate(int device, const void* bytes, int64_t n_bytes, void* out, int64_t out_cap, int64_t* out_len, int64_t* consumed,
+                         char* err, size_t errlen);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

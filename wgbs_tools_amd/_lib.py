@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 280          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 290          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -43,7 +43,9 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_debug_bimodal_terms', 'wgbsseg_sample_stats',
            'wgbsseg_pair_ranges', 'wgbsseg_pair_hist', 'wgbsseg_pair_hist_limits',
            'wgbsseg_beta2bed', 'wgbsseg_beta2bed_pass_ms', 'wgbsseg_beta2bed_limits',
-           'wgbsseg_site_counts', 'wgbsseg_site_table', 'wgbsseg_site_table_pass_ms', 'wgbsseg_site_table_limits']
+           'wgbsseg_site_counts', 'wgbsseg_site_table', 'wgbsseg_site_table_pass_ms', 'wgbsseg_site_table_limits',
+           'wgbsseg_patbeta_feed_bgzf', 'wgbsseg_homog_feed_bgzf', 'wgbsseg_bimodal_feed_bgzf',
+           'wgbsseg_patbeta_inflate_ms', 'wgbsseg_homog_inflate_ms', 'wgbsseg_bimodal_inflate_ms', 'wgbsseg_bgzf_inflate']
 
 
 class NativeLibraryError(RuntimeError):
@@ -281,6 +283,15 @@ def load():
     L.wgbsseg_bimodal_destroy.argtypes = [vp]
     L.wgbsseg_bimodal_kernel_ms.restype = C.c_double
     L.wgbsseg_bimodal_kernel_ms.argtypes = [vp]
+    for eng in ('patbeta', 'homog', 'bimodal'):
+        f = getattr(L, 'wgbsseg_%s_feed_bgzf' % eng)
+        f.restype = i32
+        f.argtypes = [vp, C.c_char_p, i64, C.POINTER(i64), C.c_char_p, C.c_size_t]
+        f = getattr(L, 'wgbsseg_%s_inflate_ms' % eng)
+        f.restype = C.c_double
+        f.argtypes = [vp]
+    L.wgbsseg_bgzf_inflate.restype = i32
+    L.wgbsseg_bgzf_inflate.argtypes = [i32, C.c_char_p, i64, vp, i64, C.POINTER(i64), C.POINTER(i64), C.c_char_p, C.c_size_t]
     L.wgbsseg_marker_stats.restype = i32
     L.wgbsseg_marker_stats.argtypes = [vp, vp, i32, vp, i32, i64, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_add_loci.restype = i32
@@ -675,6 +686,17 @@ class _PatFeed:
         """text: bytes made of whole lines (must end with a newline)"""
         self._call('feed', self._h, text, len(text))
 
+    def feed_bgzf(self, data):
+        """data: bytes of a BGZF file from a member's first byte on -> the number of bytes taken (whole members); the caller hands the
+        rest in again in front of what follows.  An engine takes feed() or feed_bgzf(), not both."""
+        used = C.c_int64(0)
+        self._call('feed_bgzf', self._h, data, len(data), C.byref(used))
+        return int(used.value)
+
+    def inflate_ms(self):
+        """device time of the inflate launches of every feed_bgzf so far (waits for them)"""
+        return float(getattr(self._L, 'wgbsseg_%s_inflate_ms' % self._abi)(self._h))
+
     def kernel_ms(self):
         """device time of the timed launches over every chunk fed so far (waits for them): the counting kernel of PatBeta and
         Homog, every launch of Bimodal"""
@@ -748,6 +770,34 @@ class Bimodal(_PatFeed):
         cnt = np.empty((self.n_blocks, 3), dtype=np.int64)
         self._call('finish', self._h, ll.ctypes.data, cnt.ctypes.data)
         return ll, cnt
+
+
+def bgzf_inflate(data, device=0, refusal=False):
+    """wgbsseg_bgzf_inflate: the whole BGZF members at the front of `data`, inflated on the device -> (their text, the bytes they take).
+    A corrupt member raises SegmentorError naming its offset in `data`; with refusal=True it does not: -> (text, bytes taken, the
+    message about the first corrupt member or None), the text of a corrupt member reading newlines from where the decoder stopped."""
+    L = load()
+    cap = 0
+    pos = 0
+    while True:                                                   # room: the sum of ISIZE over the whole members
+        size = _bgzf_member_size(data, pos)
+        if size is None or pos + size > len(data):
+            break
+        cap += int.from_bytes(data[pos + size - 4:pos + size], 'little')
+        pos += size
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    n, used = C.c_int64(0), C.c_int64(0)
+    err = C.create_string_buffer(ERRLEN)
+    rc = L.wgbsseg_bgzf_inflate(int(device), data, len(data), out.ctypes.data, out.size, C.byref(n), C.byref(used), err, ERRLEN)
+    if refusal and rc == E_ARG and used.value:                    # (a refusal of the walk takes no bytes)
+        return out[:n.value].tobytes(), int(used.value), err.value.decode(errors='replace')
+    _check(rc, err)
+    return (out[:n.value].tobytes(), int(used.value), None) if refusal else (out[:n.value].tobytes(), int(used.value))
+
+
+def _bgzf_member_size(buf, pos):
+    from .pat2beta import _bgzf_block_size
+    return _bgzf_block_size(buf, pos)
 
 
 def debug_homog_bins(edges, max_total):

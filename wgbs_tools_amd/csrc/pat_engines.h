@@ -6,20 +6,31 @@
 // The pat-text feed of an engine (wgbsseg_patbeta / _homog / _bimodal): one device and stream; text chunks through two page-locked
 // staging buffers and two device buffers, so that the caller's decompression of chunk k+1 overlaps the copy and the kernels of
 // chunk k; the input offset of the next chunk; and the device time of the launches the engine brackets with span_begin / span_end.
+// There are two ways to fill text[k]: stage_chunk copies text the caller inflated; stage_bgzf copies BGZF bytes as they lie in the file
+// (with their member table, inflate_plan.h) and has k_bgzf_inflate write the members' text behind the carry — the end of the call
+// before, from its last newline on, which is kept on the host.  Everything behind the staging is the same for both.
 // Teardown: an engine's buffers — its own and the feed's — must not go while the stream may still use them.  Members go in reverse order of
 // declaration and an engine's `feed` comes first, so declaration order alone would free the engine's buffers before the feed had a say: every
 // engine's destructor calls drain() instead (explicit, one line each), and so does the feed's own for the buffers it holds itself.
 struct PatFeed {
+    enum { LAUNCHES = 0, INFLATE = 1 };                           // the two timed spans: the engine's launches, k_bgzf_inflate
+    enum { TEXT = 1, BGZF = 2 };                                  // what the engine is fed (one of the two, once it has been fed)
     int device = 0;
     Stream st;                                                    // (declared first: goes last)
     PinnedBuf stage[2];
     DevBuf text[2];
+    PinnedBuf cstage[2];                                          // BGZF: the member table, the compressed bytes, the carry
+    DevBuf comp[2];                                               //       the member table and the compressed bytes
+    DevBuf bad_member;                                            //       (file offset << 8 | reason) of the first member refused, ~0: none
+    std::string carry;                                            //       the text behind the last newline of the calls so far
+    unsigned long long file_off = 0;                              //       BGZF bytes consumed so far
+    int mode = 0;
     Event ev[2];                                                  // after the work on slot k's text
     bool busy[2] = {false, false};
     int k = 0;                                                    // the slot of the next chunk
     unsigned long long fed = 0;                                   // bytes fed so far
-    double span_ms = 0.0;                                         // the spans read so far
-    std::deque<std::pair<Event, Event>> spans;                    // recorded, in stream order, not read yet
+    double span_ms[2] = {0.0, 0.0};                               // the spans read so far
+    std::deque<std::pair<Event, Event>> spans[2];                 // recorded, in stream order, not read yet
     std::vector<Event> spare;                                     // the events of read spans, for the next ones
 
     int open(int dev, char* err, size_t errlen)
@@ -38,12 +49,22 @@ struct PatFeed {
         collect();
     }
     ~PatFeed() { drain(); }
+    int claim(int want, const char* name, char* err, size_t errlen)
+    {
+        if (mode && mode != want) { set_err(err, errlen, "%s: feed and feed_bgzf cannot be mixed on one engine", name); return WGBSSEG_E_ARG; }
+        mode = want;
+        return WGBSSEG_OK;
+    }
     // the checks of a feed call: -1 when refused (err set), 0 for an empty chunk, else the chunk's number of tiles
     static int64_t tiles(const char* name, const void* engine, const char* text, int64_t n_bytes, char* err, size_t errlen)
     {
         if (!engine || (n_bytes && !text) || n_bytes < 0) { set_err(err, errlen, "bad arguments to %s_feed", name); return -1; }
         if (n_bytes == 0) return 0;
         if (text[n_bytes - 1] != '\n') { set_err(err, errlen, "%s_feed: a chunk must end with a complete line", name); return -1; }
+        return tiles_of(name, n_bytes, err, errlen);
+    }
+    static int64_t tiles_of(const char* name, int64_t n_bytes, char* err, size_t errlen)
+    {
         const int64_t gx = (n_bytes + WG_PAT_TILE - 1) / WG_PAT_TILE;     // one workgroup per tile of text
         if (gx > 0x7fffffff) { set_err(err, errlen, "%s_feed: chunk too large", name); return -1; }
         return gx;
@@ -59,6 +80,30 @@ struct PatFeed {
         *dev = text[k].as<char>();
         return WGBSSEG_OK;
     }
+    // the same for a planned BGZF call: the member table and the compressed bytes to comp[k], the carry to the front of text[k],
+    // k_bgzf_inflate (a timed span of its own) for the members' text behind it
+    int stage_bgzf(const void* bytes, const BgzfPlan& p, const char** dev, char* err, size_t errlen)
+    {
+        if (busy[k]) { HIP_TRY(hipEventSynchronize(ev[k])); collect(); }
+        const size_t tb = (size_t)p.n_dev * sizeof(wg_bgzf_member), cb = (size_t)p.comp_bytes, cin = (size_t)p.carry_in;
+        if (!cstage[k].ensure(tb + cb + cin)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+        HIP_TRY(comp[k].ensure(tb + cb));
+        HIP_TRY(text[k].ensure((size_t)p.text_cap));
+        if (!bad_member.p) { HIP_TRY(bad_member.ensure(8)); HIP_TRY(hipMemsetAsync(bad_member.p, 0xff, 8, st)); }
+        char* host = static_cast<char*>(cstage[k].p);
+        memcpy(host, p.members.data(), tb);
+        memcpy(host + tb, bytes, cb);
+        memcpy(host + tb + cb, carry.data(), cin);
+        HIP_TRY(hipMemcpyAsync(comp[k].p, host, tb + cb, hipMemcpyHostToDevice, st));
+        if (cin) HIP_TRY(hipMemcpyAsync(text[k].p, host + tb + cb, cin, hipMemcpyHostToDevice, st));
+        HIP_TRY(span_begin(INFLATE));
+        hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)((p.n_dev + WG_INF_WAVES - 1) / WG_INF_WAVES)), dim3(64 * WG_INF_WAVES), 0, st,
+                           comp[k].as<uint8_t>() + tb, comp[k].as<wg_bgzf_member>(), p.n_dev, text[k].as<uint8_t>(), bad_member.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(span_end(INFLATE));
+        *dev = text[k].as<char>();
+        return WGBSSEG_OK;
+    }
     // the chunk's work has been queued: the slot is busy until the stream passes here
     hipError_t chunk_queued(int64_t n_bytes)
     {
@@ -68,7 +113,7 @@ struct PatFeed {
         fed += (unsigned long long)n_bytes;
         return e;
     }
-    hipError_t span_begin()
+    hipError_t span_begin(int which = LAUNCHES)
     {
         Event e[2];
         for (auto& x : e) {
@@ -76,21 +121,19 @@ struct PatFeed {
             const hipError_t r = x.create();
             if (r != hipSuccess) return r;
         }
-        spans.emplace_back(std::move(e[0]), std::move(e[1]));
-        return hipEventRecord(spans.back().first, st);
+        spans[which].emplace_back(std::move(e[0]), std::move(e[1]));
+        return hipEventRecord(spans[which].back().first, st);
     }
-    hipError_t span_end() { return hipEventRecord(spans.back().second, st); }
-    // A feed call of an engine whose chunk is one launch: the checks, the chunk's copy, `before` (untimed stream work in front of the
-    // launch), then launch(tiles, device text) as one timed span.  Neither is called for a chunk that is refused or empty.
-    template <class Engine, class Before, class Launch>
-    static int one_launch(const char* name, Engine* e, const char* host, int64_t n_bytes, char* err, size_t errlen, Before&& before, Launch&& launch)
+    hipError_t span_end(int which = LAUNCHES) { return hipEventRecord(spans[which].back().second, st); }
+    // A staged chunk of an engine whose chunk is one launch: stage(&device text) (the chunk's copy, either way), `before` (untimed stream
+    // work in front of the launch), then launch(tiles, device text) as one timed span.
+    template <class Engine, class Stage, class Before, class Launch>
+    static int one_launch(Engine* e, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen, Before&& before, Launch&& launch)
     {
-        const int64_t gx = tiles(name, e, host, n_bytes, err, errlen);
-        if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
         PatFeed& f = e->feed;
         HIP_TRY(hipSetDevice(f.device));
         const char* dtext = nullptr;
-        const int rc = f.stage_chunk(host, n_bytes, &dtext, err, errlen);
+        const int rc = stage(&dtext);
         if (rc != WGBSSEG_OK) return rc;
         HIP_TRY(before());
         HIP_TRY(f.span_begin());
@@ -100,23 +143,87 @@ struct PatFeed {
         HIP_TRY(f.chunk_queued(n_bytes));
         return WGBSSEG_OK;
     }
+    // A feed call with text: the checks, then chunk(n_bytes, tiles, stage) — the engine's work on a chunk that stage() puts on the device.
+    // Not called for a chunk that is refused or empty.
+    template <class Engine, class Chunk>
+    static int feed_text(const char* name, Engine* e, const char* host, int64_t n_bytes, char* err, size_t errlen, Chunk&& chunk)
+    {
+        const int64_t gx = tiles(name, e, host, n_bytes, err, errlen);
+        if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
+        PatFeed& f = e->feed;
+        const int rc = f.claim(TEXT, name, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        return chunk(n_bytes, gx, [&](const char** dev) { return f.stage_chunk(host, n_bytes, dev, err, errlen); });
+    }
+    // A feed call with BGZF bytes: the plan (members, line rule), then the same chunk() over the complete lines of carry + members, staged
+    // by stage_bgzf; the text behind the last newline becomes the carry.  *consumed: the bytes of the complete members.
+    template <class Engine, class Chunk>
+    static int feed_bgzf(const char* name, Engine* e, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen, Chunk&& chunk)
+    {
+        if (!e || !consumed || n_bytes < 0 || (n_bytes && !bytes)) { set_err(err, errlen, "bad arguments to %s_feed_bgzf", name); return WGBSSEG_E_ARG; }
+        *consumed = 0;
+        PatFeed& f = e->feed;
+        int rc = f.claim(BGZF, name, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        BgzfPlan p;
+        std::string msg;
+        rc = plan_bgzf(static_cast<const uint8_t*>(bytes), n_bytes, f.file_off, f.carry, p, msg);
+        if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+        if (p.n_text > 0) {
+            const int64_t gx = tiles_of(name, p.n_text, err, errlen);
+            if (gx < 0) return WGBSSEG_E_ARG;
+            HIP_TRY(hipSetDevice(f.device));
+            rc = chunk(p.n_text, gx, [&](const char** dev) { return f.stage_bgzf(bytes, p, dev, err, errlen); });
+            if (rc != WGBSSEG_OK) return rc;
+        }
+        f.carry = std::move(p.carry);
+        f.file_off += (unsigned long long)p.consumed;
+        *consumed = p.consumed;
+        return WGBSSEG_OK;
+    }
+    // finish(): a last line without its newline is still in the carry; it is fed as text, with the newline (as pat_chunks does)
+    template <class Chunk>
+    int flush_carry(const char* name, Chunk&& chunk, char* err, size_t errlen)
+    {
+        if (carry.empty()) return WGBSSEG_OK;
+        std::string last;
+        last.swap(carry);
+        last.push_back('\n');
+        const int64_t n = (int64_t)last.size(), gx = tiles_of(name, n, err, errlen);
+        if (gx < 0) return WGBSSEG_E_ARG;
+        return chunk(n, gx, [&](const char** dev) { return stage_chunk(last.data(), n, dev, err, errlen); });      // (copied before this returns)
+    }
+    // finish(): a member k_bgzf_inflate refused comes before any refusal of the text.  Waits for the stream.
+    int inflate_refused(char* err, size_t errlen)
+    {
+        if (!bad_member.p) return WGBSSEG_OK;
+        unsigned long long bad = ~0ULL;
+        HIP_TRY(hipMemcpyAsync(&bad, bad_member.p, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (bad == ~0ULL) return WGBSSEG_OK;
+        std::string msg;
+        (void)wg_inflate_refuse(msg, bad >> 8, (int)(bad & 0xff));
+        set_err(err, errlen, "%s", msg.c_str());
+        return WGBSSEG_E_ARG;
+    }
     // adds the spans the stream has passed to span_ms (in order: the first one still running ends the walk)
     void collect()
     {
-        while (!spans.empty()) {
-            float ms = 0.f;
-            const hipError_t e = hipEventElapsedTime(&ms, spans.front().first, spans.front().second);
-            if (e == hipErrorNotReady) break;
-            if (e == hipSuccess) span_ms += (double)ms;
-            spare.push_back(std::move(spans.front().first)); spare.push_back(std::move(spans.front().second));
-            spans.pop_front();
-        }
+        for (int w = 0; w < 2; w++)
+            while (!spans[w].empty()) {
+                float ms = 0.f;
+                const hipError_t e = hipEventElapsedTime(&ms, spans[w].front().first, spans[w].front().second);
+                if (e == hipErrorNotReady) break;
+                if (e == hipSuccess) span_ms[w] += (double)ms;
+                spare.push_back(std::move(spans[w].front().first)); spare.push_back(std::move(spans[w].front().second));
+                spans[w].pop_front();
+            }
     }
-    double kernel_ms()                                            // waits for the stream; -1 on a HIP error
+    double kernel_ms(int which = LAUNCHES)                        // waits for the stream; -1 on a HIP error
     {
         if (hipSetDevice(device) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return -1.0;
         collect();
-        return span_ms;
+        return span_ms[which];
     }
 };
 
@@ -139,6 +246,16 @@ struct wgbsseg_patbeta {
     DevBuf meth, cov, outb, bad;
     ~wgbsseg_patbeta() { feed.drain(); }
 };
+
+// a staged chunk of n_bytes / gx tiles: k_pat_count over it
+template <class Stage>
+static int patbeta_chunk(wgbsseg_patbeta* p, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    return PatFeed::one_launch(p, n_bytes, gx, stage, err, errlen, [] { return hipSuccess; }, [&](unsigned gx, const char* dtext) {
+        hipLaunchKernelGGL(k_pat_count, dim3(gx), dim3(WG_BLOCK), 0, p->feed.st, dtext, n_bytes, p->start, p->end,
+                           p->meth.as<int32_t>(), p->cov.as<int32_t>(), p->bad.as<unsigned long long>(), p->feed.fed);
+    });
+}
 
 extern "C" {
 
@@ -165,10 +282,12 @@ void wgbsseg_patbeta_destroy(wgbsseg_patbeta* p) { delete p; }
 
 int wgbsseg_patbeta_feed(wgbsseg_patbeta* p, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    return PatFeed::one_launch("patbeta", p, text, n_bytes, err, errlen, [] { return hipSuccess; }, [&](unsigned gx, const char* dtext) {
-        hipLaunchKernelGGL(k_pat_count, dim3(gx), dim3(WG_BLOCK), 0, p->feed.st, dtext, n_bytes, p->start, p->end,
-                           p->meth.as<int32_t>(), p->cov.as<int32_t>(), p->bad.as<unsigned long long>(), p->feed.fed);
-    });
+    return PatFeed::feed_text("patbeta", p, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return patbeta_chunk(p, n, gx, stage, err, errlen); });
+}
+
+int wgbsseg_patbeta_feed_bgzf(wgbsseg_patbeta* p, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+{
+    return PatFeed::feed_bgzf("patbeta", p, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return patbeta_chunk(p, n, gx, stage, err, errlen); });
 }
 
 int wgbsseg_patbeta_finish(wgbsseg_patbeta* p, int32_t lbeta, void* out, char* err, size_t errlen)
@@ -176,12 +295,16 @@ int wgbsseg_patbeta_finish(wgbsseg_patbeta* p, int32_t lbeta, void* out, char* e
     if (!p || !out) { set_err(err, errlen, "bad arguments to patbeta_finish"); return WGBSSEG_E_ARG; }
     const hipStream_t st = p->feed.st;
     HIP_TRY(hipSetDevice(p->feed.device));
+    int rc = p->feed.flush_carry("patbeta", [&](int64_t n, int64_t gx, auto&& stage) { return patbeta_chunk(p, n, gx, stage, err, errlen); }, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     const int64_t n = p->end - p->start;
     const size_t ob = (size_t)n * (lbeta ? 4 : 2);
     HIP_TRY(p->outb.ensure(ob));
     unsigned long long bad = 0;
     HIP_TRY(hipMemcpyAsync(&bad, p->bad.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    rc = p->feed.inflate_refused(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     if (pat_refused(PatRefusal::bad_line, bad, "failed calculating beta:", err, errlen)) return WGBSSEG_E_ARG;
     hipLaunchKernelGGL(k_pat_trim, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, p->meth.as<int32_t>(), p->cov.as<int32_t>(), n,
                        (int)lbeta, p->outb.p);
@@ -196,6 +319,11 @@ double wgbsseg_patbeta_kernel_ms(wgbsseg_patbeta* p)
     return p ? p->feed.kernel_ms() : -1.0;
 }
 
+double wgbsseg_patbeta_inflate_ms(wgbsseg_patbeta* p)
+{
+    return p ? p->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
+}
+
 }  // extern "C"
 
 // `wgbstools homog` accumulator: (block, bin) read counts on one device; k_homog_count is timed.
@@ -207,6 +335,26 @@ struct wgbsseg_homog {
     unsigned long long chunks = 0;
     ~wgbsseg_homog() { feed.drain(); }
 };
+
+// a staged chunk of n_bytes / gx tiles: k_homog_count over it
+template <class Stage>
+static int homog_chunk(wgbsseg_homog* h, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
+    long long *in = nullptr, *out = nullptr;
+    return PatFeed::one_launch(h, n_bytes, gx, stage, err, errlen,
+        [&] {
+            out = h->prev.as<long long>() + (h->chunks & 1); in = h->prev.as<long long>() + ((h->chunks & 1) ^ 1);
+            return hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, h->feed.st);
+        },
+        [&](unsigned gx, const char* dtext) {
+            hipLaunchKernelGGL(k_homog_count, dim3(gx), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes,
+                               h->bstart.as<int32_t>(), h->bend.as<int32_t>(), h->bpmax.as<int32_t>(), h->n_blocks, h->last_end,
+                               h->range.as<float>(), h->n_bins, h->min_cpgs, h->inclusive, h->counts.as<int32_t>(),
+                               h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), in, out, h->feed.fed);
+            h->chunks += 1;                                       // (the slots swap for the next chunk)
+        });
+}
 
 extern "C" {
 
@@ -248,20 +396,12 @@ void wgbsseg_homog_destroy(wgbsseg_homog* h) { delete h; }
 
 int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
-    long long *in = nullptr, *out = nullptr;
-    return PatFeed::one_launch("homog", h, text, n_bytes, err, errlen,
-        [&] {
-            out = h->prev.as<long long>() + (h->chunks & 1); in = h->prev.as<long long>() + ((h->chunks & 1) ^ 1);
-            return hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, h->feed.st);
-        },
-        [&](unsigned gx, const char* dtext) {
-            hipLaunchKernelGGL(k_homog_count, dim3(gx), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes,
-                               h->bstart.as<int32_t>(), h->bend.as<int32_t>(), h->bpmax.as<int32_t>(), h->n_blocks, h->last_end,
-                               h->range.as<float>(), h->n_bins, h->min_cpgs, h->inclusive, h->counts.as<int32_t>(),
-                               h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), in, out, h->feed.fed);
-            h->chunks += 1;                                       // (the slots swap for the next chunk)
-        });
+    return PatFeed::feed_text("homog", h, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return homog_chunk(h, n, gx, stage, err, errlen); });
+}
+
+int wgbsseg_homog_feed_bgzf(wgbsseg_homog* h, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+{
+    return PatFeed::feed_bgzf("homog", h, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return homog_chunk(h, n, gx, stage, err, errlen); });
 }
 
 int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t errlen)
@@ -269,10 +409,14 @@ int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t er
     if (!h || !counts) { set_err(err, errlen, "bad arguments to homog_finish"); return WGBSSEG_E_ARG; }
     const hipStream_t st = h->feed.st;
     HIP_TRY(hipSetDevice(h->feed.device));
+    int rc = h->feed.flush_carry("homog", [&](int64_t n, int64_t gx, auto&& stage) { return homog_chunk(h, n, gx, stage, err, errlen); }, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     unsigned long long bad = 0, desc = 0;
     HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&desc, h->desc.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    rc = h->feed.inflate_refused(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     if (pat_refused(PatRefusal::bad_line, bad, "failed calculating homog:", err, errlen)) return WGBSSEG_E_ARG;
     if (pat_refused(PatRefusal::unsorted, desc, "failed calculating homog:", err, errlen)) return WGBSSEG_E_ARG;
     HIP_TRY(hipMemcpyAsync(counts, h->counts.p, (size_t)h->n_blocks * (size_t)h->n_bins * 4, hipMemcpyDeviceToHost, st));
@@ -283,6 +427,11 @@ int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t er
 double wgbsseg_homog_kernel_ms(wgbsseg_homog* h)
 {
     return h ? h->feed.kernel_ms() : -1.0;
+}
+
+double wgbsseg_homog_inflate_ms(wgbsseg_homog* h)
+{
+    return h ? h->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
 }
 
 int wgbsseg_debug_homog_bins(const float* range, int32_t n_bins, int32_t max_total, int8_t* out)
@@ -432,14 +581,15 @@ static int bim_drop(wgbsseg_bimodal* b, const wg_bim_state& s, char* err, size_t
     return WGBSSEG_OK;
 }
 
-// this chunk behind the table's reads: copy, count, scan, fill, order (s: the state before it, ub: the bounds the tables were reserved for)
-static int bim_parse_chunk(wgbsseg_bimodal* b, const wg_bim_state& s, const char* text, int64_t n_bytes, int64_t gx, const BimodalChunkBound& ub,
+// this chunk behind the table's reads: stage (the copy, either way), count, scan, fill, order (s: the state before it, ub: the bounds the tables were reserved for)
+template <class Stage>
+static int bim_parse_chunk(wgbsseg_bimodal* b, const wg_bim_state& s, Stage&& stage, int64_t n_bytes, int64_t gx, const BimodalChunkBound& ub,
                            char* err, size_t errlen)
 {
     PatFeed& f = b->feed;
     HIP_TRY(b->tile_cnt.ensure((size_t)gx * 8)); HIP_TRY(b->tile_base.ensure((size_t)gx * 16)); HIP_TRY(b->pos.ensure(ub.lines * 8));
     const char* dtext = nullptr;
-    const int rc = f.stage_chunk(text, n_bytes, &dtext, err, errlen);
+    const int rc = stage(&dtext);
     if (rc != WGBSSEG_OK) return rc;
     wgbsseg_bimodal::Table& T = b->tab[b->cur];
     HIP_TRY(f.span_begin());
@@ -456,6 +606,26 @@ static int bim_parse_chunk(wgbsseg_bimodal* b, const wg_bim_state& s, const char
     HIP_TRY(f.span_end());
     HIP_TRY(f.chunk_queued(n_bytes));
     return WGBSSEG_OK;
+}
+
+// a chunk of n_bytes / gx tiles that stage() puts on the device:
+// sync (the previous chunk is parsed and checked) -> reserve -> retire -> drop -> parse; every host decision is the plan's
+template <class Stage>
+static int bim_chunk(wgbsseg_bimodal* b, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    HIP_TRY(hipSetDevice(b->feed.device));
+    int rc = bim_sync_state(b, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (b->stop) { b->feed.fed += (unsigned long long)n_bytes; return WGBSSEG_OK; }     // finish() reports the error
+    const wg_bim_state s = *b->hs();
+    const BimodalChunkBound ub(n_bytes);
+    rc = bim_reserve(b, (size_t)s.R + ub.lines, (size_t)s.W + ub.words, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    rc = bim_retire(b, b->plan.retire_upto(b->pending, s.last_start), err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (s.R > 0) rc = bim_drop(b, s, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    return bim_parse_chunk(b, s, stage, n_bytes, gx, ub, err, errlen);
 }
 
 extern "C" {
@@ -493,31 +663,23 @@ int wgbsseg_bimodal_create(int device, const int64_t* start_cpg, const int64_t* 
 
 void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b) { delete b; }
 
-// sync (the previous chunk is parsed and checked) -> reserve -> retire -> drop -> parse; every host decision is the plan's
 int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    const int64_t gx = PatFeed::tiles("bimodal", b, text, n_bytes, err, errlen);
-    if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
-    HIP_TRY(hipSetDevice(b->feed.device));
-    int rc = bim_sync_state(b, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    if (b->stop) { b->feed.fed += (unsigned long long)n_bytes; return WGBSSEG_OK; }     // finish() reports the error
-    const wg_bim_state s = *b->hs();
-    const BimodalChunkBound ub(n_bytes);
-    rc = bim_reserve(b, (size_t)s.R + ub.lines, (size_t)s.W + ub.words, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    rc = bim_retire(b, b->plan.retire_upto(b->pending, s.last_start), err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    if (s.R > 0) rc = bim_drop(b, s, err, errlen);
-    if (rc != WGBSSEG_OK) return rc;
-    return bim_parse_chunk(b, s, text, n_bytes, gx, ub, err, errlen);
+    return PatFeed::feed_text("bimodal", b, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return bim_chunk(b, n, gx, stage, err, errlen); });
+}
+
+int wgbsseg_bimodal_feed_bgzf(wgbsseg_bimodal* b, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+{
+    return PatFeed::feed_bgzf("bimodal", b, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return bim_chunk(b, n, gx, stage, err, errlen); });
 }
 
 int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char* err, size_t errlen)
 {
     if (!b || !ll || !counts) { set_err(err, errlen, "bad arguments to bimodal_finish"); return WGBSSEG_E_ARG; }
     HIP_TRY(hipSetDevice(b->feed.device));
-    int rc = bim_sync_state(b, err, errlen);
+    int rc = b->feed.flush_carry("bimodal", [&](int64_t n, int64_t gx, auto&& stage) { return bim_chunk(b, n, gx, stage, err, errlen); }, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    rc = bim_sync_state(b, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     if (!b->stop) {
         rc = bim_retire(b, b->plan.n_blocks, err, errlen);        // every read has been seen
@@ -525,6 +687,8 @@ int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char
         rc = bim_sync_state(b, err, errlen);
         if (rc != WGBSSEG_OK) return rc;
     }
+    rc = b->feed.inflate_refused(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
     const wg_bim_state* s = b->hs();
     if (pat_refused(PatRefusal::bad_line, s->bad, "test_bimodal:", err, errlen)) return WGBSSEG_E_ARG;
     if (s->neg != ~0ULL) {
@@ -544,6 +708,49 @@ int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char
 double wgbsseg_bimodal_kernel_ms(wgbsseg_bimodal* b)
 {
     return b ? b->feed.kernel_ms() : -1.0;
+}
+
+double wgbsseg_bimodal_inflate_ms(wgbsseg_bimodal* b)
+{
+    return b ? b->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
+}
+
+// BGZF bytes -> the text of their complete members, inflated by k_bgzf_inflate (no line rule: every member goes to the device)
+int wgbsseg_bgzf_inflate(int device, const void* bytes, int64_t n_bytes, void* out, int64_t out_cap, int64_t* out_len, int64_t* consumed, char* err, size_t errlen)
+{
+    if (!out_len || !consumed || n_bytes < 0 || out_cap < 0 || (n_bytes && !bytes) || (out_cap && !out)) { set_err(err, errlen, "bad arguments to bgzf_inflate"); return WGBSSEG_E_ARG; }
+    *out_len = *consumed = 0;
+    int rc = check_device(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    std::vector<wg_bgzf_member> members;
+    std::string msg;
+    int64_t used = 0;
+    rc = bgzf_walk(static_cast<const uint8_t*>(bytes), n_bytes, 0, members, &used, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    const int64_t n_text = members.empty() ? 0 : (int64_t)(members.back().out_off + members.back().isize);
+    if (n_text > out_cap) { set_err(err, errlen, "bgzf_inflate: %lld bytes of text, room for %lld", (long long)n_text, (long long)out_cap); return WGBSSEG_E_CAPACITY; }
+    *consumed = used;
+    if (members.empty()) return WGBSSEG_OK;
+    HIP_TRY(hipSetDevice(device));
+    const size_t tb = members.size() * sizeof(wg_bgzf_member);
+    DevBuf comp, text, bad;
+    HIP_TRY(comp.ensure(tb + (size_t)used)); HIP_TRY(text.ensure((size_t)n_text + 1)); HIP_TRY(bad.ensure(8));
+    HIP_TRY(hipMemcpy(comp.p, members.data(), tb, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(comp.as<uint8_t>() + tb, bytes, (size_t)used, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(bad.p, 0xff, 8));
+    hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)((members.size() + WG_INF_WAVES - 1) / WG_INF_WAVES)), dim3(64 * WG_INF_WAVES), 0, 0,
+                       comp.as<uint8_t>() + tb, comp.as<wg_bgzf_member>(), (int64_t)members.size(), text.as<uint8_t>(), bad.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    unsigned long long first_bad = ~0ULL;
+    HIP_TRY(hipMemcpy(&first_bad, bad.p, 8, hipMemcpyDeviceToHost));
+    if (n_text) HIP_TRY(hipMemcpy(out, text.p, (size_t)n_text, hipMemcpyDeviceToHost));
+    *out_len = n_text;
+    if (first_bad != ~0ULL) {
+        (void)wg_inflate_refuse(msg, first_bad >> 8, (int)(first_bad & 0xff));
+        set_err(err, errlen, "%s", msg.c_str());
+        return WGBSSEG_E_ARG;
+    }
+    return WGBSSEG_OK;
 }
 
 }  // extern "C"

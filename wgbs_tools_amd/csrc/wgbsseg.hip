@@ -40,6 +40,8 @@
 #include "pat_kernels.h"
 #include "homog_kernels.h"
 #include "bimodal_kernels.h"
+#include "inflate_plan.h"
+#include "inflate_kernels.h"
 #include "stats_kernels.h"
 #include "pair_kernels.h"
 #include "bed_kernels.h"

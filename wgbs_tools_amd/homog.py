@@ -46,7 +46,7 @@ import numpy as np
 from .beta_to_blocks import load_blocks_file
 from .convert import delete_or_skip
 from .genome import IllegalArgumentError
-from .pat2beta import feed_pat, splitextgz
+from .pat2beta import add_inflate_option, feed_pat, splitextgz
 from .cliutil import default_threads
 
 
@@ -148,7 +148,7 @@ def count_blocks(pat, blocks, edges, args, timings=None):
     order = np.lexsort((blocks.endCpG, blocks.startCpG))
     t = timings if timings is not None else {}
     with _lib.Homog(blocks.startCpG[order], blocks.endCpG[order], edges, args.rlen, args.inclusive, device=getattr(args, 'device', 0)) as h:
-        feed_pat(h, pat, t)
+        feed_pat(h, pat, t, inflate=getattr(args, 'inflate', 'host'))
         t0 = time.perf_counter()
         try:
             counts = h.finish()
@@ -293,6 +293,7 @@ def parse_args(argv=None):
     parser.add_argument('--debug', '-d', action='store_true')
     parser.add_argument('-@', '--threads', type=int, default=default_threads(), help='Threads compressing the output [all CPUs]')
     parser.add_argument('--device', type=int, default=0, help='HIP device index [0]')
+    add_inflate_option(parser)
     return parser.parse_args(argv)
 
 

@@ -10,9 +10,12 @@ formats:
             stored as (trunc(meth / cov * M), M) (utils_wgbs.py:277-290).
 
 The reference pipes `gunzip -c x.pat.gz` into its stdin2beta binary; here the text is decompressed on the host in chunks and
-counted on the GPU (wgbsseg_patbeta_*, include/wgbsseg.h) while the next chunk is being decompressed.  No CPU fallback.
+counted on the GPU (wgbsseg_patbeta_*, include/wgbsseg.h) while the next chunk is being decompressed.  With `--inflate device` the
+bytes of a BGZF file go to the GPU as they lie in the file and its members are inflated there (wgbsseg_patbeta_feed_bgzf).  No CPU
+fallback.
 """
 import argparse
+import contextlib
 import gzip
 import os
 import os.path as op
@@ -142,8 +145,92 @@ def pat_chunks(pat_path, chunk_bytes=CHUNK_BYTES):
         yield rest if rest.endswith(b'\n') else rest + b'\n'
 
 
-def feed_pat(engine, pat_path, timings):
-    """every chunk of a pat file (pat_chunks) to engine.feed; timings['inflate_s'] / ['feed_s']: the time spent in each"""
+def bgzf_members(path, read_bytes=64 << 20):
+    """The bytes of a BGZF file as they lie in it, in pieces of read_bytes, for engine.feed_bgzf (which finds the members itself: a
+    piece may end anywhere).  Yields nothing and returns False when the file does not begin with a BGZF member."""
+    with open(path, 'rb') as f:
+        buf = f.read(read_bytes)
+        if _bgzf_block_size(buf, 0) is None:
+            return False
+        while buf:
+            yield buf
+            buf = f.read(read_bytes)
+    return True
+
+
+def add_inflate_option(parser):
+    parser.add_argument('--inflate', choices=('host', 'device'), default='host',
+                        help='where a BGZF pat.gz is inflated: on the host (zlib on a pool of threads) or on the GPU [host]')
+
+
+def _feed_bgzf(engine, pat_path, timings):
+    """every piece of a BGZF file (bgzf_members) to engine.feed_bgzf, the bytes it did not take in front of the next piece; False (nothing
+    fed) when the file is not BGZF"""
+    t_read = t_feed = 0.0
+    gen = bgzf_members(pat_path)
+    tail, offset, bgzf = b'', 0, None
+    while True:
+        t0 = time.perf_counter()
+        try:
+            piece = next(gen)
+        except StopIteration as e:
+            bgzf = e.value
+            break
+        finally:
+            t1 = time.perf_counter()
+            t_read += t1 - t0
+        buf = tail + piece if tail else piece
+        used = engine.feed_bgzf(buf)
+        offset += used
+        tail = buf[used:]
+        if len(tail) > (1 << 20):                                # a BGZF member is at most 64 KB
+            raise IllegalArgumentError(f'Invalid gzip data in {pat_path}: no BGZF member at file offset {offset}')
+        t_feed += time.perf_counter() - t1
+    if not bgzf:
+        return False
+    if tail:
+        raise IllegalArgumentError(f'Invalid gzip data in {pat_path}: truncated (the BGZF member at file offset {offset} is incomplete)')
+    timings['inflate_s'], timings['feed_s'] = t_read, t_feed
+    return True
+
+
+_default_inflate = 'host'
+
+
+@contextlib.contextmanager
+def default_inflate(mode):
+    """Within the block, feed_pat calls that do not say where to inflate use `mode`.  For a command whose own code does not pass the
+    choice on: `wgbstools test_bimodal --inflate device` (wgbs_tools.py takes the option and runs the command inside this block)."""
+    global _default_inflate
+    if mode not in ('host', 'device'):
+        raise IllegalArgumentError(f"inflate must be 'host' or 'device' (got {mode!r})")
+    before, _default_inflate = _default_inflate, mode
+    try:
+        yield
+    finally:
+        _default_inflate = before
+
+
+def feed_pat(engine, pat_path, timings, inflate=None):
+    """every chunk of a pat file to the engine; timings['inflate_s'] / ['feed_s']: the time spent in each.  inflate=None: 'host', or what
+    an enclosing default_inflate() block says.  inflate='host': the text
+    of pat_chunks to engine.feed.  inflate='device': the bytes of a BGZF file to engine.feed_bgzf (inflate_s is then the time spent
+    reading the file, timings['inflate_ms'] the device time of the inflate kernel); a file that is not BGZF takes the host path,
+    and one line on stderr says so."""
+    if inflate is None:
+        inflate = _default_inflate
+    if inflate not in ('host', 'device'):
+        raise IllegalArgumentError(f"inflate must be 'host' or 'device' (got {inflate!r})")
+    if inflate == 'device':
+        try:
+            done = pat_path.endswith('.gz') and _feed_bgzf(engine, pat_path, timings)
+        except _SegmentorError() as e:
+            raise IllegalArgumentError(f'{pat_path}: {e.msg}')
+        if done:
+            timings['inflate_ms'] = engine.inflate_ms()
+            return
+        import sys
+        print(f'[wgbs_tools_amd] {pat_path} is not BGZF: --inflate device does not apply, inflating on the host', file=sys.stderr)
     t_inflate = t_feed = 0.0
     it = iter(pat_chunks(pat_path))
     while True:
@@ -158,6 +245,11 @@ def feed_pat(engine, pat_path, timings):
     timings['inflate_s'], timings['feed_s'] = t_inflate, t_feed
 
 
+def _SegmentorError():
+    from . import _lib
+    return _lib.SegmentorError
+
+
 def pat2beta(pat_path, out_dir, args, force=True):
     """pat2beta.py:17-44 for one file; returns the path written (None when skipped)."""
     require_file(pat_path)
@@ -170,7 +262,7 @@ def pat2beta(pat_path, out_dir, args, force=True):
     from . import _lib
     nr_sites = GenomeRefPaths(args.genome).get_nr_sites()
     with _lib.PatBeta(1, nr_sites + 1, device=getattr(args, 'device', 0)) as pb:
-        feed_pat(pb, pat_path, {})
+        feed_pat(pb, pat_path, {}, inflate=getattr(args, 'inflate', 'host'))
         try:
             rows = pb.finish(lbeta=args.lbeta)
         except _lib.SegmentorError as e:
@@ -188,6 +280,7 @@ def parse_args(argv=None):
     parser.add_argument('--genome', help='Genome reference name.')
     add_threads_option(parser)
     parser.add_argument('--device', type=int, default=0, help='HIP device index [0]')
+    add_inflate_option(parser)
     return parser.parse_args(argv)
 
 

@@ -32,6 +32,27 @@ def print_help():
     return 1
 
 
+def _take_inflate(args):
+    """`--inflate {host,device}` taken out of a command's arguments -> (the other arguments, the choice or None).  For test_bimodal,
+    whose module hands no such choice to the feed: main() below runs it inside pat2beta.default_inflate(choice)."""
+    rest, choice, k = [], None, 0
+    while k < len(args):
+        a = args[k]
+        if a == '--inflate':
+            if k + 1 >= len(args):
+                raise IllegalArgumentError('--inflate: expected host or device')
+            choice, k = args[k + 1], k + 2
+            continue
+        if a.startswith('--inflate='):
+            choice = a[len('--inflate='):]
+        else:
+            rest.append(a)
+        k += 1
+    if choice is not None and choice not in ('host', 'device'):
+        raise IllegalArgumentError(f"--inflate: invalid choice {choice!r} (choose from 'host', 'device')")
+    return rest, choice
+
+
 def main(argv=None):
     argv = list(sys.argv if argv is None else argv)
     if len(argv) < 2 or argv[1] in ('-h', '--help'):
@@ -48,7 +69,13 @@ def main(argv=None):
         return print_help()
     try:
         import importlib
-        importlib.import_module('.' + cmd, __package__).main(argv[2:])
+        args, inflate = _take_inflate(argv[2:]) if cmd == 'test_bimodal' else (argv[2:], None)
+        if inflate is not None:                # where the BGZF pat.gz is inflated: the other pat commands have the option themselves
+            from .pat2beta import default_inflate
+            with default_inflate(inflate):
+                importlib.import_module('.' + cmd, __package__).main(args)
+            return 0
+        importlib.import_module('.' + cmd, __package__).main(args)
         return 0
     except IllegalArgumentError as e:          # wgbs_tools.py:77-79
         eprint(f'Invalid input argument\n{e}')
