@@ -98,7 +98,10 @@ int wgbsseg_set_lbetas_host(wgbsseg_ctx* ctx, const uint16_t* const* samples, in
 int wgbsseg_set_betas_device(wgbsseg_ctx* ctx, const void* base, int64_t n_samples, int64_t pitch_bytes,
                              int64_t n_sites, char* err, size_t errlen);
 
-/* loci[i] = bp position of CpG i+1 (column 2 of CpG.bed.gz; what `tabix | cut -f2` feeds load_dists, segmentor.cpp:36-48). */
+/* loci[i] = bp position of CpG i+1 (column 2 of CpG.bed.gz; what `tabix | cut -f2` feeds load_dists, segmentor.cpp:36-48).
+ * _device: borrows a device array of n_sites uint32; `loci` must be a multiple of 4 bytes (any such address: no 16-byte
+ *          alignment, no padding behind the last entry is needed; nothing outside [loci, loci + n_sites) is read), else
+ *          WGBSSEG_E_ARG and the context keeps the loci it had. */
 int wgbsseg_set_loci_host(wgbsseg_ctx* ctx, const uint32_t* loci, int64_t n_sites, char* err, size_t errlen);
 int wgbsseg_set_loci_device(wgbsseg_ctx* ctx, const void* loci, int64_t n_sites, char* err, size_t errlen);
 

@@ -401,6 +401,11 @@ class Segmenter:
         loci = np.ascontiguousarray(loci, dtype=np.uint32)
         _check(self._L.wgbsseg_set_loci_host(self._h, loci.ctypes.data, loci.size, self._err, ERRLEN), self._err)
 
+    def set_loci_device(self, data_ptr, n_sites, keepalive=None):
+        """Borrow a device array of n_sites uint32 loci (e.g. a torch int32 tensor's data_ptr(), any multiple of 4 bytes)."""
+        _check(self._L.wgbsseg_set_loci_device(self._h, C.c_void_p(int(data_ptr)), int(n_sites), self._err, ERRLEN), self._err)
+        self._keep_loci = keepalive
+
     def set_site_base(self, base):
         """absolute 0-based index of resident site 0: error messages then name absolute sites"""
         self._L.wgbsseg_set_site_base(self._h, int(base))

@@ -567,6 +567,9 @@ int wgbsseg_set_loci_host(wgbsseg_ctx* c, const uint32_t* loci, int64_t n_sites,
 int wgbsseg_set_loci_device(wgbsseg_ctx* c, const void* loci, int64_t n_sites, char* err, size_t errlen)
 {
     if (!c || !loci || n_sites < 1) { set_err(err, errlen, "bad arguments to set_loci_device"); return WGBSSEG_E_ARG; }
+    // every kernel reads the loci as uint32; k_window's 16-byte loads start at the 16-byte boundary at or below a locus, which it works
+    // out from the address itself, and never leave [loci, loci + n_sites): whole entries is all the alignment they need
+    if ((uintptr_t)loci & 3) { set_err(err, errlen, "device loci must be a multiple of 4 bytes"); return WGBSSEG_E_ARG; }
     c->loci = reinterpret_cast<const uint32_t*>(loci);
     c->n_loci = n_sites;
     c->last_valid = false;
