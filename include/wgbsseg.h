@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 290            /* 0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 300            /* 0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -639,6 +639,31 @@ double wgbsseg_homog_inflate_ms(wgbsseg_homog* h);
 double wgbsseg_bimodal_inflate_ms(wgbsseg_bimodal* b);
 int wgbsseg_bgzf_inflate(int device, const void* bytes, int64_t n_bytes, void* out, int64_t out_cap, int64_t* out_len, int64_t* consumed,
                          char* err, size_t errlen);
+
+/*
+ * pat -> the histogram of the reads' lengths in CpGs, weighted by the reads' counts (`wgbstools frag_len`: frag_len.py:21-46 pipes
+ * `tabix` or the reference's cview into an awk program).  create(): max_frag (the reference's -m; 1 .. 2^20), and the blocks that
+ * select reads: n_blocks == 0 selects every read; otherwise [start_cpg[j], end_cpg[j]) in the order `sort -k1,1n` gives the text
+ * "startCpG\tendCpG" (startCpG ascending, refused otherwise; equal starts in the caller's order; startCpG >= 1, endCpG > startCpG,
+ * endCpG < 2^31) — one block for a region or a site range.  groups: the cap on the workgroups of a launch (-1: the default; a small
+ * value makes every workgroup walk many tiles: a test hook).  feed() / feed_bgzf(): as for wgbsseg_homog (asynchronous, the text is
+ * copied; text or BGZF bytes, not both).  A selected read `chr, s, pattern, count` adds count to hist[min(len(pattern), max_frag) - 1].
+ * The selection is cview's without --strict on reads sorted by start (src/cview/cview.cpp:87-128): a read is dropped when
+ * s >= endCpG of the LAST block given; else, with cur the first block whose endCpG > s, it is selected — whole — iff
+ * s + len - 1 >= startCpG[cur].  finish(): hist[max_frag] (int64: exact sums); it first feeds a last line that has no newline, then
+ * returns WGBSSEG_E_ARG for a BGZF member refused on the device, else naming the byte offset of the first malformed line (fewer than
+ * four fields, a site / count that is not a number, an EMPTY pattern), else — with blocks only — of the first read that starts before
+ * the read before it.  kernel_ms / inflate_ms: device time (HIP events) of the histogram / inflate launches so far; wait for them.
+ */
+typedef struct wgbsseg_fraglen wgbsseg_fraglen;
+int wgbsseg_fraglen_create(int device, int32_t max_frag, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, int32_t groups,
+                           wgbsseg_fraglen** out, char* err, size_t errlen);
+int wgbsseg_fraglen_feed(wgbsseg_fraglen* h, const char* text, int64_t n_bytes, char* err, size_t errlen);
+int wgbsseg_fraglen_feed_bgzf(wgbsseg_fraglen* h, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen);
+int wgbsseg_fraglen_finish(wgbsseg_fraglen* h, int64_t* hist, char* err, size_t errlen);
+void wgbsseg_fraglen_destroy(wgbsseg_fraglen* h);
+double wgbsseg_fraglen_kernel_ms(wgbsseg_fraglen* h);
+double wgbsseg_fraglen_inflate_ms(wgbsseg_fraglen* h);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

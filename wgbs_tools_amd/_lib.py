@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 290          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 300          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -45,7 +45,9 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_beta2bed', 'wgbsseg_beta2bed_pass_ms', 'wgbsseg_beta2bed_limits',
            'wgbsseg_site_counts', 'wgbsseg_site_table', 'wgbsseg_site_table_pass_ms', 'wgbsseg_site_table_limits',
            'wgbsseg_patbeta_feed_bgzf', 'wgbsseg_homog_feed_bgzf', 'wgbsseg_bimodal_feed_bgzf',
-           'wgbsseg_patbeta_inflate_ms', 'wgbsseg_homog_inflate_ms', 'wgbsseg_bimodal_inflate_ms', 'wgbsseg_bgzf_inflate']
+           'wgbsseg_patbeta_inflate_ms', 'wgbsseg_homog_inflate_ms', 'wgbsseg_bimodal_inflate_ms', 'wgbsseg_bgzf_inflate',
+           'wgbsseg_fraglen_create', 'wgbsseg_fraglen_feed', 'wgbsseg_fraglen_feed_bgzf', 'wgbsseg_fraglen_finish', 'wgbsseg_fraglen_destroy',
+           'wgbsseg_fraglen_kernel_ms', 'wgbsseg_fraglen_inflate_ms']
 
 
 class NativeLibraryError(RuntimeError):
@@ -283,7 +285,17 @@ def load():
     L.wgbsseg_bimodal_destroy.argtypes = [vp]
     L.wgbsseg_bimodal_kernel_ms.restype = C.c_double
     L.wgbsseg_bimodal_kernel_ms.argtypes = [vp]
-    for eng in ('patbeta', 'homog', 'bimodal'):
+    L.wgbsseg_fraglen_create.restype = i32
+    L.wgbsseg_fraglen_create.argtypes = [i32, i32, vp, vp, i64, i32, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.wgbsseg_fraglen_feed.restype = i32
+    L.wgbsseg_fraglen_feed.argtypes = [vp, C.c_char_p, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_fraglen_finish.restype = i32
+    L.wgbsseg_fraglen_finish.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_fraglen_destroy.restype = None
+    L.wgbsseg_fraglen_destroy.argtypes = [vp]
+    L.wgbsseg_fraglen_kernel_ms.restype = C.c_double
+    L.wgbsseg_fraglen_kernel_ms.argtypes = [vp]
+    for eng in ('patbeta', 'homog', 'bimodal', 'fraglen'):
         f = getattr(L, 'wgbsseg_%s_feed_bgzf' % eng)
         f.restype = i32
         f.argtypes = [vp, C.c_char_p, i64, C.POINTER(i64), C.c_char_p, C.c_size_t]
@@ -755,6 +767,28 @@ class Homog(_PatFeed):
         return out
 
 
+class FragLen(_PatFeed):
+    """wgbsseg_fraglen: pat text -> int64 hist[max_frag], the counts of the selected reads by min(length in CpGs, max_frag), on one GPU.
+    starts / ends: the selecting blocks in cview's order (startCpG ascending; see frag_len.cview_order), none: every read.
+    groups: the cap on the workgroups of a launch (-1: the library's; a small value is the tests' hook for the tile loop)."""
+    _abi = 'fraglen'
+
+    def __init__(self, max_frag=30, starts=None, ends=None, device=0, groups=-1):
+        super().__init__()
+        s = np.ascontiguousarray([] if starts is None else starts, dtype=np.int64)
+        e = np.ascontiguousarray([] if ends is None else ends, dtype=np.int64)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError('starts / ends: one value per block')
+        self.max_frag = int(max_frag)
+        self._call('create', int(device), self.max_frag, s.ctypes.data if s.size else None, e.ctypes.data if e.size else None, s.size,
+                   int(groups), C.byref(self._h))
+
+    def finish(self):
+        out = np.empty(self.max_frag, dtype=np.int64)
+        self._call('finish', self._h, out.ctypes.data)
+        return out
+
+
 class Bimodal(_PatFeed):
     """wgbsseg_bimodal: pat text -> per block [starts, ends) (any order) the two-allele EM test's raw numbers on one GPU.
     finish() -> (float64 [n][3]: ll0, ll_em, sum of n_per_col; int64 [n][3]: columns, rows, EM iterations)."""
@@ -1181,6 +1215,10 @@ class ParsedBlocks:
             for c in range(count):
                 cols[c].append(tok[first + c] if len(tok) > first + c else '')
         return cols
+
+    def cpg_text(self, idx=None):
+        """-> (startCpG, endCpG) lists of str: the fourth and fifth fields of every row (of the rows idx), as the file has them"""
+        return tuple(self.fields(idx, 3, 2))
 
     def _ptrs(self):
         self.line_off = np.ascontiguousarray(self.line_off, dtype=np.int64)

@@ -1,9 +1,9 @@
-// pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_bimodal), the feed they share
+// pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_fraglen, wgbsseg_bimodal), the feed they share
 // and their extern "C" entry points.  Part of wgbsseg.hip, which includes it once set_err, HIP_TRY, check_device and the owners are
-// in scope; what an engine decides on the host is in homog_plan.h and bimodal_plan.h, this file stages, launches and fetches.
+// in scope; what an engine decides on the host is in homog_plan.h, frag_plan.h and bimodal_plan.h, this file stages, launches and fetches.
 #pragma once
 
-// The pat-text feed of an engine (wgbsseg_patbeta / _homog / _bimodal): one device and stream; text chunks through two page-locked
+// The pat-text feed of an engine (wgbsseg_patbeta / _homog / _fraglen / _bimodal): one device and stream; text chunks through two page-locked
 // staging buffers and two device buffers, so that the caller's decompression of chunk k+1 overlaps the copy and the kernels of
 // chunk k; the input offset of the next chunk; and the device time of the launches the engine brackets with span_begin / span_end.
 // There are two ways to fill text[k]: stage_chunk copies text the caller inflated; stage_bgzf copies BGZF bytes as they lie in the file
@@ -466,6 +466,118 @@ int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t co
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, d_out.p, 6 * sizeof(uint64_t) * (size_t)count, hipMemcpyDeviceToHost));
     return WGBSSEG_OK;
+}
+
+}  // extern "C"
+
+// `wgbstools frag_len` accumulator: the histogram of the selected reads' lengths on one device; k_frag_hist is timed.
+struct wgbsseg_fraglen {
+    PatFeed feed;
+    FragPlan plan;
+    DevBuf bstart, bpmax, hist, bad, desc, prev;
+    unsigned long long chunks = 0;
+    ~wgbsseg_fraglen() { feed.drain(); }
+};
+
+// a staged chunk of n_bytes / gx tiles: k_frag_hist over it, min(gx, plan.groups) workgroups walking the tiles
+template <class Stage>
+static int fraglen_chunk(wgbsseg_fraglen* h, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
+    long long *in = nullptr, *out = nullptr;
+    return PatFeed::one_launch(h, n_bytes, gx, stage, err, errlen,
+        [&] {
+            out = h->prev.as<long long>() + (h->chunks & 1); in = h->prev.as<long long>() + ((h->chunks & 1) ^ 1);
+            return hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, h->feed.st);
+        },
+        [&](unsigned gx, const char* dtext) {
+            const unsigned grid = std::min<unsigned>(gx, (unsigned)h->plan.groups);
+            hipLaunchKernelGGL(k_frag_hist, dim3(grid), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes, (int64_t)gx,
+                               h->bstart.as<int32_t>(), h->bpmax.as<int32_t>(), h->plan.n_blocks, h->plan.end_last, (int)h->plan.max_frag,
+                               h->hist.as<unsigned long long>(), h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), in, out, h->feed.fed);
+            h->chunks += 1;                                       // (the slots swap for the next chunk)
+        });
+}
+
+extern "C" {
+
+// plan (frag_plan.h) -> the two tables on the device, the histogram and the edges cleared
+int wgbsseg_fraglen_create(int device, int32_t max_frag, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, int32_t groups,
+                           wgbsseg_fraglen** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    FragPlan plan;
+    std::string msg;
+    int rc = plan_frag(start_cpg, end_cpg, n_blocks, max_frag, plan, msg);
+    if (rc == WGBSSEG_OK) rc = plan_frag_groups(groups, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    std::unique_ptr<wgbsseg_fraglen> h(new (std::nothrow) wgbsseg_fraglen());      // (a failing call below frees what has been made)
+    if (!h) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    rc = h->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    h->plan = std::move(plan);
+    const hipStream_t st = h->feed.st;
+    const size_t nb4 = std::max<size_t>((size_t)n_blocks, 1) * 4, hb = (size_t)max_frag * 8;
+    HIP_TRY(h->bstart.ensure(nb4)); HIP_TRY(h->bpmax.ensure(nb4)); HIP_TRY(h->hist.ensure(hb));
+    HIP_TRY(h->bad.ensure(8)); HIP_TRY(h->desc.ensure(8)); HIP_TRY(h->prev.ensure(16));
+    if (n_blocks) {
+        HIP_TRY(hipMemcpy(h->bstart.p, h->plan.start.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->bpmax.p, h->plan.pmax.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice));
+    }
+    const long long none[2] = {WG_PAT_NO_SITE, WG_PAT_NO_SITE};
+    HIP_TRY(hipMemcpy(h->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(h->hist.p, 0, hb, st));
+    HIP_TRY(hipMemsetAsync(h->bad.p, 0xff, 8, st));
+    HIP_TRY(hipMemsetAsync(h->desc.p, 0xff, 8, st));
+    *out = h.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_fraglen_destroy(wgbsseg_fraglen* h) { delete h; }
+
+int wgbsseg_fraglen_feed(wgbsseg_fraglen* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    return PatFeed::feed_text("fraglen", h, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return fraglen_chunk(h, n, gx, stage, err, errlen); });
+}
+
+int wgbsseg_fraglen_feed_bgzf(wgbsseg_fraglen* h, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+{
+    return PatFeed::feed_bgzf("fraglen", h, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return fraglen_chunk(h, n, gx, stage, err, errlen); });
+}
+
+// the carry, then a refused BGZF member before a malformed line before a descending read, then the histogram
+int wgbsseg_fraglen_finish(wgbsseg_fraglen* h, int64_t* hist, char* err, size_t errlen)
+{
+    if (!h || !hist) { set_err(err, errlen, "bad arguments to fraglen_finish"); return WGBSSEG_E_ARG; }
+    const hipStream_t st = h->feed.st;
+    HIP_TRY(hipSetDevice(h->feed.device));
+    int rc = h->feed.flush_carry("fraglen", [&](int64_t n, int64_t gx, auto&& stage) { return fraglen_chunk(h, n, gx, stage, err, errlen); }, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    unsigned long long bad = 0, desc = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&desc, h->desc.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    rc = h->feed.inflate_refused(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (bad != ~0ULL) {
+        set_err(err, errlen, "failed calculating frag_len: invalid line at byte offset %llu of the input (too few columns, a site / count that is not a number, or an empty pattern)", bad);
+        return WGBSSEG_E_ARG;
+    }
+    if (pat_refused(PatRefusal::unsorted, desc, "failed calculating frag_len:", err, errlen)) return WGBSSEG_E_ARG;
+    HIP_TRY(hipMemcpyAsync(hist, h->hist.p, (size_t)h->plan.max_frag * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_fraglen_kernel_ms(wgbsseg_fraglen* h)
+{
+    return h ? h->feed.kernel_ms() : -1.0;
+}
+
+double wgbsseg_fraglen_inflate_ms(wgbsseg_fraglen* h)
+{
+    return h ? h->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // pat_kernels.h — the pat text format on gfx950: the staging of a tile of pat text in LDS, its line finding and the parsing of a
-// line, shared by every kernel that reads a pat file (k_pat_count here, k_homog_count in homog_kernels.h, k_bim_tile_count /
+// line, shared by every kernel that reads a pat file (k_pat_count here, k_homog_count in homog_kernels.h, k_frag_hist in frag_kernels.h, k_bim_tile_count /
 // k_bim_fill in bimodal_kernels.h), and the pat -> beta kernels k_pat_count / k_pat_trim.  Includes block_kernels.h for the
 // wg_block_sum_store that k_pat_trim uses (and, through it, seg_kernels.h for WG_BLOCK and wg_wave_incl_scan_dpp_u32).
 #pragma once
@@ -133,6 +133,33 @@ __device__ __forceinline__ bool wg_pat_parse_line(const PatText& T, int64_t p, i
         ok = i < n && T.at(i) != '\n' && wg_parse_int(T, i, n, count);   // field 4: how many reads (an empty one: stoi throws)
     }
     return ok;
+}
+
+// The two ends of the sortedness check of a kernel that walks a chunk tile by tile (k_frag_hist in frag_kernels.h; k_homog_count has
+// the same two steps written out in its body).  WG_PAT_NO_SITE: no read (none yet, or a malformed line: nothing to compare with).
+#define WG_PAT_NO_SITE ((long long)INT64_MIN)
+
+// The start of the read before the first line of the tile at byte `base`: back over empty lines to the line that holds byte base - 1,
+// parsed from global memory; *prev_in (the last read of the chunks before) when the tile's first line is the chunk's first.  One thread.
+__device__ __forceinline__ long long wg_pat_site_before(const char* __restrict__ text, int64_t n, int64_t base, const long long* prev_in)
+{
+    int64_t i = base - 1;
+    while (i >= 0 && text[i] == '\n') i--;
+    if (i < 0) return *prev_in;
+    while (i > 0 && text[i - 1] != '\n') i--;
+    const PatText G = {text, text, INT64_MIN / 4, n};               // (base far below: every byte from g)
+    int64_t site = 0, ps = 0, plen = 0, count = 0;
+    return wg_pat_parse_line(G, i, n, site, ps, plen, count) ? (long long)site : WG_PAT_NO_SITE;
+}
+
+// Is the line whose pattern is [ps, ps + plen) the chunk's last read (only newlines behind its end)?  Its start is then what the next
+// chunk's first read is checked against (prev_out).
+__device__ __forceinline__ bool wg_pat_is_last_read(const PatText& T, int64_t ps, int64_t plen, int64_t n)
+{
+    int64_t i = ps + plen;
+    while (i < n && T.at(i) != '\n') i++;
+    while (i < n && T.at(i) == '\n') i++;
+    return i == n;
 }
 
 __global__ __launch_bounds__(WG_BLOCK) void k_pat_count(const char* __restrict__ text, int64_t n, int64_t start, int64_t end,

@@ -5,8 +5,8 @@ indexes, what feeds `segment -L`), `pat2beta` (the producer of the beta files), 
 reads' U / X / M counts over those blocks), `test_bimodal` (the per-block two-allele test over the same reads),
 `beta_cov` / `beta_stats` (the per-sample coverage and methylation summary read before choosing what goes into `segment`),
 `compare_betas` (the 2-D histogram of every pair of those files: which samples agree), `beta2bed` (a file's sites as BED
-text, formatted on the device) and `beta_to_450k` (the files' values at the Illumina 450K / EPIC probes as one CSV table, gathered
-and formatted on the device);
+text, formatted on the device), `beta_to_450k` (the files' values at the Illumina 450K / EPIC probes as one CSV table, gathered
+and formatted on the device) and `frag_len` (the histogram of a pat file's read lengths in CpGs: what `homog -l` is chosen from);
 every other reference subcommand is out of scope and says so."""
 import sys
 
@@ -14,12 +14,12 @@ from .genome import IllegalArgumentError, eprint
 
 VERSION = '0.2.0-mi355x'
 COMMANDS = ['segment', 'convert', 'pat2beta', 'beta_to_blocks', 'beta_to_table', 'find_markers', 'homog', 'test_bimodal',
-            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k']
+            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k', 'frag_len']
 # reference command list (wgbs_tools.py:11-48), for the "not in this build" message
 REFERENCE_ONLY = ['view', 'merge', 'cview', 'index',
                   'beta2bw', 'bam2pat', 'mbias', 'init_genome', 'set_default_ref', 'vis', 'pat_fig',
                   'dmb', 'mix_pat', 'bed2beta',
-                  'split_by_allele', 'split_by_meth', 'frag_len', 'add_cpg_counts']
+                  'split_by_allele', 'split_by_meth', 'add_cpg_counts']
 
 
 def print_help():
