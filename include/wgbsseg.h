@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 300            /* 0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 310            /* 0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -398,6 +398,30 @@ int wgbsseg_beta2bed(wgbsseg_ctx* ctx, int32_t sample, int64_t start0, int64_t e
                      const wgbsseg_bed_opts* opts, int fd, int64_t* lines_written, int64_t* bytes_written,
                      char* err, size_t errlen);
 void wgbsseg_beta2bed_pass_ms(const wgbsseg_ctx* ctx, double* length_ms, double* emit_ms);
+
+/*
+ * The same text as BGZF (the SAM specification, 4.1: gzip members of at most 64 KiB that `bgzip -d`, `gzip -d`, `tabix` and
+ * wgbsseg_bgzf_inflate read): the arguments of wgbsseg_beta2bed and text_bytes.  Behind a slab's emit pass its text is cut into members
+ * of 65280 bytes (the last one shorter), each deflated by one wavefront (csrc/deflate_core.h, csrc/deflate_kernels.h) and packed densely
+ * on the device; only the compressed bytes come to the host and go to fd.  The end-of-file member (28 bytes) follows the last slab; a call
+ * without a line writes it alone.  The text the file inflates to never depends on slab_sites or stage_bytes.  The compressed bytes do
+ * depend on slab_sites, since members are cut per slab.  bytes_written: what went to fd; text_bytes (may be NULL): the text before
+ * compression.  wgbsseg_bgzf_deflate_ms: the device time of the deflate and pack launches of the last call (-1 without a context);
+ * wgbsseg_bgzf_deflate_pass_ms splits it (either pointer may be NULL).
+ *
+ * wgbsseg_bgzf_deflate: n bytes of host text -> BGZF bytes in out[0 .. *out_len), with the end-of-file member when eof is not 0.  out_cap
+ * must be at least wgbsseg_bgzf_deflate_bound(n) (every member stored, plus the end-of-file member), else WGBSSEG_E_CAPACITY: the size is
+ * known only when the device is done.  n = 0 gives no member, or the end-of-file member alone.  The same bytes as the encoder's host twin
+ * (deflate_member_host) gives member by member.  The counterpart of wgbsseg_bgzf_inflate.
+ */
+int wgbsseg_beta2bed_bgzf(wgbsseg_ctx* ctx, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
+                          const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
+                          const wgbsseg_bed_opts* opts, int fd, int64_t* lines_written, int64_t* bytes_written, int64_t* text_bytes,
+                          char* err, size_t errlen);
+double wgbsseg_bgzf_deflate_ms(const wgbsseg_ctx* ctx);
+void wgbsseg_bgzf_deflate_pass_ms(const wgbsseg_ctx* ctx, double* deflate_ms, double* pack_ms);
+int64_t wgbsseg_bgzf_deflate_bound(int64_t n);
+int wgbsseg_bgzf_deflate(int device, const void* text, int64_t n, void* out, int64_t out_cap, int64_t* out_len, int eof, char* err, size_t errlen);
 /* the default and the largest slab_sites, the largest (= default) stage_bytes, the longest chromosome name; any pointer may be NULL */
 void wgbsseg_beta2bed_limits(int64_t* default_slab, int64_t* max_slab, int32_t* max_stage_bytes, int32_t* max_name);
 

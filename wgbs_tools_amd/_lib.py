@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 300          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 310          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -47,7 +47,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_patbeta_feed_bgzf', 'wgbsseg_homog_feed_bgzf', 'wgbsseg_bimodal_feed_bgzf',
            'wgbsseg_patbeta_inflate_ms', 'wgbsseg_homog_inflate_ms', 'wgbsseg_bimodal_inflate_ms', 'wgbsseg_bgzf_inflate',
            'wgbsseg_fraglen_create', 'wgbsseg_fraglen_feed', 'wgbsseg_fraglen_feed_bgzf', 'wgbsseg_fraglen_finish', 'wgbsseg_fraglen_destroy',
-           'wgbsseg_fraglen_kernel_ms', 'wgbsseg_fraglen_inflate_ms']
+           'wgbsseg_fraglen_kernel_ms', 'wgbsseg_fraglen_inflate_ms',
+           'wgbsseg_bgzf_deflate', 'wgbsseg_bgzf_deflate_bound', 'wgbsseg_beta2bed_bgzf', 'wgbsseg_bgzf_deflate_ms', 'wgbsseg_bgzf_deflate_pass_ms']
 
 
 class NativeLibraryError(RuntimeError):
@@ -205,6 +206,16 @@ def load():
     L.wgbsseg_pair_hist_limits.argtypes = [vp, vp]
     L.wgbsseg_beta2bed.restype = i32
     L.wgbsseg_beta2bed.argtypes = [vp, i32, i64, i64, vp, vp, C.POINTER(C.c_char_p), i32, C.POINTER(BedOpts), C.c_int, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_beta2bed_bgzf.restype = i32
+    L.wgbsseg_beta2bed_bgzf.argtypes = [vp, i32, i64, i64, vp, vp, C.POINTER(C.c_char_p), i32, C.POINTER(BedOpts), C.c_int, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_bgzf_deflate_ms.restype = C.c_double
+    L.wgbsseg_bgzf_deflate_ms.argtypes = [vp]
+    L.wgbsseg_bgzf_deflate_pass_ms.restype = None
+    L.wgbsseg_bgzf_deflate_pass_ms.argtypes = [vp, vp, vp]
+    L.wgbsseg_bgzf_deflate_bound.restype = i64
+    L.wgbsseg_bgzf_deflate_bound.argtypes = [i64]
+    L.wgbsseg_bgzf_deflate.restype = i32
+    L.wgbsseg_bgzf_deflate.argtypes = [i32, C.c_char_p, i64, vp, i64, C.POINTER(i64), i32, C.c_char_p, C.c_size_t]
     L.wgbsseg_beta2bed_pass_ms.restype = None
     L.wgbsseg_beta2bed_pass_ms.argtypes = [vp, vp, vp]
     L.wgbsseg_beta2bed_limits.restype = None
@@ -552,10 +563,11 @@ class Segmenter:
         return counts
 
     def beta2bed(self, fd, sample, chrom_names, chrom_cum, start0=0, end0=None, mult=None, min_cov=1, mean=False, keep_na=False,
-                 slab_sites=0, stage_bytes=0):
+                 slab_sites=0, stage_bytes=0, bgzf=False):
         """wgbsseg_beta2bed: resident sample `sample` as BED text, a line per site of [start0, end0) (`mult`: uint16 copies per
         site), written to the file descriptor `fd` -> (lines written, bytes written).  A failed write raises OSError with the
-        descriptor's errno (BrokenPipeError for a reader that went away)."""
+        descriptor's errno (BrokenPipeError for a reader that went away).  bgzf=True (wgbsseg_beta2bed_bgzf): the text is deflated
+        into BGZF members on the device and those are written, the end-of-file member last -> (lines, bytes written, bytes of text)."""
         end0 = self.n_sites if end0 is None else int(end0)
         cum = np.ascontiguousarray(chrom_cum, dtype=np.int64)
         names = (C.c_char_p * len(chrom_names))(*[str(n).encode() for n in chrom_names])
@@ -566,15 +578,29 @@ class Segmenter:
                 raise ValueError('beta2bed: mult must hold one count per site of [start0, end0): %d for %d sites' % (m.size, end0 - int(start0)))
         opts = BedOpts(int(min_cov), int(bool(mean)), int(bool(keep_na)), int(stage_bytes), int(slab_sites))
         lines, nbytes = C.c_int64(0), C.c_int64(0)
-        rc = self._L.wgbsseg_beta2bed(self._h, int(sample), int(start0), end0, None if m is None else m.ctypes.data, cum.ctypes.data, names,
-                                      len(chrom_names), C.byref(opts), int(fd), C.addressof(lines), C.addressof(nbytes), self._err, ERRLEN)
+        ntext = C.c_int64(0)
+        if bgzf:
+            rc = self._L.wgbsseg_beta2bed_bgzf(self._h, int(sample), int(start0), end0, None if m is None else m.ctypes.data, cum.ctypes.data, names,
+                                               len(chrom_names), C.byref(opts), int(fd), C.addressof(lines), C.addressof(nbytes), C.addressof(ntext),
+                                               self._err, ERRLEN)
+        else:
+            rc = self._L.wgbsseg_beta2bed(self._h, int(sample), int(start0), end0, None if m is None else m.ctypes.data, cum.ctypes.data, names,
+                                          len(chrom_names), C.byref(opts), int(fd), C.addressof(lines), C.addressof(nbytes), self._err, ERRLEN)
         if rc == E_IO:
             import re
             found = re.search(r'errno (\d+)', self._err.value.decode(errors='replace'))
             code = int(found.group(1)) if found else 5
             raise OSError(code, os.strerror(code))
         _check(rc, self._err)
+        if bgzf:
+            return int(lines.value), int(nbytes.value), int(ntext.value)
         return int(lines.value), int(nbytes.value)
+
+    def bgzf_deflate_ms(self):
+        """(deflate launches, pack launches) of the last beta2bed(bgzf=True) call, HIP-event milliseconds summed over its slabs"""
+        a, b = C.c_double(0), C.c_double(0)
+        self._L.wgbsseg_bgzf_deflate_pass_ms(self._h, C.addressof(a), C.addressof(b))
+        return float(a.value), float(b.value)
 
     def beta2bed_pass_ms(self):
         """(length + scan passes, emit pass) of the last beta2bed call, HIP-event milliseconds summed over its slabs"""
@@ -832,6 +858,23 @@ def bgzf_inflate(data, device=0, refusal=False):
         return out[:n.value].tobytes(), int(used.value), err.value.decode(errors='replace')
     _check(rc, err)
     return (out[:n.value].tobytes(), int(used.value), None) if refusal else (out[:n.value].tobytes(), int(used.value))
+
+
+def bgzf_deflate_bound(n):
+    """wgbsseg_bgzf_deflate_bound: the most bytes n bytes of text can become, the end-of-file member included"""
+    return int(load().wgbsseg_bgzf_deflate_bound(int(n)))
+
+
+def bgzf_deflate(data, device=0, eof=True, cap=None):
+    """wgbsseg_bgzf_deflate: `data` as BGZF members of 65280 bytes of text each (the last one shorter), deflated on the device, with the
+    end-of-file member behind them unless eof=False -> bytes.  cap: the room handed to the library (default: its bound)."""
+    L = load()
+    data = bytes(data)
+    out = np.empty(max(int(L.wgbsseg_bgzf_deflate_bound(len(data))) if cap is None else int(cap), 1), dtype=np.uint8)
+    n = C.c_int64(0)
+    err = C.create_string_buffer(ERRLEN)
+    _check(L.wgbsseg_bgzf_deflate(int(device), data, len(data), out.ctypes.data, out.size if cap is None else int(cap), C.byref(n), int(bool(eof)), err, ERRLEN), err)
+    return out[:n.value].tobytes()
 
 
 def _bgzf_member_size(buf, pos):

@@ -23,6 +23,9 @@ view.py:35-51, src/view_beta.sh, src/view_lbeta.sh: `gunzip | awk | paste | hexd
               not run.
     -o PATH   default: standard output.  A path ending in .gz is compressed in this process (zlib, through gzip.GzipFile); no
               program is started.  -f / the skip message: delete_or_skip.  A reader that goes away ends the command quietly.
+    --deflate device   (with -o PATH.gz only) the text never leaves the device: wgbsseg_beta2bed_bgzf deflates every slab into BGZF
+              members there (csrc/deflate_kernels.h) and writes them straight to the file, the end-of-file member last; no pipe, no
+              thread.  The file is BGZF, so `gzip -d` reads it as before and `tabix` can index it.  The default, host, is the line above.
 
 Deliberate deviations from the reference: a beta file whose length differs from the genome's is refused after the reference's
 warning (its `paste` would print ragged lines); `bedtools`, `tabix`, `hexdump`, `awk` and `gzip` are not run.  No CPU fallback.
@@ -119,8 +122,16 @@ class _GzipSink:
             raise self._error
 
 
-def write_bed(seg, fd, gr, bed_path, min_cov=1, mean=False, keep_na=False, sample=0, slab_sites=0):
-    """the selected lines of resident sample `sample` to the descriptor -> (lines, bytes)"""
+def check_deflate(deflate, opath):
+    """--deflate device needs a .gz path to write BGZF to"""
+    if deflate not in ('host', 'device'):
+        raise IllegalArgumentError(f"deflate must be 'host' or 'device', not {deflate!r}")
+    if deflate == 'device' and (opath is None or opath == '/dev/stdout' or not opath.endswith('.gz')):
+        raise IllegalArgumentError('--deflate device compresses the output on the GPU: give -o a path that ends in .gz')
+
+
+def write_bed(seg, fd, gr, bed_path, min_cov=1, mean=False, keep_na=False, sample=0, slab_sites=0, bgzf=False):
+    """the selected lines of resident sample `sample` to the descriptor -> (lines, bytes); bgzf: as BGZF -> (lines, bytes, bytes of text)"""
     names, sizes = gr.genome.get_chrom_cpg_sizes()
     cum = np.cumsum(sizes)
     start0, end0, mult = 0, seg.n_sites, None
@@ -129,12 +140,13 @@ def write_bed(seg, fd, gr, bed_path, min_cov=1, mean=False, keep_na=False, sampl
         end0 = start0 + mult.size
     elif not gr.is_whole():
         start0, end0 = gr.sites[0] - 1, gr.sites[1] - 1
-    return seg.beta2bed(fd, sample, names, cum, start0, end0, mult, min_cov=min_cov, mean=mean, keep_na=keep_na, slab_sites=slab_sites)
+    return seg.beta2bed(fd, sample, names, cum, start0, end0, mult, min_cov=min_cov, mean=mean, keep_na=keep_na, slab_sites=slab_sites, bgzf=bgzf)
 
 
-def beta_to_bed(beta_path, gr, bed_path, min_cov, mean, keep_na, force, opath, device=0):
+def beta_to_bed(beta_path, gr, bed_path, min_cov, mean, keep_na, force, opath, device=0, deflate='host', slab_sites=0):
     """beta2bed.py:22-31"""
     from . import _lib
+    check_deflate(deflate, opath)
     if not delete_or_skip(opath, force):
         return
     same_size = beta_sanity_check(beta_path, gr.genome)              # (view.py:36: the warning comes before the suffix is looked at)
@@ -151,7 +163,7 @@ def beta_to_bed(beta_path, gr, bed_path, min_cov, mean, keep_na, force, opath, d
         if to_stdout:
             sys.stdout.flush()
             fd = 1
-        elif opath.endswith('.gz'):
+        elif opath.endswith('.gz') and deflate != 'device':
             sink = _GzipSink(opath)
             fd = sink.fd
         else:
@@ -159,7 +171,7 @@ def beta_to_bed(beta_path, gr, bed_path, min_cov, mean, keep_na, force, opath, d
             fd = out.fileno()
         try:
             try:
-                write_bed(seg, fd, gr, bed_path, min_cov, mean, keep_na)
+                write_bed(seg, fd, gr, bed_path, min_cov, mean, keep_na, slab_sites=slab_sites, bgzf=deflate == 'device')
             except _lib.SegmentorError as e:
                 raise IllegalArgumentError(f'{beta_path}: {e.msg}')
         finally:
@@ -183,6 +195,9 @@ def parse_args(argv=None):
     parser.add_argument('--outpath', '-o', default='/dev/stdout', help='Output path. [stdout]')
     add_where_options(parser, bed_file=True)
     parser.add_argument('--device', type=int, default=0, help='HIP device index [0]')
+    parser.add_argument('--deflate', choices=['host', 'device'], default='host',
+                        help='Where a .gz output is compressed: in this process by zlib [host], or on the GPU into BGZF members (device)')
+    parser.add_argument('--slab_sites', type=int, default=0, help='Sites per slab of text; 0: the default of the library. Changes speed only [0]')
     return parser.parse_args(argv)
 
 
@@ -194,7 +209,7 @@ def main(argv=None):
     require_file(args.beta_path)
     gr = GenomicRegion(args)
     try:
-        beta_to_bed(args.beta_path, gr, args.bed_file, args.min_cov, args.mean, args.keep_na, args.force, args.outpath, args.device)
+        beta_to_bed(args.beta_path, gr, args.bed_file, args.min_cov, args.mean, args.keep_na, args.force, args.outpath, args.device, args.deflate, args.slab_sites)
     except BrokenPipeError:                                        # e.g. the output is piped to head (cview.py:12-17)
         os.dup2(os.open(os.devnull, os.O_WRONLY), sys.stdout.fileno())
 

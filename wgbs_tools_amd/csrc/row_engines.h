@@ -283,6 +283,8 @@ struct BedRun {
     BedWgTable wg = {};                  // where the workgroup table keeps what (bed_plan.h)
     int64_t lines = 0, bytes = 0;        // lines counted | bytes written so far
     uint64_t home_bytes[2] = {0, 0};     // per parity: the text of the slab that last took it, in bytes
+    bool bgzf = false;                   // the text stays on the device: its BGZF members come home and are written
+    int64_t text_bytes = 0;              //   the text deflated so far, in bytes
 
     wg_bed_args slab_args(int64_t k) const { wg_bed_args s = base; s.first = plan.slab_first(k); s.n = (int32_t)plan.slab_count(k); return s; }
     uint64_t* wg_at(int64_t word) const { return c->bed.wg.as<uint64_t>() + word; }
@@ -299,6 +301,8 @@ struct BedRun {
     int wait_home(int64_t k);              // waits for the stream: slab k's totals and slab k-1's text are home; reads slab k-1's emit time
     int take_totals(int64_t k);            // reads slab k's length time and its totals: lines counted, bytes checked and kept for its parity
     int queue_emit(int64_t k);             // queues slab k's emit pass (emit0 .. emit1) and its text's way home; nothing for a slab without text
+    int queue_deflate(int64_t k);          // bgzf: behind slab k's emit pass its text becomes members (def0 .. def1), packed densely (.. pack1); the packed size's way home
+    int fetch_packed(int64_t k);           // bgzf: slab k's packed members, whose size is home, come home on a stream of their own; waits for them
     int write_home(int64_t k);             // writes slab k's text, which is home, to fd; -> 0 or errno
     int finish(int io, int64_t* lines_written, int64_t* bytes_written);   // the call's time and counts; after a failed write, waits for what is still queued
 };
@@ -307,6 +311,7 @@ int BedRun::tables_up(int32_t sample, const int64_t* chrom_cum, const char* cons
 {
     BedScratch& s = c->bed;
     for (auto& ev : s.ev) for (Event* e : {&ev.len0, &ev.len1, &ev.emit0, &ev.emit1}) if (!e->h) HIP_TRY(e->create());
+    if (bgzf) for (auto& ev : s.ev) for (Event* e : {&ev.def0, &ev.def1, &ev.pack1}) if (!e->h) HIP_TRY(e->create());
     const std::vector<char> tab = wg_bed_pack_chroms(chrom_cum, chrom_names, n_chroms);
     const BedChromTable at = wg_bed_chrom_table(n_chroms);
     wg = wg_bed_wg_table(BedPlan::workgroups(plan.slab_count(0)));
@@ -349,6 +354,10 @@ int BedRun::wait_home(int64_t k)
     if (k == 0) return WGBSSEG_OK;
     const int before = wg_bed_parity(k - 1);
     if (home_bytes[before]) HIP_TRY(add_ms(c->bed.emit_ms, c->bed.ev[before].emit0, c->bed.ev[before].emit1));
+    if (home_bytes[before] && bgzf) {
+        HIP_TRY(add_ms(c->bed.deflate_ms, c->bed.ev[before].def0, c->bed.ev[before].def1));
+        HIP_TRY(add_ms(c->bed.pack_ms, c->bed.ev[before].def1, c->bed.ev[before].pack1));
+    }
     return WGBSSEG_OK;
 }
 
@@ -373,14 +382,55 @@ int BedRun::queue_emit(int64_t k)
     if (!tot) return WGBSSEG_OK;
     const BedTextCap cap = wg_bed_text_capacity(tot, plan.slab_bytes_bound(0));
     HIP_TRY(s.out[par].ensure(cap.device));
-    if (!s.home[par].ensure(cap.home)) { set_err(err, errlen, "beta2bed: out of page-locked host memory (%llu bytes)", (unsigned long long)tot); return WGBSSEG_E_NOMEM; }
+    if (!bgzf && !s.home[par].ensure(cap.home)) { set_err(err, errlen, "beta2bed: out of page-locked host memory (%llu bytes)", (unsigned long long)tot); return WGBSSEG_E_NOMEM; }
     const wg_bed_args a = slab_args(k);
     const dim3 grid((unsigned)BedPlan::workgroups(a.n));
     HIP_TRY(hipEventRecord(s.ev[par].emit0, c->sA));
     by_elem(c->elem, [&](auto E) { hipLaunchKernelGGL(k_bed_emit<decltype(E)::value>, grid, dim3(WG_BED_BLOCK), 0, c->sA, a, wg_at(wg.base), s.out[par].as<char>()); });
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s.ev[par].emit1, c->sA));
+    if (bgzf) return queue_deflate(k);
     HIP_TRY(hipMemcpyAsync(s.home[par].p, s.out[par].p, (size_t)tot, hipMemcpyDeviceToHost, c->sA));
+    return WGBSSEG_OK;
+}
+
+// The members of a slab are cut from the slab's own text (65280 bytes each, the last one shorter), so the compressed bytes depend on the
+// slab size; the text they inflate to does not.
+int BedRun::queue_deflate(int64_t k)
+{
+    BedScratch& s = c->bed;
+    const int par = wg_bed_parity(k);
+    const int64_t tot = (int64_t)home_bytes[par], members = wg_deflate_members(tot);
+    HIP_TRY(s.slots.ensure((size_t)members * WG_DEF_PITCH));
+    HIP_TRY(s.zmeta.ensure((size_t)(2 * members + 2) * 8));
+    HIP_TRY(s.packed[par].ensure((size_t)wg_deflate_bound(tot)));
+    if (!s.ztot.ensure(2 * 2 * 8)) { set_err(err, errlen, "beta2bed: out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    uint64_t* sizes = s.zmeta.as<uint64_t>(), *first = sizes + members, *totals = first + members;
+    HIP_TRY(hipEventRecord(s.ev[par].def0, c->sA));
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)((members + WG_DEF_WAVES - 1) / WG_DEF_WAVES)), dim3(64 * WG_DEF_WAVES), 0, c->sA,
+                       s.out[par].as<const uint8_t>(), tot, members, s.slots.as<uint8_t>(), sizes);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s.ev[par].def1, c->sA));
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, c->sA, sizes, sizes, members, first, totals);
+    hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)members), dim3(WG_PACK_BLOCK), 0, c->sA, s.slots.as<const uint8_t>(), sizes, first, s.packed[par].as<uint8_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s.ev[par].pack1, c->sA));
+    HIP_TRY(hipMemcpyAsync(static_cast<uint64_t*>(s.ztot.p) + 2 * par, totals, 16, hipMemcpyDeviceToHost, c->sA));
+    return WGBSSEG_OK;
+}
+
+int BedRun::fetch_packed(int64_t k)
+{
+    BedScratch& s = c->bed;
+    const int par = wg_bed_parity(k);
+    if (!home_bytes[par]) return WGBSSEG_OK;
+    const uint64_t packed = static_cast<volatile const uint64_t*>(s.ztot.p)[2 * par];
+    if (packed > (uint64_t)wg_deflate_bound((int64_t)home_bytes[par])) { set_err(err, errlen, "beta2bed: slab %lld packed to %llu bytes, more than its bound", (long long)k, (unsigned long long)packed); return WGBSSEG_E_HIP; }
+    if (!s.home[par].ensure((size_t)packed)) { set_err(err, errlen, "beta2bed: out of page-locked host memory (%llu bytes)", (unsigned long long)packed); return WGBSSEG_E_NOMEM; }
+    HIP_TRY(hipMemcpyAsync(s.home[par].p, s.packed[par].p, (size_t)packed, hipMemcpyDeviceToHost, c->sB));
+    HIP_TRY(hipStreamSynchronize(c->sB));
+    text_bytes += (int64_t)home_bytes[par];
+    home_bytes[par] = packed;                                    // what write_home writes
     return WGBSSEG_OK;
 }
 
@@ -396,6 +446,10 @@ int BedRun::write_home(int64_t k)
 int BedRun::finish(int io, int64_t* lines_written, int64_t* bytes_written)
 {
     c->last_block_sums_ms = c->bed.len_ms + c->bed.emit_ms;
+    if (bgzf && !io) {
+        io = write_all(fd, reinterpret_cast<const char*>(WG_BGZF_EOF), sizeof(WG_BGZF_EOF));
+        if (!io) bytes += (int64_t)sizeof(WG_BGZF_EOF);
+    }
     if (bytes_written) *bytes_written = bytes;
     if (io) {
         (void)hipStreamSynchronize(c->sA);                       // (what is still in flight lands in buffers the context keeps)
@@ -410,39 +464,109 @@ int BedRun::finish(int io, int64_t* lines_written, int64_t* bytes_written)
 
 extern "C" {
 
-// state checks -> plan (bed_plan.h) -> the slab pipeline: while the device emits slab k and measures slab k+1, the host writes slab k-1
-int wgbsseg_beta2bed(wgbsseg_ctx* c, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
-                     const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
-                     const wgbsseg_bed_opts* o, int fd, int64_t* lines_written, int64_t* bytes_written,
-                     char* err, size_t errlen)
+}  // extern "C"
+
+namespace {
+
+// state checks -> plan (bed_plan.h) -> the slab pipeline: while the device emits slab k and measures slab k+1, the host writes slab k-1.
+// bgzf: slab k's text is deflated and packed on the device behind its emit pass; what comes home and is written are its BGZF members,
+// and the end-of-file member follows the last slab.
+int beta2bed_run(wgbsseg_ctx* c, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
+                 const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
+                 const wgbsseg_bed_opts* o, int fd, bool bgzf, int64_t* lines_written, int64_t* bytes_written, int64_t* text_bytes,
+                 char* err, size_t errlen)
 {
     if (c && lines_written) *lines_written = 0;
     if (c && bytes_written) *bytes_written = 0;
+    if (c && text_bytes) *text_bytes = 0;
     if (const int rc = need_rows(c, err, errlen)) return rc;
     if (!c->loci || c->n_loci != c->n_total) { set_err(err, errlen, "loci not set or length differs from the betas (%lld vs %lld)", (long long)c->n_loci, (long long)c->n_total); return WGBSSEG_E_STATE; }
     BedRun run;
-    run.c = c; run.mult = mult; run.fd = fd; run.err = err; run.errlen = errlen;
+    run.c = c; run.mult = mult; run.fd = fd; run.err = err; run.errlen = errlen; run.bgzf = bgzf;
     std::string msg;
     int rc = wg_bed_plan(sample, c->n_samples, start0, end0, c->n_total, chrom_cum, chrom_names, n_chroms, o, run.plan, msg);
     if (rc == WGBSSEG_OK) rc = wg_bed_check_mult(mult, end0 - start0, start0, msg);
     if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
-    c->bed.len_ms = c->bed.emit_ms = c->last_block_sums_ms = 0.0;
+    c->bed.len_ms = c->bed.emit_ms = c->bed.deflate_ms = c->bed.pack_ms = c->last_block_sums_ms = 0.0;
     const int64_t n = run.plan.n_slabs;
-    if (n == 0) return WGBSSEG_OK;
+    if (n == 0) return bgzf ? run.finish(0, lines_written, bytes_written) : WGBSSEG_OK;
     HIP_TRY(hipSetDevice(c->device));
     rc = run.tables_up(sample, chrom_cum, chrom_names, n_chroms, o);
     if (rc != WGBSSEG_OK) return rc;
     HIP_TRY(run.queue_lengths(0));
     int io = 0;
     for (int64_t k = 0; k <= n && !io; k++) {
-        rc = run.wait_home(k);                                   // slab k's totals and slab k-1's text arrive
+        rc = run.wait_home(k);                                   // slab k's totals and slab k-1's text (bgzf: its packed size) arrive
         if (rc == WGBSSEG_OK && k < n) rc = run.take_totals(k);
-        if (rc == WGBSSEG_OK && k < n) rc = run.queue_emit(k);   // slab k is emitted ...
+        if (rc == WGBSSEG_OK && k < n) rc = run.queue_emit(k);   // slab k is emitted (bgzf: and deflated and packed) ...
         if (rc != WGBSSEG_OK) return rc;
         if (k + 1 < n) HIP_TRY(run.queue_lengths(k + 1));        // ... and the lengths of slab k+1 queued
+        if (k > 0 && bgzf) { rc = run.fetch_packed(k - 1); if (rc != WGBSSEG_OK) return rc; }      // slab k-1's members come home beside that
         if (k > 0) io = run.write_home(k - 1);                   // slab k-1 is written while the device works
     }
+    if (text_bytes) *text_bytes = run.text_bytes;
     return run.finish(io, lines_written, bytes_written);
+}
+
+}  // namespace
+
+extern "C" {
+
+int wgbsseg_beta2bed(wgbsseg_ctx* c, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
+                     const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
+                     const wgbsseg_bed_opts* o, int fd, int64_t* lines_written, int64_t* bytes_written,
+                     char* err, size_t errlen)
+{
+    return beta2bed_run(c, sample, start0, end0, mult, chrom_cum, chrom_names, n_chroms, o, fd, false, lines_written, bytes_written, nullptr, err, errlen);
+}
+
+int wgbsseg_beta2bed_bgzf(wgbsseg_ctx* c, int32_t sample, int64_t start0, int64_t end0, const uint16_t* mult,
+                          const int64_t* chrom_cum, const char* const* chrom_names, int32_t n_chroms,
+                          const wgbsseg_bed_opts* o, int fd, int64_t* lines_written, int64_t* bytes_written, int64_t* text_bytes,
+                          char* err, size_t errlen)
+{
+    return beta2bed_run(c, sample, start0, end0, mult, chrom_cum, chrom_names, n_chroms, o, fd, true, lines_written, bytes_written, text_bytes, err, errlen);
+}
+
+double wgbsseg_bgzf_deflate_ms(const wgbsseg_ctx* c) { return c ? c->bed.deflate_ms + c->bed.pack_ms : -1.0; }
+
+void wgbsseg_bgzf_deflate_pass_ms(const wgbsseg_ctx* c, double* deflate_ms, double* pack_ms)
+{
+    if (deflate_ms) *deflate_ms = c ? c->bed.deflate_ms : 0.0;
+    if (pack_ms) *pack_ms = c ? c->bed.pack_ms : 0.0;
+}
+
+int64_t wgbsseg_bgzf_deflate_bound(int64_t n) { return n < 0 ? -1 : wg_deflate_bound(n); }
+
+// host text -> BGZF bytes: every member by k_bgzf_deflate, packed by k_bgzf_pack (the counterpart of wgbsseg_bgzf_inflate)
+int wgbsseg_bgzf_deflate(int device, const void* text, int64_t n, void* out, int64_t cap, int64_t* out_len, int eof, char* err, size_t errlen)
+{
+    if (!out_len) { set_err(err, errlen, "bad arguments to bgzf_deflate"); return WGBSSEG_E_ARG; }
+    *out_len = 0;
+    DeflatePlan p;
+    std::string msg;
+    int rc = plan_deflate(text, n, out, cap, WG_DEF_WAVES, p, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    rc = check_device(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    uint64_t totals[2] = {0, 0};
+    if (p.members) {
+        HIP_TRY(hipSetDevice(device));
+        DevBuf dtext, slots, meta, dense;
+        HIP_TRY(dtext.ensure((size_t)n)); HIP_TRY(slots.ensure((size_t)p.slot_bytes)); HIP_TRY(meta.ensure((size_t)(2 * p.members + 2) * 8)); HIP_TRY(dense.ensure((size_t)p.bound));
+        uint64_t* sizes = meta.as<uint64_t>(), *first = sizes + p.members, *dtot = first + p.members;
+        HIP_TRY(hipMemcpy(dtext.p, text, (size_t)n, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)p.grid), dim3(64 * WG_DEF_WAVES), 0, 0, dtext.as<const uint8_t>(), n, p.members, slots.as<uint8_t>(), sizes);
+        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, 0, sizes, sizes, p.members, first, dtot);
+        hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)p.members), dim3(WG_PACK_BLOCK), 0, 0, slots.as<const uint8_t>(), sizes, first, dense.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(totals, dtot, 16, hipMemcpyDeviceToHost));
+        if ((int64_t)totals[0] > p.bound - (int64_t)sizeof(WG_BGZF_EOF)) { set_err(err, errlen, "bgzf_deflate: %llu bytes came out, more than the bound", (unsigned long long)totals[0]); return WGBSSEG_E_HIP; }
+        HIP_TRY(hipMemcpy(out, dense.p, (size_t)totals[0], hipMemcpyDeviceToHost));
+    }
+    if (eof) memcpy(static_cast<char*>(out) + totals[0], WG_BGZF_EOF, sizeof(WG_BGZF_EOF));
+    *out_len = (int64_t)totals[0] + (eof ? (int64_t)sizeof(WG_BGZF_EOF) : 0);
+    return WGBSSEG_OK;
 }
 
 void wgbsseg_beta2bed_pass_ms(const wgbsseg_ctx* c, double* length_ms, double* emit_ms)

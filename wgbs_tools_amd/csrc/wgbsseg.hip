@@ -43,6 +43,8 @@
 #include "bimodal_kernels.h"
 #include "inflate_plan.h"
 #include "inflate_kernels.h"
+#include "deflate_plan.h"
+#include "deflate_kernels.h"
 #include "stats_kernels.h"
 #include "pair_kernels.h"
 #include "bed_kernels.h"
@@ -91,11 +93,14 @@ enum BatchEvent { EV_BEGIN, EV_WINDOWS, EV_SCAN_END, EV_PLAN, EV_TRACE0, EV_TRAC
 // at home | per slab parity the events around the length pass and scan and around the emit pass | the two passes' times of the last call.
 // Members go in reverse order of declaration: events, then page-locked memory, then device memory, as when they were the context's own.
 // The context's destructor has synchronised the device by then, so nothing here needs a teardown rule of its own.
+// wgbsseg_beta2bed_bgzf adds: the member slots of one slab | its sizes, first bytes and total (deflate_plan.h) | the packed members of two
+// slabs | their totals at home | per slab parity the events around the deflate launch and behind the pack launch | the two launches' times.
 struct BedScratch {
     DevBuf tab, mult, wg, out[2];
-    PinnedBuf home[2], tot;
-    struct PassEvents { Event len0, len1, emit0, emit1; } ev[2];
-    double len_ms = 0.0, emit_ms = 0.0;
+    DevBuf slots, zmeta, packed[2];
+    PinnedBuf home[2], tot, ztot;
+    struct PassEvents { Event len0, len1, emit0, emit1, def0, def1, pack1; } ev[2];
+    double len_ms = 0.0, emit_ms = 0.0, deflate_ms = 0.0, pack_ms = 0.0;
 };
 
 // What wgbsseg_site_counts and wgbsseg_site_table keep between calls (row_engines.h, SiteRun) beyond BedScratch's workgroup table, text buffers,

@@ -169,9 +169,18 @@ def _bgzf_member(data):
             struct.pack('<II', zlib.crc32(data) & 0xffffffff, len(data)))
 
 
-def write_bgzf(path, data, threads=None):
+def write_bgzf(path, data, threads=None, deflate='host', device=0):
     """`data` as a BGZF file (gzip members of at most 64 KB with the 'BC' size field, then the empty end-of-file member),
-    the members compressed on a pool of threads (zlib releases the interpreter lock)"""
+    the members compressed on a pool of threads (zlib releases the interpreter lock); deflate='device': on the GPU, by one library
+    call (_lib.bgzf_deflate: other bytes, the same text)"""
+    if deflate not in ('host', 'device'):
+        raise IllegalArgumentError(f"deflate must be 'host' or 'device', not {deflate!r}")
+    if deflate == 'device':
+        from . import _lib
+        packed = _lib.bgzf_deflate(data, device=device, eof=True)
+        with open(path, 'wb') as f:
+            f.write(packed)
+        return
     from concurrent.futures import ThreadPoolExecutor
     mv = memoryview(data)
     pieces = [mv[p:p + 65280] for p in range(0, len(data), 65280)]
@@ -219,7 +228,8 @@ def homog_process(pat, blocks, edges, args, outdir, prefix, timings=None):
     if args.binary:
         trim_uxm(vals, args.nr_bits).tofile(opath)
     else:
-        write_bgzf(opath, table_text(blocks, left, vals, op.dirname(opath) or '.'), getattr(args, 'threads', None))
+        write_bgzf(opath, table_text(blocks, left, vals, op.dirname(opath) or '.'), getattr(args, 'threads', None),
+                   deflate=getattr(args, 'deflate', 'host'), device=getattr(args, 'device', 0))
     t['write_s'] = time.perf_counter() - t0
     return opath
 
@@ -294,6 +304,8 @@ def parse_args(argv=None):
     parser.add_argument('-@', '--threads', type=int, default=default_threads(), help='Threads compressing the output [all CPUs]')
     parser.add_argument('--device', type=int, default=0, help='HIP device index [0]')
     add_inflate_option(parser)
+    parser.add_argument('--deflate', choices=['host', 'device'], default='host',
+                        help='Where the .bed.gz output is compressed: on the CPU threads of -@ [host], or on the GPU (device)')
     return parser.parse_args(argv)
 
 
