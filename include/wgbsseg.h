@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 310            /* 0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 320            /* 0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -688,6 +688,44 @@ int wgbsseg_fraglen_finish(wgbsseg_fraglen* h, int64_t* hist, char* err, size_t 
 void wgbsseg_fraglen_destroy(wgbsseg_fraglen* h);
 double wgbsseg_fraglen_kernel_ms(wgbsseg_fraglen* h);
 double wgbsseg_fraglen_inflate_ms(wgbsseg_fraglen* h);
+
+/*
+ * pat -> pat: the reads an interval of CpG indexes lets through, cut, sorted and collapsed (`wgbstools view` / `cview` with one
+ * block: src/cview/cview.cpp:8-17,:87-167, patter_utils.cpp:260-280, `sort -k2,2n -k3,3`, collapse_pat.pl).  create(): the interval
+ * [start_cpg, end_cpg) (start_cpg >= 1, end_cpg > start_cpg, end_cpg < 2^31; the whole genome is [1, nr_sites + 1)); flags, a sum of
+ * WGBSSEG_VIEW_STRICT (1), _STRIP (2), _NO_GAPS (4) and _SORT (8); min_len >= 1; initial_records: the first size of the record table
+ * (<= 0: the default; a small value makes the table and the arena grow: a test hook).  feed() / feed_bgzf(): as for wgbsseg_homog
+ * (text or BGZF bytes, not both); a call first waits for the chunk before it.  Per line `chrom, rs, pattern, count`: dropped when
+ * rs >= end_cpg or rs + len - 1 < start_cpg; STRICT cuts the pattern to the interval; STRIP removes trailing, then leading dots
+ * (moving rs; nothing but dots: dropped); dropped when min_len exceeds what is left; NO_GAPS drops a read that still holds a '.'.
+ * finish(): with SORT the survivors are ordered by rs, then the pattern's bytes, then the chromosome's (a prefix first; ties by input
+ * position), else they keep the input order; adjacent lines equal in all three become one with the int64 sum of their counts, a sum
+ * <= 0 prints nothing; the text "chrom\trs\tpattern\tsum\n" stays on the device, deflated there into BGZF members (wgbsseg_bgzf_deflate's
+ * member rule, the end-of-file member last) when `deflate` is not 0.  *n_lines: the lines; *n_bytes: the bytes read() hands out.
+ * finish() first feeds a last line that has no newline, then returns WGBSSEG_E_ARG for a BGZF member refused on the device, else
+ * "failed in view: ..." naming the byte offset of the first malformed line (fewer than four fields, a site / count that is not a
+ * number, an empty pattern, any byte between the count's digits and the newline), else of the first read that starts before the read
+ * before it (always checked), else for a sum of 10^15 or more.  read(): bytes [offset, offset + len) of the result, after finish().
+ * kernel_ms / inflate_ms: device time of the chunk launches / inflate launches so far; phase_ms: of finish()'s sort, collapse + emit
+ * and deflate.  info(): out[6] = records kept, arena bytes, growths of the record table, growths of the arena, merge passes run,
+ * order (0: no sort asked, 1: found in order, no sort run, 2: sorted).
+ */
+#define WGBSSEG_VIEW_STRICT 1
+#define WGBSSEG_VIEW_STRIP 2
+#define WGBSSEG_VIEW_NO_GAPS 4
+#define WGBSSEG_VIEW_SORT 8
+typedef struct wgbsseg_patview wgbsseg_patview;
+int wgbsseg_patview_create(int device, int64_t start_cpg, int64_t end_cpg, int32_t flags, int32_t min_len, int64_t initial_records,
+                           wgbsseg_patview** out, char* err, size_t errlen);
+int wgbsseg_patview_feed(wgbsseg_patview* v, const char* text, int64_t n_bytes, char* err, size_t errlen);
+int wgbsseg_patview_feed_bgzf(wgbsseg_patview* v, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen);
+int wgbsseg_patview_finish(wgbsseg_patview* v, int64_t* n_lines, int64_t* n_bytes, int32_t deflate, char* err, size_t errlen);
+int wgbsseg_patview_read(wgbsseg_patview* v, int64_t offset, void* buf, int64_t len, char* err, size_t errlen);
+void wgbsseg_patview_destroy(wgbsseg_patview* v);
+double wgbsseg_patview_kernel_ms(wgbsseg_patview* v);
+double wgbsseg_patview_inflate_ms(wgbsseg_patview* v);
+void wgbsseg_patview_phase_ms(const wgbsseg_patview* v, double* sort_ms, double* emit_ms, double* deflate_ms);
+void wgbsseg_patview_info(const wgbsseg_patview* v, int64_t* out);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

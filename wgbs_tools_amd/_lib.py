@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 310          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 320          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -48,7 +48,9 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_patbeta_inflate_ms', 'wgbsseg_homog_inflate_ms', 'wgbsseg_bimodal_inflate_ms', 'wgbsseg_bgzf_inflate',
            'wgbsseg_fraglen_create', 'wgbsseg_fraglen_feed', 'wgbsseg_fraglen_feed_bgzf', 'wgbsseg_fraglen_finish', 'wgbsseg_fraglen_destroy',
            'wgbsseg_fraglen_kernel_ms', 'wgbsseg_fraglen_inflate_ms',
-           'wgbsseg_bgzf_deflate', 'wgbsseg_bgzf_deflate_bound', 'wgbsseg_beta2bed_bgzf', 'wgbsseg_bgzf_deflate_ms', 'wgbsseg_bgzf_deflate_pass_ms']
+           'wgbsseg_bgzf_deflate', 'wgbsseg_bgzf_deflate_bound', 'wgbsseg_beta2bed_bgzf', 'wgbsseg_bgzf_deflate_ms', 'wgbsseg_bgzf_deflate_pass_ms',
+           'wgbsseg_patview_create', 'wgbsseg_patview_feed', 'wgbsseg_patview_feed_bgzf', 'wgbsseg_patview_finish', 'wgbsseg_patview_read',
+           'wgbsseg_patview_destroy', 'wgbsseg_patview_kernel_ms', 'wgbsseg_patview_inflate_ms', 'wgbsseg_patview_phase_ms', 'wgbsseg_patview_info']
 
 
 class NativeLibraryError(RuntimeError):
@@ -306,7 +308,23 @@ def load():
     L.wgbsseg_fraglen_destroy.argtypes = [vp]
     L.wgbsseg_fraglen_kernel_ms.restype = C.c_double
     L.wgbsseg_fraglen_kernel_ms.argtypes = [vp]
-    for eng in ('patbeta', 'homog', 'bimodal', 'fraglen'):
+    L.wgbsseg_patview_create.restype = i32
+    L.wgbsseg_patview_create.argtypes = [i32, i64, i64, i32, i32, i64, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_feed.restype = i32
+    L.wgbsseg_patview_feed.argtypes = [vp, C.c_char_p, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_finish.restype = i32
+    L.wgbsseg_patview_finish.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), i32, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_read.restype = i32
+    L.wgbsseg_patview_read.argtypes = [vp, i64, vp, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_destroy.restype = None
+    L.wgbsseg_patview_destroy.argtypes = [vp]
+    L.wgbsseg_patview_kernel_ms.restype = C.c_double
+    L.wgbsseg_patview_kernel_ms.argtypes = [vp]
+    L.wgbsseg_patview_phase_ms.restype = None
+    L.wgbsseg_patview_phase_ms.argtypes = [vp, vp, vp, vp]
+    L.wgbsseg_patview_info.restype = None
+    L.wgbsseg_patview_info.argtypes = [vp, vp]
+    for eng in ('patbeta', 'homog', 'bimodal', 'fraglen', 'patview'):
         f = getattr(L, 'wgbsseg_%s_feed_bgzf' % eng)
         f.restype = i32
         f.argtypes = [vp, C.c_char_p, i64, C.POINTER(i64), C.c_char_p, C.c_size_t]
@@ -813,6 +831,52 @@ class FragLen(_PatFeed):
         out = np.empty(self.max_frag, dtype=np.int64)
         self._call('finish', self._h, out.ctypes.data)
         return out
+
+
+class PatView(_PatFeed):
+    """wgbsseg_patview: pat text -> the pat text of `wgbstools view` for the CpG interval [start_cpg, end_cpg) on one GPU: the reads it
+    lets through, cut (strict, strip, min_len, no_gaps), sorted when sort=True, adjacent equal lines collapsed.  finish() -> (lines,
+    bytes) of the result, which stays on the device (as BGZF with deflate=True); read() / chunks() fetch it.  initial_records: the first
+    size of the record table (<= 0: the library's; a small value is the tests' hook for growth)."""
+    _abi = 'patview'
+    STRICT, STRIP, NO_GAPS, SORT = 1, 2, 4, 8                    # include/wgbsseg.h WGBSSEG_VIEW_*
+
+    def __init__(self, start_cpg, end_cpg, strict=False, strip=False, no_gaps=False, sort=False, min_len=1, device=0, initial_records=0):
+        super().__init__()
+        flags = (self.STRICT if strict else 0) | (self.STRIP if strip else 0) | (self.NO_GAPS if no_gaps else 0) | (self.SORT if sort else 0)
+        self.n_lines = self.n_bytes = None
+        self._call('create', int(device), int(start_cpg), int(end_cpg), flags, int(min_len), int(initial_records), C.byref(self._h))
+
+    def finish(self, deflate=False):
+        lines, nbytes = C.c_int64(0), C.c_int64(0)
+        self._call('finish', self._h, C.byref(lines), C.byref(nbytes), 1 if deflate else 0)
+        self.n_lines, self.n_bytes = int(lines.value), int(nbytes.value)
+        return self.n_lines, self.n_bytes
+
+    def read(self, offset=0, length=None):
+        """bytes [offset, offset + length) of the result (default: to its end)"""
+        length = self.n_bytes - offset if length is None else int(length)
+        out = np.empty(max(length, 1), dtype=np.uint8)
+        self._call('read', self._h, int(offset), out.ctypes.data, length)
+        return out[:length].tobytes()
+
+    def chunks(self, piece=64 << 20):
+        """the result in pieces of at most `piece` bytes"""
+        for at in range(0, self.n_bytes, piece):
+            yield self.read(at, min(piece, self.n_bytes - at))
+
+    def phase_ms(self):
+        """(sort, collapse + emit, deflate) of finish(), HIP-event milliseconds"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._L.wgbsseg_patview_phase_ms(self._h, C.addressof(a), C.addressof(b), C.addressof(c))
+        return a.value, b.value, c.value
+
+    def info(self):
+        """records kept, arena bytes, growths of the record table and of the arena, merge passes run, order (0: no sort asked,
+        1: found in order, 2: sorted)"""
+        out = np.zeros(6, dtype=np.int64)
+        self._L.wgbsseg_patview_info(self._h, out.ctypes.data)
+        return dict(zip(('records', 'arena_bytes', 'grown_records', 'grown_arena', 'merge_passes', 'order'), out.tolist()))
 
 
 class Bimodal(_PatFeed):

@@ -1,9 +1,9 @@
-// pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_fraglen, wgbsseg_bimodal), the feed they share
+// pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_fraglen, wgbsseg_bimodal, wgbsseg_patview), the feed they share
 // and their extern "C" entry points.  Part of wgbsseg.hip, which includes it once set_err, HIP_TRY, check_device and the owners are
-// in scope; what an engine decides on the host is in homog_plan.h, frag_plan.h and bimodal_plan.h, this file stages, launches and fetches.
+// in scope; what an engine decides on the host is in homog_plan.h, frag_plan.h, bimodal_plan.h and view_plan.h, this file stages, launches and fetches.
 #pragma once
 
-// The pat-text feed of an engine (wgbsseg_patbeta / _homog / _fraglen / _bimodal): one device and stream; text chunks through two page-locked
+// The pat-text feed of an engine (wgbsseg_patbeta / _homog / _fraglen / _bimodal / _patview): one device and stream; text chunks through two page-locked
 // staging buffers and two device buffers, so that the caller's decompression of chunk k+1 overlaps the copy and the kernels of
 // chunk k; the input offset of the next chunk; and the device time of the launches the engine brackets with span_begin / span_end.
 // There are two ways to fill text[k]: stage_chunk copies text the caller inflated; stage_bgzf copies BGZF bytes as they lie in the file
@@ -863,6 +863,349 @@ int wgbsseg_bgzf_inflate(int device, const void* bytes, int64_t n_bytes, void* o
         return WGBSSEG_E_ARG;
     }
     return WGBSSEG_OK;
+}
+
+}  // extern "C"
+
+// `wgbstools view` / `cview` on one device: the surviving reads of every chunk as records + arena bytes (view_kernels.h), kept until
+// finish(), which sorts (when asked), collapses and writes the text — or its BGZF form — on the device; read() fetches it in slabs.
+// A chunk first waits for the chunk before it (the caller inflated this one meanwhile) and takes its totals, so the two buffers are
+// sized by what they hold plus what this chunk can add (view_plan.h).  The chunk launches are the LAUNCHES span; the phases of finish()
+// have events of their own.
+struct wgbsseg_patview {
+    enum { SORT = 0, EMIT = 1, DEFLATE = 2 };
+    PatFeed feed;
+    ViewPlan plan;
+    DevBuf recs, arena, tiles, totals, state, prev;              // state: bad, desc (8 bytes each), unsorted, too_big (4 bytes each)
+    DevBuf perm[2], head, wg, run_end, run_tail, run_sum, text, slots, meta, dense;
+    PinnedBuf host_tot, fetch;
+    int64_t cap_recs = 0, cap_arena = 0;                          // what recs / arena have room for
+    int64_t n_recs = 0, n_arena = 0;                              // what they hold (the chunks whose totals have been taken)
+    bool pending = false;                                         // a chunk's totals are on their way to host_tot
+    int64_t grown_recs = 0, grown_arena = 0;
+    int passes = 0, order = 0;                                    // order: 0 no sort asked, 1 found in order, 2 sorted
+    unsigned long long chunks = 0;
+    bool finished = false;
+    const void* out = nullptr;                                    // the result on the device (text or dense) and its bytes
+    int64_t out_bytes = 0;
+    Event ph[3][2];
+    bool timed[3] = {false, false, false};
+    double phase_ms[3] = {0.0, 0.0, 0.0};
+    wg_view_args args() const { return {plan.s, plan.e, plan.min_len, plan.flags & (WG_VIEW_STRICT | WG_VIEW_STRIP | WG_VIEW_NO_GAPS)}; }
+    ~wgbsseg_patview() { feed.drain(); }
+};
+
+// waits for the chunk before; its survivors and their bytes join the totals
+static int view_take_totals(wgbsseg_patview* v, char* err, size_t errlen)
+{
+    HIP_TRY(hipStreamSynchronize(v->feed.st));
+    v->feed.collect();
+    if (v->pending) {
+        const uint64_t* t = reinterpret_cast<const uint64_t*>(v->host_tot.p);
+        v->n_recs += (int64_t)t[0]; v->n_arena += (int64_t)t[1];
+        v->pending = false;
+    }
+    return WGBSSEG_OK;
+}
+
+// room for `recs` records and `bytes` arena bytes, by view_plan.h's growth rule; what the buffers hold is kept (the stream is idle)
+static int view_reserve(wgbsseg_patview* v, int64_t recs, int64_t bytes, char* err, size_t errlen)
+{
+    const int64_t nr = wg_view_grow(v->cap_recs, recs), nb = wg_view_grow(v->cap_arena, bytes);
+    if (nr != v->cap_recs) {
+        DevBuf fresh;
+        HIP_TRY(fresh.ensure((size_t)nr * sizeof(wg_view_rec)));
+        if (v->n_recs) HIP_TRY(hipMemcpy(fresh.p, v->recs.p, (size_t)v->n_recs * sizeof(wg_view_rec), hipMemcpyDeviceToDevice));
+        if (v->cap_recs) v->grown_recs++;
+        v->recs = std::move(fresh);
+        v->cap_recs = nr;
+    }
+    if (nb != v->cap_arena) {
+        DevBuf fresh;
+        HIP_TRY(fresh.ensure((size_t)nb));
+        if (v->n_arena) HIP_TRY(hipMemcpy(fresh.p, v->arena.p, (size_t)v->n_arena, hipMemcpyDeviceToDevice));
+        if (v->cap_arena) v->grown_arena++;
+        v->arena = std::move(fresh);
+        v->cap_arena = nb;
+    }
+    return WGBSSEG_OK;
+}
+
+// a staged chunk of n_bytes / gx tiles: totals of the chunk before -> reserve -> measure, scan, scan, pack -> its totals on their way
+template <class Stage>
+static int view_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    PatFeed& f = v->feed;
+    HIP_TRY(hipSetDevice(f.device));
+    if (v->finished) { set_err(err, errlen, "patview_feed: finish() has been called"); return WGBSSEG_E_STATE; }
+    int rc = view_take_totals(v, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    std::string msg;
+    rc = plan_view_chunk(v->n_recs, n_bytes, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    rc = view_reserve(v, v->n_recs + wg_view_chunk_records(n_bytes), v->n_arena + n_bytes, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    HIP_TRY(v->tiles.ensure((size_t)gx * 32));
+    const char* dtext = nullptr;
+    rc = stage(&dtext);
+    if (rc != WGBSSEG_OK) return rc;
+    uint64_t *tile_recs = v->tiles.as<uint64_t>(), *tile_bytes = tile_recs + gx, *rec_base = tile_bytes + gx, *arena_base = rec_base + gx;
+    uint64_t* tot = v->totals.as<uint64_t>();
+    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
+    long long *out = v->prev.as<long long>() + (v->chunks & 1), *in = v->prev.as<long long>() + ((v->chunks & 1) ^ 1);
+    HIP_TRY(hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, f.st));
+    HIP_TRY(f.span_begin());
+    hipLaunchKernelGGL(k_view_measure, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), tile_recs, tile_bytes,
+                       v->state.as<unsigned long long>(), v->state.as<unsigned long long>() + 1, in, out, f.fed);
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_recs, tile_bytes, gx, rec_base, tot);
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_bytes, tile_bytes, gx, arena_base, tot + 2);
+    hipLaunchKernelGGL(k_view_pack, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), rec_base, arena_base,
+                       (uint64_t)v->n_recs, (uint64_t)v->n_arena, v->recs.as<wg_view_rec>(), v->arena.as<char>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(f.span_end());
+    HIP_TRY(hipMemcpyAsync(v->host_tot.p, tot, 16, hipMemcpyDeviceToHost, f.st));
+    v->pending = true;
+    v->chunks += 1;                                               // (the slots swap for the next chunk)
+    HIP_TRY(f.chunk_queued(n_bytes));
+    return WGBSSEG_OK;
+}
+
+static hipError_t view_phase(wgbsseg_patview* v, int which, int end)
+{
+    if (!end) v->timed[which] = true;
+    return hipEventRecord(v->ph[which][end], v->feed.st);
+}
+
+// the permutation of the n records in sorted order -> *perm (nullptr: the input order is the sorted one)
+static int view_sort(wgbsseg_patview* v, int64_t n, const uint32_t** perm, char* err, size_t errlen)
+{
+    const hipStream_t st = v->feed.st;
+    const wg_view_rec* recs = v->recs.as<wg_view_rec>();
+    const char* arena = v->arena.as<char>();
+    uint32_t* unsorted = v->state.as<uint32_t>() + 4;
+    *perm = nullptr;
+    HIP_TRY(view_phase(v, wgbsseg_patview::SORT, 0));
+    hipLaunchKernelGGL(k_view_inorder, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, recs, arena, n, unsorted);
+    HIP_TRY(hipGetLastError());
+    uint32_t flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, unsorted, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    v->order = flag ? 2 : 1;
+    if (flag) {
+        HIP_TRY(v->perm[0].ensure((size_t)n * 4)); HIP_TRY(v->perm[1].ensure((size_t)n * 4));
+        int cur = 0;
+        hipLaunchKernelGGL(k_view_sort_runs, dim3((unsigned)wg_view_runs(n)), dim3(WG_BLOCK), 0, st, recs, arena, n, v->perm[0].as<uint32_t>());
+        const int passes = wg_view_merge_passes(n);
+        int64_t run = WG_VIEW_RUN;
+        const int64_t threads = (n + WG_VIEW_MERGE_ITEMS - 1) / WG_VIEW_MERGE_ITEMS;
+        for (int k = 0; k < passes; k++, run *= 2, cur ^= 1)
+            hipLaunchKernelGGL(k_view_merge, dim3((unsigned)((threads + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, recs, arena, n, run,
+                               v->perm[cur].as<const uint32_t>(), v->perm[cur ^ 1].as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        v->passes = passes;
+        *perm = v->perm[cur].as<const uint32_t>();
+    }
+    HIP_TRY(view_phase(v, wgbsseg_patview::SORT, 1));
+    return WGBSSEG_OK;
+}
+
+// the n records through `perm` -> the collapsed text in v->text; *lines, *bytes
+static int view_emit(wgbsseg_patview* v, int64_t n, const uint32_t* perm, int64_t* lines, int64_t* bytes, char* err, size_t errlen)
+{
+    const hipStream_t st = v->feed.st;
+    const wg_view_rec* recs = v->recs.as<wg_view_rec>();
+    const char* arena = v->arena.as<char>();
+    const int64_t nb = (n + WG_BLOCK - 1) / WG_BLOCK;
+    HIP_TRY(v->head.ensure((size_t)n)); HIP_TRY(v->wg.ensure((size_t)(7 * nb + 6) * 8));
+    HIP_TRY(v->run_end.ensure((size_t)n * 8)); HIP_TRY(v->run_tail.ensure((size_t)n * 4)); HIP_TRY(v->run_sum.ensure((size_t)n * 8));
+    uint64_t *wg_counts = v->wg.as<uint64_t>(), *wg_heads = wg_counts + nb, *count_base = wg_heads + nb, *head_base = count_base + nb;
+    uint64_t *wg_bytes = head_base + nb, *wg_lines = wg_bytes + nb, *line_base = wg_lines + nb, *tot = line_base + nb;      // tot: 3 pairs
+    uint32_t* too_big = v->state.as<uint32_t>() + 5;
+    const dim3 grid((unsigned)nb), block(WG_BLOCK);
+    HIP_TRY(view_phase(v, wgbsseg_patview::EMIT, 0));
+    hipLaunchKernelGGL(k_view_heads, grid, block, 0, st, recs, arena, perm, n, v->head.as<uint8_t>(), wg_counts, wg_heads);
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, wg_counts, wg_heads, nb, count_base, tot);
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, wg_heads, wg_heads, nb, head_base, tot + 2);
+    hipLaunchKernelGGL(k_view_tails, grid, block, 0, st, recs, perm, n, v->head.as<const uint8_t>(), count_base, head_base, v->run_end.as<int64_t>(), v->run_tail.as<uint32_t>());
+    hipLaunchKernelGGL(k_view_runs, grid, block, 0, st, recs, perm, tot + 2, v->run_end.as<const int64_t>(), v->run_tail.as<const uint32_t>(), v->run_sum.as<int64_t>(),
+                       wg_bytes, wg_lines, too_big);
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, wg_bytes, wg_lines, nb, line_base, tot + 4);
+    HIP_TRY(hipGetLastError());
+    uint64_t got[2] = {0, 0};
+    uint32_t big = 0;
+    HIP_TRY(hipMemcpyAsync(got, tot + 4, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&big, too_big, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (big) {
+        set_err(err, errlen, "failed in view: a collapsed count of 10^15 or more (the reference's collapse script would print it in exponent form)");
+        return WGBSSEG_E_ARG;
+    }
+    HIP_TRY(v->text.ensure((size_t)got[0] + 16));
+    hipLaunchKernelGGL(k_view_emit, grid, block, 0, st, recs, arena, perm, tot + 2, v->run_sum.as<const int64_t>(), v->run_tail.as<const uint32_t>(), line_base, v->text.as<char>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(view_phase(v, wgbsseg_patview::EMIT, 1));
+    *bytes = (int64_t)got[0]; *lines = (int64_t)got[1];
+    return WGBSSEG_OK;
+}
+
+// v->text[0, n) -> BGZF members in v->dense, the end-of-file member behind them (the member rule and the kernels of wgbsseg_bgzf_deflate)
+static int view_deflate(wgbsseg_patview* v, int64_t n, int64_t* bytes, char* err, size_t errlen)
+{
+    const hipStream_t st = v->feed.st;
+    const int64_t members = wg_deflate_members(n), bound = wg_deflate_bound(n);
+    if ((members + WG_DEF_WAVES - 1) / WG_DEF_WAVES > 0x7fffffff) { set_err(err, errlen, "view: too much text to deflate in one call"); return WGBSSEG_E_ARG; }
+    HIP_TRY(v->dense.ensure((size_t)bound));
+    uint64_t total = 0;
+    if (members) {
+        HIP_TRY(v->slots.ensure((size_t)members * WG_DEF_PITCH)); HIP_TRY(v->meta.ensure((size_t)(2 * members + 2) * 8));
+        uint64_t *sizes = v->meta.as<uint64_t>(), *first = sizes + members, *dtot = first + members;
+        HIP_TRY(view_phase(v, wgbsseg_patview::DEFLATE, 0));
+        hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)((members + WG_DEF_WAVES - 1) / WG_DEF_WAVES)), dim3(64 * WG_DEF_WAVES), 0, st,
+                           v->text.as<const uint8_t>(), n, members, v->slots.as<uint8_t>(), sizes);
+        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, sizes, sizes, members, first, dtot);
+        hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)members), dim3(WG_PACK_BLOCK), 0, st, v->slots.as<const uint8_t>(), sizes, first, v->dense.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(view_phase(v, wgbsseg_patview::DEFLATE, 1));
+        HIP_TRY(hipMemcpyAsync(&total, dtot, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((int64_t)total > bound - (int64_t)sizeof(WG_BGZF_EOF)) { set_err(err, errlen, "view: %llu bytes came out of the deflate, more than the bound", (unsigned long long)total); return WGBSSEG_E_HIP; }
+    }
+    HIP_TRY(hipMemcpyAsync(v->dense.as<uint8_t>() + total, WG_BGZF_EOF, sizeof(WG_BGZF_EOF), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *bytes = (int64_t)total + (int64_t)sizeof(WG_BGZF_EOF);
+    return WGBSSEG_OK;
+}
+
+extern "C" {
+
+int wgbsseg_patview_create(int device, int64_t start_cpg, int64_t end_cpg, int32_t flags, int32_t min_len, int64_t initial_records,
+                           wgbsseg_patview** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    ViewPlan plan;
+    std::string msg;
+    int rc = plan_view(start_cpg, end_cpg, flags, min_len, initial_records, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    std::unique_ptr<wgbsseg_patview> v(new (std::nothrow) wgbsseg_patview());      // (a failing call below frees what has been made)
+    if (!v) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    rc = v->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    v->plan = plan;
+    for (auto& p : v->ph) for (auto& e : p) HIP_TRY(e.create());
+    HIP_TRY(v->totals.ensure(32)); HIP_TRY(v->state.ensure(24)); HIP_TRY(v->prev.ensure(16));
+    if (!v->host_tot.ensure(16)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    rc = view_reserve(v.get(), plan.initial_records, plan.initial_records * 16, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    const long long none[2] = {WG_PAT_NO_SITE, WG_PAT_NO_SITE};
+    HIP_TRY(hipMemcpy(v->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(v->state.p, 0xff, 16, v->feed.st));
+    HIP_TRY(hipMemsetAsync(v->state.as<char>() + 16, 0, 8, v->feed.st));
+    *out = v.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_patview_destroy(wgbsseg_patview* v) { delete v; }
+
+int wgbsseg_patview_feed(wgbsseg_patview* v, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    return PatFeed::feed_text("patview", v, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
+}
+
+int wgbsseg_patview_feed_bgzf(wgbsseg_patview* v, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+{
+    return PatFeed::feed_bgzf("patview", v, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
+}
+
+// the carry; a refused BGZF member before a malformed line before a descending read; then sort, collapse, emit and (deflate) the BGZF form
+int wgbsseg_patview_finish(wgbsseg_patview* v, int64_t* n_lines, int64_t* n_bytes, int32_t deflate, char* err, size_t errlen)
+{
+    if (!v || !n_lines || !n_bytes) { set_err(err, errlen, "bad arguments to patview_finish"); return WGBSSEG_E_ARG; }
+    *n_lines = *n_bytes = 0;
+    if (v->finished) { set_err(err, errlen, "patview_finish: called twice"); return WGBSSEG_E_STATE; }
+    const hipStream_t st = v->feed.st;
+    HIP_TRY(hipSetDevice(v->feed.device));
+    int rc = v->feed.flush_carry("patview", [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); }, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    v->finished = true;
+    unsigned long long refused[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(refused, v->state.p, 16, hipMemcpyDeviceToHost, st));
+    rc = view_take_totals(v, err, errlen);                         // (waits for the stream)
+    if (rc != WGBSSEG_OK) return rc;
+    rc = v->feed.inflate_refused(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    if (refused[0] != ~0ULL) {
+        set_err(err, errlen, "failed in view: invalid line at byte offset %llu of the input (too few columns, a site / count that is not a number, an empty pattern, or something between the count and the end of the line)", refused[0]);
+        return WGBSSEG_E_ARG;
+    }
+    if (pat_refused(PatRefusal::unsorted, refused[1], "failed in view:", err, errlen)) return WGBSSEG_E_ARG;
+    const int64_t n = v->n_recs;
+    int64_t lines = 0, bytes = 0;
+    if (n) {
+        const uint32_t* perm = nullptr;
+        if (v->plan.flags & WG_VIEW_SORT) {
+            rc = view_sort(v, n, &perm, err, errlen);
+            if (rc != WGBSSEG_OK) return rc;
+        }
+        rc = view_emit(v, n, perm, &lines, &bytes, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+    }
+    v->out = v->text.p; v->out_bytes = bytes;
+    if (deflate) {
+        rc = view_deflate(v, bytes, &v->out_bytes, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        v->out = v->dense.p;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < 3; k++) {
+        float ms = 0.f;
+        if (v->timed[k] && hipEventElapsedTime(&ms, v->ph[k][0], v->ph[k][1]) == hipSuccess) v->phase_ms[k] = (double)ms;
+    }
+    *n_lines = lines; *n_bytes = v->out_bytes;
+    return WGBSSEG_OK;
+}
+
+// bytes [offset, offset + len) of the result, in slabs through page-locked staging
+int wgbsseg_patview_read(wgbsseg_patview* v, int64_t offset, void* buf, int64_t len, char* err, size_t errlen)
+{
+    if (!v || !v->finished) { set_err(err, errlen, "patview_read: nothing to read before finish()"); return WGBSSEG_E_STATE; }
+    std::string msg;
+    const int rc = plan_view_read(offset, len, v->out_bytes, buf, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    if (len == 0) return WGBSSEG_OK;
+    HIP_TRY(hipSetDevice(v->feed.device));
+    if (!v->fetch.ensure_exact((size_t)std::min<int64_t>(len, WG_VIEW_SLAB))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    const char* src = static_cast<const char*>(v->out) + offset;
+    for (int64_t k = 0; k < wg_view_slabs(len); k++) {
+        const int64_t nb = wg_view_slab_len(len, k);
+        HIP_TRY(hipMemcpyAsync(v->fetch.p, src + k * WG_VIEW_SLAB, (size_t)nb, hipMemcpyDeviceToHost, v->feed.st));
+        HIP_TRY(hipStreamSynchronize(v->feed.st));
+        memcpy(static_cast<char*>(buf) + k * WG_VIEW_SLAB, v->fetch.p, (size_t)nb);
+    }
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_patview_kernel_ms(wgbsseg_patview* v)
+{
+    return v ? v->feed.kernel_ms() : -1.0;
+}
+
+double wgbsseg_patview_inflate_ms(wgbsseg_patview* v)
+{
+    return v ? v->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
+}
+
+void wgbsseg_patview_phase_ms(const wgbsseg_patview* v, double* sort_ms, double* emit_ms, double* deflate_ms)
+{
+    if (sort_ms) *sort_ms = v ? v->phase_ms[wgbsseg_patview::SORT] : 0.0;
+    if (emit_ms) *emit_ms = v ? v->phase_ms[wgbsseg_patview::EMIT] : 0.0;
+    if (deflate_ms) *deflate_ms = v ? v->phase_ms[wgbsseg_patview::DEFLATE] : 0.0;
+}
+
+void wgbsseg_patview_info(const wgbsseg_patview* v, int64_t* out)
+{
+    if (!v || !out) return;
+    out[0] = v->n_recs; out[1] = v->n_arena; out[2] = v->grown_recs; out[3] = v->grown_arena; out[4] = v->passes; out[5] = v->order;
 }
 
 }  // extern "C"

@@ -1,0 +1,81 @@
+// view_plan.h — the host plan of `wgbstools view` (wgbsseg_patview_*): the argument checks with their messages, the limits of the
+// record table and its arena, how the two grow, the sort's run length and number of merge passes, and the slabs of the fetch.  No HIP
+// here (like frag_plan.h): g++ compiles it alone, tests/native/view_host.cpp hands it to the tests.
+//
+// Limits.  A record is 32 bytes (view_core.h); their number stays below 2^31, so a permutation entry is a uint32.  A survivor puts
+// its chromosome and at most its pattern into the arena, both bytes of its own line: the arena never holds more than the text fed,
+// and room for "the bytes fed so far + this chunk" is always enough — no count from the device is needed to size it.  A valid line
+// has at least WG_VIEW_MIN_LINE bytes, which bounds the records a chunk can add.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include "block_plan.h"                // wg_plan_refuse
+#include "view_core.h"
+
+#define WG_VIEW_MAX_RECORDS 0x7fffffffLL
+#define WG_VIEW_MIN_LINE 7               // "\t1\tC\t1\n": the shortest line that parses
+#define WG_VIEW_MAX_CHUNK 0x7fffffffLL   // bytes of one chunk: lengths inside it fit 32 bits
+#define WG_VIEW_DEFAULT_RECORDS (1 << 20)
+#define WG_VIEW_RUN 512                  // R: indices one workgroup sorts in LDS
+#define WG_VIEW_MERGE_ITEMS 16           // output elements one thread merges
+#define WG_VIEW_SLAB (8ll << 20)         // bytes of one fetch through the page-locked staging buffer
+
+struct ViewPlan {
+    int64_t s = 1, e = 2;
+    int flags = 0;
+    int64_t min_len = 1;
+    int64_t initial_records = WG_VIEW_DEFAULT_RECORDS;
+};
+
+inline int plan_view(int64_t s, int64_t e, int32_t flags, int32_t min_len, int64_t initial_records, ViewPlan& p, std::string& msg)
+{
+    p = ViewPlan();
+    if (s < 1) return wg_plan_refuse(msg, "view: the interval starts at site %lld (sites count from 1)", (long long)s);
+    if (e <= s) return wg_plan_refuse(msg, "view: the interval [%lld, %lld) is empty", (long long)s, (long long)e);
+    if (e > 0x7fffffffLL) return wg_plan_refuse(msg, "view: the interval ends at site %lld (at most %lld)", (long long)e, 0x7fffffffLL);
+    if (flags & ~WG_VIEW_FLAGS_ALL) return wg_plan_refuse(msg, "view: unknown flags %d", (int)flags);
+    if (min_len < 1) return wg_plan_refuse(msg, "view: min_len %d (at least 1)", (int)min_len);
+    if (initial_records > WG_VIEW_MAX_RECORDS) return wg_plan_refuse(msg, "view: %lld initial records (below 2^31)", (long long)initial_records);
+    p.s = s; p.e = e; p.flags = flags; p.min_len = min_len;
+    p.initial_records = initial_records <= 0 ? WG_VIEW_DEFAULT_RECORDS : initial_records;
+    return WGBSSEG_OK;
+}
+
+// the records a chunk of n_bytes can add at most
+inline int64_t wg_view_chunk_records(int64_t n_bytes) { return n_bytes / WG_VIEW_MIN_LINE + 1; }
+
+// The growth rule of both buffers: room for `need` units where `cap` are there -> the new capacity: `cap` when it is enough, else
+// at least twice as much (geometric: k growths hold 2^k times the first size).  The engine copies what the old buffer held.
+inline int64_t wg_view_grow(int64_t cap, int64_t need) { return need <= cap ? cap : std::max(need, 2 * cap); }
+
+// the records of the chunks so far + a chunk of n_bytes: refused at 2^31
+inline int plan_view_chunk(int64_t n_records, int64_t n_bytes, std::string& msg)
+{
+    if (n_bytes > WG_VIEW_MAX_CHUNK) return wg_plan_refuse(msg, "view: a chunk of %lld bytes (at most %lld)", (long long)n_bytes, WG_VIEW_MAX_CHUNK);
+    if (n_records + wg_view_chunk_records(n_bytes) > WG_VIEW_MAX_RECORDS) {
+        (void)wg_plan_refuse(msg, "view: more than %lld reads selected", WG_VIEW_MAX_RECORDS);
+        return WGBSSEG_E_CAPACITY;
+    }
+    return WGBSSEG_OK;
+}
+
+// The sort of n records: runs of WG_VIEW_RUN indices sorted in LDS, then merge passes that double the run length until one run is left.
+inline int64_t wg_view_runs(int64_t n) { return (n + WG_VIEW_RUN - 1) / WG_VIEW_RUN; }
+inline int wg_view_merge_passes(int64_t n)
+{
+    int passes = 0;
+    for (int64_t runs = wg_view_runs(n); runs > 1; runs = (runs + 1) / 2) passes++;
+    return passes;
+}
+
+// the fetch of [offset, offset + len) in slabs of WG_VIEW_SLAB bytes: how many, and slab k's bytes
+inline int64_t wg_view_slabs(int64_t len) { return (len + WG_VIEW_SLAB - 1) / WG_VIEW_SLAB; }
+inline int64_t wg_view_slab_len(int64_t len, int64_t k) { return std::min<int64_t>(WG_VIEW_SLAB, len - k * WG_VIEW_SLAB); }
+
+inline int plan_view_read(int64_t offset, int64_t len, int64_t total, const void* buf, std::string& msg)
+{
+    if (offset < 0 || len < 0 || offset + len > total || (len && !buf))
+        return wg_plan_refuse(msg, "view: read of [%lld, %lld) from %lld bytes of output", (long long)offset, (long long)(offset + len), (long long)total);
+    return WGBSSEG_OK;
+}

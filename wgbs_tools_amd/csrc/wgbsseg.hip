@@ -40,6 +40,7 @@
 #include "pat_kernels.h"
 #include "homog_kernels.h"
 #include "frag_kernels.h"
+#include "view_kernels.h"
 #include "bimodal_kernels.h"
 #include "inflate_plan.h"
 #include "inflate_kernels.h"
@@ -2452,7 +2453,7 @@ int64_t wgbsseg_format_fixed(const double* v, int64_t n, int32_t digits, char* o
 
 }  // extern "C"
 
-#include "pat_engines.h"      // the engines that take pat text in chunks (pat2beta, homog, frag_len, test_bimodal) and their entry points
+#include "pat_engines.h"      // the engines that take pat text in chunks (pat2beta, homog, frag_len, test_bimodal, view) and their entry points
 
 // what is left of the segmenter context's calls: its timings and the wgbsseg_debug_* views of its buffers and arithmetic
 extern "C" {

@@ -6,17 +6,20 @@ reads' U / X / M counts over those blocks), `test_bimodal` (the per-block two-al
 `beta_cov` / `beta_stats` (the per-sample coverage and methylation summary read before choosing what goes into `segment`),
 `compare_betas` (the 2-D histogram of every pair of those files: which samples agree), `beta2bed` (a file's sites as BED
 text, formatted on the device), `beta_to_450k` (the files' values at the Illumina 450K / EPIC probes as one CSV table, gathered
-and formatted on the device) and `frag_len` (the histogram of a pat file's read lengths in CpGs: what `homog -l` is chosen from);
-every other reference subcommand is out of scope and says so."""
+and formatted on the device), `frag_len` (the histogram of a pat file's read lengths in CpGs: what `homog -l` is chosen from) and
+`view` / `cview` (a pat file's reads as pat text: filtered by an interval, cut, sorted and collapsed on the device; both names run
+view.main); every other reference subcommand is out of scope and says so."""
 import sys
 
 from .genome import IllegalArgumentError, eprint
 
 VERSION = '0.2.0-mi355x'
 COMMANDS = ['segment', 'convert', 'pat2beta', 'beta_to_blocks', 'beta_to_table', 'find_markers', 'homog', 'test_bimodal',
-            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k', 'frag_len']
-# reference command list (wgbs_tools.py:11-48), for the "not in this build" message
-REFERENCE_ONLY = ['view', 'merge', 'cview', 'index',
+            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k', 'frag_len', 'view', 'cview']
+MODULES = {'cview': 'view'}            # commands that run another command's module
+# reference command list (wgbs_tools.py:11-48), for the "not in this build" message.  `view` is in both lists: COMMANDS is looked at first and
+# carries its pat side; of a .beta / .lbeta input view.py itself says that it is not part of this build (and names `beta2bed`)
+REFERENCE_ONLY = ['view', 'merge', 'index',
                   'beta2bw', 'bam2pat', 'mbias', 'init_genome', 'set_default_ref', 'vis', 'pat_fig',
                   'dmb', 'mix_pat', 'bed2beta',
                   'split_by_allele', 'split_by_meth', 'add_cpg_counts']
@@ -61,7 +64,7 @@ def main(argv=None):
         print('wgbstools (MI355X segment) version', VERSION)
         return 0
     cmd = argv[1]
-    if cmd in REFERENCE_ONLY:
+    if cmd in REFERENCE_ONLY and cmd not in COMMANDS:
         eprint(f'wgbstools {cmd}: not part of this build (it carries the MI355X-native `segment`, `convert`, `beta_to_blocks`, `beta_to_table`)')
         return 1
     if cmd not in COMMANDS:
@@ -73,9 +76,9 @@ def main(argv=None):
         if inflate is not None:                # where the BGZF pat.gz is inflated: the other pat commands have the option themselves
             from .pat2beta import default_inflate
             with default_inflate(inflate):
-                importlib.import_module('.' + cmd, __package__).main(args)
+                importlib.import_module('.' + MODULES.get(cmd, cmd), __package__).main(args)
             return 0
-        importlib.import_module('.' + cmd, __package__).main(args)
+        importlib.import_module('.' + MODULES.get(cmd, cmd), __package__).main(args)
         return 0
     except IllegalArgumentError as e:          # wgbs_tools.py:77-79
         eprint(f'Invalid input argument\n{e}')
