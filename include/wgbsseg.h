@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 320            /* 0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 330            /* 0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -325,6 +325,20 @@ typedef struct {
 } wgbsseg_sample_stat;
 int wgbsseg_sample_stats(wgbsseg_ctx* ctx, const int64_t* start0, const int64_t* end0, int64_t n_ranges, int32_t depth_at,
                          wgbsseg_sample_stat* out, char* err, size_t errlen);
+
+/*
+ * The sum of resident rows, site by site, with the saturation rule of `wgbstools merge` (merge.py:123-140 merge_betas,
+ * utils_wgbs.py:277-290 trim_to_uint8).  samples: n_samples >= 1 indexes of resident rows (at most 65,536; a row may be named twice).
+ * Per site M = the sum of meth and C = the sum of cov, exact integers; with max = 255 (65535 when lbeta_out is not 0): where C > max,
+ * M = (int64)trunc(fl(fl((double)M / (double)C) * (double)max)) — two IEEE double operations, then the C cast — and C = max; then both
+ * wrap to the width of the result (uint8, or uint16 when lbeta_out), as numpy's astype does: meth > cov in the input is not checked.
+ * Works on uint8 rows (wgbsseg_set_betas_*, borrowed rows included: nothing beyond 2 * n_sites bytes of a row is read) and uint16 rows
+ * (wgbsseg_set_lbetas_host).  out is a HOST buffer of n_sites x 2 uint8, or uint16 when lbeta_out.  Refused with WGBSSEG_E_ARG:
+ * n_samples < 1 or > 65,536, an index that names no resident row, out == NULL.  wgbsseg_last_merge_rows_ms: the HIP-event time of the
+ * kernel of the last call (ms).
+ */
+int wgbsseg_merge_rows(wgbsseg_ctx* ctx, const int32_t* samples, int32_t n_samples, int32_t lbeta_out, void* out, char* err, size_t errlen);
+double wgbsseg_last_merge_rows_ms(const wgbsseg_ctx* ctx);
 
 /*
  * Pairwise 2-D histograms of the resident samples — what `wgbstools compare_betas` draws per pair of files
@@ -709,6 +723,17 @@ double wgbsseg_fraglen_inflate_ms(wgbsseg_fraglen* h);
  * kernel_ms / inflate_ms: device time of the chunk launches / inflate launches so far; phase_ms: of finish()'s sort, collapse + emit
  * and deflate.  info(): out[6] = records kept, arena bytes, growths of the record table, growths of the arena, merge passes run,
  * order (0: no sort asked, 1: found in order, no sort run, 2: sorted).
+ *
+ * Several files in one view (`wgbstools merge`): next_file() between the feeds of two files.  It feeds a last line that has no newline
+ * as finish() does, refuses (WGBSSEG_E_ARG) BGZF bytes that the last feed_bgzf() left over — they are no whole member —, and makes the
+ * feed forget the file: text or BGZF may change from file to file, member offsets count from 0 again, and the next file may begin
+ * below where this one ended (reads ascend inside a file, not across files).  The records of all files share the one table in input
+ * order, so finish() sorts and collapses them together and ties still break by (file, line).  After a next_file() call finish() names
+ * the file (0-based, in feed order) and the byte offset inside it: "failed in view: file K: invalid line at byte offset N of the file
+ * ...", "... file K: the pat file is not sorted: the read at byte offset N of the file ...", and it refuses a count below 1 in any
+ * line, "failed in view: file K: count < 1 at byte N" — the reference collapses every file by itself before it merges them, so a run
+ * whose sum is <= 0 vanishes there while it would be summed into the other files' runs here; with counts of at least 1 the two agree.
+ * Without a next_file() call everything is as described above.  WGBSSEG_E_STATE after finish().
  */
 #define WGBSSEG_VIEW_STRICT 1
 #define WGBSSEG_VIEW_STRIP 2
@@ -726,6 +751,7 @@ double wgbsseg_patview_kernel_ms(wgbsseg_patview* v);
 double wgbsseg_patview_inflate_ms(wgbsseg_patview* v);
 void wgbsseg_patview_phase_ms(const wgbsseg_patview* v, double* sort_ms, double* emit_ms, double* deflate_ms);
 void wgbsseg_patview_info(const wgbsseg_patview* v, int64_t* out);
+int wgbsseg_patview_next_file(wgbsseg_patview* v, char* err, size_t errlen);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 320          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 330          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -50,7 +50,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_fraglen_kernel_ms', 'wgbsseg_fraglen_inflate_ms',
            'wgbsseg_bgzf_deflate', 'wgbsseg_bgzf_deflate_bound', 'wgbsseg_beta2bed_bgzf', 'wgbsseg_bgzf_deflate_ms', 'wgbsseg_bgzf_deflate_pass_ms',
            'wgbsseg_patview_create', 'wgbsseg_patview_feed', 'wgbsseg_patview_feed_bgzf', 'wgbsseg_patview_finish', 'wgbsseg_patview_read',
-           'wgbsseg_patview_destroy', 'wgbsseg_patview_kernel_ms', 'wgbsseg_patview_inflate_ms', 'wgbsseg_patview_phase_ms', 'wgbsseg_patview_info']
+           'wgbsseg_patview_destroy', 'wgbsseg_patview_kernel_ms', 'wgbsseg_patview_inflate_ms', 'wgbsseg_patview_phase_ms', 'wgbsseg_patview_info',
+           'wgbsseg_patview_next_file', 'wgbsseg_merge_rows', 'wgbsseg_last_merge_rows_ms']
 
 
 class NativeLibraryError(RuntimeError):
@@ -324,6 +325,12 @@ def load():
     L.wgbsseg_patview_phase_ms.argtypes = [vp, vp, vp, vp]
     L.wgbsseg_patview_info.restype = None
     L.wgbsseg_patview_info.argtypes = [vp, vp]
+    L.wgbsseg_patview_next_file.restype = i32
+    L.wgbsseg_patview_next_file.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_merge_rows.restype = i32
+    L.wgbsseg_merge_rows.argtypes = [vp, vp, i32, i32, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_last_merge_rows_ms.restype = C.c_double
+    L.wgbsseg_last_merge_rows_ms.argtypes = [vp]
     for eng in ('patbeta', 'homog', 'bimodal', 'fraglen', 'patview'):
         f = getattr(L, 'wgbsseg_%s_feed_bgzf' % eng)
         f.restype = i32
@@ -553,6 +560,18 @@ class Segmenter:
         _check(self._L.wgbsseg_sample_stats(self._h, s.ctypes.data, e.ctypes.data, s.size, int(depth_at), out.ctypes.data,
                                             self._err, ERRLEN), self._err)
         return out
+
+    def merge_rows(self, samples, lbeta=False):
+        """wgbsseg_merge_rows: the sum of the resident rows `samples` (indexes; a row may be named twice), saturated as `wgbstools merge`
+        saturates -> uint8 [n_sites, 2], or uint16 with lbeta=True.  last_merge_rows_ms(): the kernel's HIP-event time."""
+        idx = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1)
+        out = np.empty((self.n_sites, 2), dtype=np.uint16 if lbeta else np.uint8)
+        _check(self._L.wgbsseg_merge_rows(self._h, idx.ctypes.data if idx.size else None, idx.size, 1 if lbeta else 0, out.ctypes.data,
+                                          self._err, ERRLEN), self._err)
+        return out
+
+    def last_merge_rows_ms(self):
+        return float(self._L.wgbsseg_last_merge_rows_ms(self._h))
 
     @staticmethod
     def _pair_columns(pairs):
@@ -864,6 +883,11 @@ class PatView(_PatFeed):
         """the result in pieces of at most `piece` bytes"""
         for at in range(0, self.n_bytes, piece):
             yield self.read(at, min(piece, self.n_bytes - at))
+
+    def next_file(self):
+        """between the feeds of two files: the file ends here (a last line without its newline is fed), the next one may be text or
+        BGZF and may begin below where this one ended; finish() then names the file of a refused line and refuses counts below 1"""
+        self._call('next_file', self._h)
 
     def phase_ms(self):
         """(sort, collapse + emit, deflate) of finish(), HIP-event milliseconds"""

@@ -876,7 +876,9 @@ struct wgbsseg_patview {
     enum { SORT = 0, EMIT = 1, DEFLATE = 2 };
     PatFeed feed;
     ViewPlan plan;
-    DevBuf recs, arena, tiles, totals, state, prev;              // state: bad, desc (8 bytes each), unsorted, too_big (4 bytes each)
+    DevBuf recs, arena, tiles, totals, state, prev;              // state: bad, desc (8 bytes each), unsorted, too_big (4 bytes each), low (8 bytes)
+    ViewFiles files;                                              // the boundaries next_file() has recorded (view_plan.h)
+    int64_t bgzf_left = 0;                                        // bytes the last feed_bgzf did not take
     DevBuf perm[2], head, wg, run_end, run_tail, run_sum, text, slots, meta, dense;
     PinnedBuf host_tot, fetch;
     int64_t cap_recs = 0, cap_arena = 0;                          // what recs / arena have room for
@@ -956,7 +958,7 @@ static int view_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& s
     HIP_TRY(hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, f.st));
     HIP_TRY(f.span_begin());
     hipLaunchKernelGGL(k_view_measure, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), tile_recs, tile_bytes,
-                       v->state.as<unsigned long long>(), v->state.as<unsigned long long>() + 1, in, out, f.fed);
+                       v->state.as<unsigned long long>(), v->state.as<unsigned long long>() + 1, v->state.as<unsigned long long>() + 3, in, out, f.fed);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_recs, tile_bytes, gx, rec_base, tot);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_bytes, tile_bytes, gx, arena_base, tot + 2);
     hipLaunchKernelGGL(k_view_pack, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), rec_base, arena_base,
@@ -1093,7 +1095,7 @@ int wgbsseg_patview_create(int device, int64_t start_cpg, int64_t end_cpg, int32
     if (rc != WGBSSEG_OK) return rc;
     v->plan = plan;
     for (auto& p : v->ph) for (auto& e : p) HIP_TRY(e.create());
-    HIP_TRY(v->totals.ensure(32)); HIP_TRY(v->state.ensure(24)); HIP_TRY(v->prev.ensure(16));
+    HIP_TRY(v->totals.ensure(32)); HIP_TRY(v->state.ensure(32)); HIP_TRY(v->prev.ensure(16));
     if (!v->host_tot.ensure(16)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
     rc = view_reserve(v.get(), plan.initial_records, plan.initial_records * 16, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
@@ -1101,6 +1103,7 @@ int wgbsseg_patview_create(int device, int64_t start_cpg, int64_t end_cpg, int32
     HIP_TRY(hipMemcpy(v->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(v->state.p, 0xff, 16, v->feed.st));
     HIP_TRY(hipMemsetAsync(v->state.as<char>() + 16, 0, 8, v->feed.st));
+    HIP_TRY(hipMemsetAsync(v->state.as<char>() + 24, 0xff, 8, v->feed.st));
     *out = v.release();
     return WGBSSEG_OK;
 }
@@ -1114,7 +1117,32 @@ int wgbsseg_patview_feed(wgbsseg_patview* v, const char* text, int64_t n_bytes, 
 
 int wgbsseg_patview_feed_bgzf(wgbsseg_patview* v, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
-    return PatFeed::feed_bgzf("patview", v, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
+    const int rc = PatFeed::feed_bgzf("patview", v, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
+    if (rc == WGBSSEG_OK) v->bgzf_left = n_bytes - *consumed;
+    return rc;
+}
+
+// Between the feeds of two files: the carry (a last line without its newline) is fed as finish() feeds it; BGZF bytes left over are refused;
+// the feed forgets the file — text or BGZF, the member offset, the read before — and the boundary goes into the host table.  What the
+// files left in the record table and the arena stays: finish() sorts and collapses the records of all files, ties in input order.
+int wgbsseg_patview_next_file(wgbsseg_patview* v, char* err, size_t errlen)
+{
+    if (!v) { set_err(err, errlen, "bad arguments to patview_next_file"); return WGBSSEG_E_ARG; }
+    std::string msg;
+    int rc = plan_view_next_file(v->finished, v->bgzf_left, v->files.open_file(), msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    PatFeed& f = v->feed;
+    HIP_TRY(hipSetDevice(f.device));
+    rc = f.flush_carry("patview", [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); }, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    rc = view_take_totals(v, err, errlen);                         // (waits for the stream: the records of the file are counted)
+    if (rc != WGBSSEG_OK) return rc;
+    const long long none[2] = {WG_PAT_NO_SITE, WG_PAT_NO_SITE};    // the next file may begin below where this one ended
+    HIP_TRY(hipMemcpy(v->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    f.mode = 0; f.file_off = 0; f.carry.clear();
+    v->bgzf_left = 0;
+    v->files.close((int64_t)f.fed, v->n_recs);
+    return WGBSSEG_OK;
 }
 
 // the carry; a refused BGZF member before a malformed line before a descending read; then sort, collapse, emit and (deflate) the BGZF form
@@ -1128,12 +1156,19 @@ int wgbsseg_patview_finish(wgbsseg_patview* v, int64_t* n_lines, int64_t* n_byte
     int rc = v->feed.flush_carry("patview", [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); }, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     v->finished = true;
-    unsigned long long refused[2] = {0, 0};
+    unsigned long long refused[2] = {0, 0}, low = 0;
     HIP_TRY(hipMemcpyAsync(refused, v->state.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&low, v->state.as<unsigned long long>() + 3, 8, hipMemcpyDeviceToHost, st));
     rc = view_take_totals(v, err, errlen);                         // (waits for the stream)
     if (rc != WGBSSEG_OK) return rc;
     rc = v->feed.inflate_refused(err, errlen);
     if (rc != WGBSSEG_OK) return rc;
+    if (v->files.several()) {                                      // several files: the file and the offset inside it; a count below 1 is refused
+        const ViewRefusal why[3] = {ViewRefusal::bad_line, ViewRefusal::unsorted, ViewRefusal::low_count};
+        const unsigned long long at[3] = {refused[0], refused[1], low};
+        for (int k = 0; k < 3; k++)
+            if (at[k] != ~0ULL) { set_err(err, errlen, "%s", wg_view_file_refusal(v->files, why[k], at[k]).c_str()); return WGBSSEG_E_ARG; }
+    }
     if (refused[0] != ~0ULL) {
         set_err(err, errlen, "failed in view: invalid line at byte offset %llu of the input (too few columns, a site / count that is not a number, an empty pattern, or something between the count and the end of the line)", refused[0]);
         return WGBSSEG_E_ARG;

@@ -1,6 +1,6 @@
-// row_engines.h — the calls that work on the context's resident rows (wgbsseg_block_sums, _marker_stats, _sample_stats, _pair_ranges,
+// row_engines.h — the calls that work on the context's resident rows (wgbsseg_block_sums, _marker_stats, _sample_stats, _merge_rows, _pair_ranges,
 // _pair_hist, _beta2bed, _convert_regions, _site_counts, _site_table), the helpers they share and their extern "C" entry points.  Part of wgbsseg.hip, which includes
-// it once set_err, HIP_TRY, the owners and the context are in scope; what a call decides on the host is in block_plan.h, stats_plan.h,
+// it once set_err, HIP_TRY, the owners and the context are in scope; what a call decides on the host is in block_plan.h, stats_plan.h, merge_plan.h,
 // pair_plan.h, bed_plan.h and array_plan.h, this file stages, launches and fetches.
 #pragma once
 
@@ -190,6 +190,48 @@ int wgbsseg_sample_stats(wgbsseg_ctx* c, const int64_t* start0, const int64_t* e
     HIP_TRY(clock.end({{out, dout, sizeof(*out) * (size_t)c->n_samples}}));
     return WGBSSEG_OK;
 }
+
+// plan (merge_plan.h) -> the row list up -> one launch -> the summed row home in slabs through the two page-locked text buffers of beta2bed:
+// while the host copies slab k out of one, slab k+1 arrives in the other
+int wgbsseg_merge_rows(wgbsseg_ctx* c, const int32_t* samples, int32_t n_samples, int32_t lbeta_out, void* out, char* err, size_t errlen)
+{
+    if (const int rc = need_rows(c, err, errlen)) return rc;
+    MergePlan p;
+    std::string msg;
+    const int rc = plan_merge_rows(samples, n_samples, c->n_samples, c->n_total, c->elem, lbeta_out, out, p, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(c->mg_samples.ensure((size_t)n_samples * 4));
+    HIP_TRY(c->mg_out.ensure((size_t)p.out_bytes));
+    const size_t slab = (size_t)wg_merge_slab_len(p.out_bytes, 0);
+    for (auto& h : c->bed.home) if (!h.ensure(slab)) { set_err(err, errlen, "merge_rows: out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    HIP_TRY(hipMemcpyAsync(c->mg_samples.p, samples, (size_t)n_samples * 4, hipMemcpyHostToDevice, c->sA));
+    HIP_TRY(hipEventRecord(c->ev[0], c->sA));
+    const dim3 grid((unsigned)p.groups), block(WG_MG_BLOCK);
+    by_elem(c->elem, [&](auto E) {
+        constexpr int ELEM = decltype(E)::value;
+        const auto k = lbeta_out ? k_beta_merge<ELEM, 2> : k_beta_merge<ELEM, 1>;
+        hipLaunchKernelGGL(k, grid, block, 0, c->sA, c->betas, c->pitch, c->n_total, c->mg_samples.as<const int32_t>(), n_samples, p.n_vec, c->mg_out.as<uint8_t>());
+    });
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c->ev[1], c->sA));
+    const int64_t n_slabs = wg_merge_slabs(p.out_bytes);
+    const auto fetch = [&](int64_t k) {
+        return hipMemcpyAsync(c->bed.home[k & 1].p, c->mg_out.as<uint8_t>() + k * WG_MG_SLAB, (size_t)wg_merge_slab_len(p.out_bytes, k), hipMemcpyDeviceToHost, c->sA);
+    };
+    HIP_TRY(fetch(0));
+    for (int64_t k = 0; k < n_slabs; k++) {
+        HIP_TRY(hipStreamSynchronize(c->sA));
+        if (k + 1 < n_slabs) HIP_TRY(fetch(k + 1));
+        memcpy(static_cast<uint8_t*>(out) + k * WG_MG_SLAB, c->bed.home[k & 1].p, (size_t)wg_merge_slab_len(p.out_bytes, k));
+    }
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    c->last_merge_rows_ms = ms;
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_last_merge_rows_ms(const wgbsseg_ctx* c) { return c ? c->last_merge_rows_ms : 0.0; }
 
 static_assert(sizeof(wgbsseg_pair_range) == sizeof(wg_pair_range) && sizeof(wg_pair_range) == 40, "wgbsseg_pair_range is the kernels' wg_pair_range");
 

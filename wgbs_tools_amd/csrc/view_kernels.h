@@ -9,8 +9,9 @@
 // with a single block) — provided the reads do ascend, which k_view_measure checks always, the whole genome included.
 //
 // Per fed chunk (one workgroup per 4 KB tile of text, one line per thread, as k_pat_count):
-//   k_view_measure   parses the tile's lines, applies the cut rule, reports the lowest malformed (`bad`) and descending (`desc`) line,
-//                    and writes the tile's number of survivors and the bytes they put into the arena
+//   k_view_measure   parses the tile's lines, applies the cut rule, reports the lowest malformed (`bad`) and descending (`desc`) line and
+//                    the lowest line whose count is below 1 (`low`: finish() looks at it only for a view over several files), and
+//                    writes the tile's number of survivors and the bytes they put into the arena
 //   (k_bed_scan)     twice: the tiles' first record and first arena byte in the chunk
 //   k_view_pack      parses again and writes every survivor's record and bytes (chromosome, cut pattern) at tile offset + prefix inside
 //                    the tile: input order, no atomics — the unsorted modes and the tie-break of the sort rest on it
@@ -89,7 +90,7 @@ __device__ __forceinline__ uint64_t wg_view_block_incl_u64(uint64_t v, uint64_t*
 
 __global__ __launch_bounds__(WG_BLOCK) void k_view_measure(const char* __restrict__ text, int64_t n, wg_view_args a, uint64_t* __restrict__ tile_recs,
                                                            uint64_t* __restrict__ tile_bytes, unsigned long long* bad, unsigned long long* desc,
-                                                           const long long* prev_in, long long* prev_out, unsigned long long chunk_off)
+                                                           unsigned long long* low, const long long* prev_in, long long* prev_out, unsigned long long chunk_off)
 {
     __shared__ PatTile tile;
     __shared__ long long s_last[WG_BLOCK / 64];              // the start of every wavefront's last line in the round (WG_PAT_NO_SITE: no line / malformed)
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(WG_BLOCK) void k_view_measure(const char* __restric
             const int64_t p = base + tile.lstart[l];
             L = wg_view_eval(T, p, n, a);
             if (!L.ok) atomicMin(bad, chunk_off + (unsigned long long)p);
+            else if (L.count < 1) atomicMin(low, chunk_off + (unsigned long long)p);
         }
         const long long mine = L.ok ? (long long)L.site : WG_PAT_NO_SITE;
         long long pv = __shfl_up(mine, 1);                       // the line before: the lane below, ...

@@ -1,5 +1,6 @@
 // view_plan.h — the host plan of `wgbstools view` (wgbsseg_patview_*): the argument checks with their messages, the limits of the
-// record table and its arena, how the two grow, the sort's run length and number of merge passes, and the slabs of the fetch.  No HIP
+// record table and its arena, how the two grow, the sort's run length and number of merge passes, the slabs of the fetch, and the table
+// of file boundaries of a view over several files (`wgbstools merge`) with the messages that name a file.  No HIP
 // here (like frag_plan.h): g++ compiles it alone, tests/native/view_host.cpp hands it to the tests.
 //
 // Limits.  A record is 32 bytes (view_core.h); their number stays below 2^31, so a permutation entry is a uint32.  A survivor puts
@@ -9,7 +10,9 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <string>
+#include <vector>
 #include "block_plan.h"                // wg_plan_refuse
 #include "view_core.h"
 
@@ -67,6 +70,47 @@ inline int wg_view_merge_passes(int64_t n)
     int passes = 0;
     for (int64_t runs = wg_view_runs(n); runs > 1; runs = (runs + 1) / 2) passes++;
     return passes;
+}
+
+// The files of a view over several (wgbsseg_patview_next_file): a host table of the boundaries.  end_bytes[k] / end_recs[k]: the bytes fed /
+// the records kept when file k ended, counted over all files — the kernels keep their global byte offsets, and locate() turns one into
+// (file, offset inside it) for a message.  The last file has no entry: it is open until finish().
+struct ViewFiles {
+    std::vector<int64_t> end_bytes, end_recs;
+    bool several() const { return !end_bytes.empty(); }
+    int64_t open_file() const { return (int64_t)end_bytes.size(); }      // the 0-based index of the file being fed
+    void close(int64_t bytes, int64_t recs) { end_bytes.push_back(bytes); end_recs.push_back(recs); }
+    // a file that ends at `bytes` holds the offsets below it: an offset belongs to the first file whose end lies beyond it
+    void locate(uint64_t off, int64_t& file, uint64_t& inside) const
+    {
+        file = (int64_t)(std::upper_bound(end_bytes.begin(), end_bytes.end(), (int64_t)off) - end_bytes.begin());
+        inside = off - (file ? (uint64_t)end_bytes[(size_t)file - 1] : 0u);
+    }
+};
+
+// next_file(): `left` BGZF bytes that the last feed_bgzf did not take are the beginning of a member the file does not finish
+inline int plan_view_next_file(bool finished, int64_t left, int64_t file, std::string& msg)
+{
+    if (finished) { (void)wg_plan_refuse(msg, "patview_next_file: finish() has been called"); return WGBSSEG_E_STATE; }
+    if (left > 0) return wg_plan_refuse(msg, "failed in view: file %lld: truncated (%lld bytes behind its last whole BGZF member)", (long long)file, (long long)left);
+    return WGBSSEG_OK;
+}
+
+// What finish() says of a refused line once next_file() has been called: the file (0-based, in feed order) and the byte offset inside it.
+enum class ViewRefusal { bad_line, unsorted, low_count };
+inline std::string wg_view_file_refusal(const ViewFiles& files, ViewRefusal why, uint64_t off)
+{
+    int64_t file = 0;
+    uint64_t inside = 0;
+    files.locate(off, file, inside);
+    char buf[320];
+    if (why == ViewRefusal::bad_line)
+        snprintf(buf, sizeof buf, "failed in view: file %lld: invalid line at byte offset %llu of the file (too few columns, a site / count that is not a number, an empty pattern, or something between the count and the end of the line)", (long long)file, (unsigned long long)inside);
+    else if (why == ViewRefusal::unsorted)
+        snprintf(buf, sizeof buf, "failed in view: file %lld: the pat file is not sorted: the read at byte offset %llu of the file starts before the read before it", (long long)file, (unsigned long long)inside);
+    else
+        snprintf(buf, sizeof buf, "failed in view: file %lld: count < 1 at byte %llu", (long long)file, (unsigned long long)inside);
+    return buf;
 }
 
 // the fetch of [offset, offset + len) in slabs of WG_VIEW_SLAB bytes: how many, and slab k's bytes

@@ -47,6 +47,7 @@
 #include "deflate_plan.h"
 #include "deflate_kernels.h"
 #include "stats_kernels.h"
+#include "merge_kernels.h"
 #include "pair_kernels.h"
 #include "bed_kernels.h"
 #include "array_kernels.h"
@@ -173,6 +174,8 @@ struct wgbsseg_ctx {
     DevBuf bs_plan, bs_desc, bs_out;   // wgbsseg_block_sums: the plan's tables (block_plan.h) | the streaming kernel's block descriptors | the result
     DevBuf mk_out, cv_in, cv_out;      // wgbsseg_marker_stats: the statistics and the two sample lists; wgbsseg_convert_regions: the regions' columns | their CpG ranges
     DevBuf st_ranges, st_parts;     // wgbsseg_sample_stats: the range table | the tiles' partial results and the per-sample results
+    DevBuf mg_samples, mg_out;      // wgbsseg_merge_rows: the rows named | the summed row
+    double last_merge_rows_ms = 0.0;
     DevBuf ph_pairs, ph_edges, ph_out;   // wgbsseg_pair_ranges / _pair_hist: the pair list (a | b) | the edges | the ranges or the counts
     BedScratch bed;                      // wgbsseg_beta2bed
     SiteScratch site;                    // wgbsseg_site_counts, wgbsseg_site_table

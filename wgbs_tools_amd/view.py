@@ -26,7 +26,8 @@ src/collapse_pat.pl):
 
 The file's text — inflated on the host or, with `--inflate device`, on the GPU — goes through the feed the other pat commands share;
 the survivors stay on the device, where they are sorted, collapsed and written out (wgbsseg_patview_*, include/wgbsseg.h,
-csrc/view_kernels.h).  No CPU fallback.
+csrc/view_kernels.h).  No CPU fallback.  view_pats() is the same over several files — one engine, wgbsseg_patview_next_file between two
+files, the reads of all of them sorted and collapsed together — and what `wgbstools merge` (merge.py) runs; view_pat() is view_pats() of one.
 
 Deliberate deviations from the reference:
   1. No index and no tabix window: the whole file is read.  A read that starts more than 150 sites before s and still reaches it is
@@ -68,25 +69,52 @@ def check_interval(s, e, min_len=1):
         raise IllegalArgumentError(f'view: the interval [{s}, {e}) is empty')
 
 
-def view_pat(pat, s, e, sink, strict=False, strip=False, no_gaps=False, min_len=1, sort=True, device=0, inflate='host', deflate=False,
-             initial_records=0, timings=None):
-    """the view of one pat file over [s, e): every piece of the result to sink(bytes) -> (lines, bytes)"""
+def view_pats(pats, s, e, sink, strict=False, strip=False, no_gaps=False, min_len=1, sort=True, device=0, inflate='host', deflate=False,
+              initial_records=0, timings=None):
+    """the view of the reads of several pat files over [s, e) as if they were one file's (what `merge` is): every file is fed to ONE
+    engine, next_file() between two of them; every piece of the result to sink(bytes) -> (lines, bytes).  A refusal of the engine
+    names the file by its index in `pats` (from 0) once there is more than one; the message here adds its path in front."""
     from . import _lib
     check_interval(s, e, min_len)
     t = timings if timings is not None else {}
+    spent = {}
+    at = 0
     try:
         with _lib.PatView(s, e, strict=strict, strip=strip, no_gaps=no_gaps, sort=sort, min_len=min_len, device=device,
                           initial_records=initial_records) as v:
-            feed_pat(v, pat, t, inflate=inflate)
+            for at, pat in enumerate(pats):
+                if at:
+                    v.next_file()
+                one = {}
+                feed_pat(v, pat, one, inflate=inflate)
+                for key, val in one.items():                     # (inflate_ms is the engine's running total)
+                    spent[key] = val if key == 'inflate_ms' else spent.get(key, 0.0) + val
+            at = None
             lines, nbytes = v.finish(deflate=deflate)
+            t.update(spent)
             t['kernel_ms'] = v.kernel_ms()
             t['sort_ms'], t['emit_ms'], t['deflate_ms'] = v.phase_ms()
             t.update(v.info())
             for piece in v.chunks():
                 sink(piece)
     except _lib.SegmentorError as err:
-        raise IllegalArgumentError(f'{pat}: {err.msg}')
+        where = pats[at] if at is not None else _refused_file(pats, err.msg)
+        raise IllegalArgumentError(f'{where}: {err.msg}')
     return lines, nbytes
+
+
+def _refused_file(pats, msg):
+    """the path finish()'s message is about: `file K:` names it when several files were fed"""
+    import re
+    m = re.search(r'\bfile (\d+):', msg) if len(pats) > 1 else None
+    return pats[int(m.group(1))] if m and int(m.group(1)) < len(pats) else pats[0] if len(pats) == 1 else ', '.join(pats)
+
+
+def view_pat(pat, s, e, sink, strict=False, strip=False, no_gaps=False, min_len=1, sort=True, device=0, inflate='host', deflate=False,
+             initial_records=0, timings=None):
+    """the view of one pat file over [s, e): every piece of the result to sink(bytes) -> (lines, bytes)"""
+    return view_pats([pat], s, e, sink, strict=strict, strip=strip, no_gaps=no_gaps, min_len=min_len, sort=sort, device=device, inflate=inflate,
+                     deflate=deflate, initial_records=initial_records, timings=timings)
 
 
 def _write_all(fd, data):
