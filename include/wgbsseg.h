@@ -759,11 +759,18 @@ int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
  * Test hooks (used by tests/ to compare device intermediates with the oracle; not part of the drop-in surface).
  * wgbsseg_debug_fetch copies an intermediate of the LAST wgbsseg_segment_chunks() call to a host buffer:
  *   "window"  uint16[sites]   F_k (number of admissible ends of a block starting at k)
- *   "cum"     uint32[sites]   exclusive prefix of F inside each chunk (row offset of start site k)
+ *   "cum"     uint32[sites]   exclusive prefix of F inside each chunk (row offset of start site k; chunk-relative: 0 at
+ *                             every chunk's first site)
  *   "back"    uint16[sites]   i+1-argmax_k of M[i+1]
- *   "cost"    double[pairs]   scored blocks, start-major CSR (row k = ends k .. k+F_k-1), only if the call ran as a
- *                             single stage
- * Returns the number of bytes written, or a negative code.
+ *   "cost"    double[pairs]   scored blocks, only if the call ran as a single stage (WGBSSEG_FORCE_STAGES=1 makes it so;
+ *                             WGBSSEG_E_STATE otherwise)
+ * Layout, for a call of any number of chunks: DENSE, chunk after chunk in the caller's order.  sites = the sum of the
+ * chunks' lengths, and chunk c's entries begin at the sum of the lengths before it — the padding the library keeps
+ * between the chunks' slices of its own arrays (each begins at a multiple of 8 entries) is left out.  pairs = the sum
+ * of F over all sites; chunk c's rows begin at the sum of F over the chunks before it, wherever the library placed
+ * them in its cost buffer.  Inside a chunk the rows are start-major: row k (at the chunk's "cum"[k]) holds the blocks
+ * that start at site k and end at k .. k+F_k-1.
+ * Returns the number of bytes written, or a negative code (WGBSSEG_E_CAPACITY: cap_bytes is less than that).
  * wgbsseg_debug_sample_terms evaluates the per-(block,sample) term on the device for arrays of (nmeth, ntotal).
  * wgbsseg_debug_log2 evaluates the device arithmetic for `count` consecutive float bit patterns p starting at
  * `first_bits`: out_f = uint32 bits of log2f(p); out_d = uint64 bits of the exact log2(1.0-(double)p) restatement;

@@ -196,6 +196,64 @@ def random_world(seed):
     return slices, loci, pcount, max_cpg, max_bp, chunks
 
 
+# The worlds of tests/test_gpu_parity.py's test_16 / test_17 / test_18, shared with tests/test_gpu_intermediates.py (which compares the scored
+# blocks and back-pointers on them, not only the borders).  The order of the draws is part of the worlds: do not rearrange.
+MEDIUM_WORLD_CHUNKS = [(0, 3000), (1999, 1203), (2005, 700), (4103, 1531), (8000, 1000), (8737, 263), (5, 253)]
+LEAN_WORLD_CHUNKS = [(0, 9000), (37, 9003), (4096 + 32, 8000), (9000, 11000), (14000, 3000), (123, 700)]
+LEAN_WORLD_PARAMS = [(15.0, 1000, 2000), (15.0, 200, 2000), (1.0, 100, 1200), (0.5, 1000, 900), (15.0, 65, 2000)]
+
+
+def medium_tile_world(n_samples, cov_mode):
+    """9000 dense sites (~2 bp apart: max_bp decides nothing), counts saturated ('sat') or mixed -> (slices, loci)"""
+    rng = np.random.default_rng(1600 + n_samples)
+    n = 9000
+    loci = (np.cumsum(rng.integers(1, 4, n)) + 5000).astype(np.uint32)              # ~2 bp apart: max_bp decides nothing below
+    slices = []
+    for _ in range(n_samples):
+        if cov_mode == 'sat':
+            cov = np.full(n, 255)
+            meth = np.where(rng.random(n) < 0.5, 255, 0)
+            meth[2000:2600] = 255                                               # 600 saturated sites in a row
+        else:
+            cov = rng.integers(0, 256, n)
+            cov[rng.random(n) < 0.1] = 0
+            meth = np.minimum(cov, rng.integers(0, 256, n))
+        slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
+    return slices, loci
+
+
+def lean_step_world():
+    """20,000 sites: open sea (windows ~20), an island every 900 sites, one very dense stretch; 3 samples -> (slices, loci)"""
+    rng = np.random.default_rng(1717)
+    n = 20000
+    gap = np.full(n, 100)
+    for a in range(300, n - 700, 900):                       # an island every 900 sites, 80 .. 500 sites long, 4 .. 12 bp apart
+        ln = int(rng.integers(80, 500))
+        gap[a:a + ln] = rng.integers(4, 13)
+    gap[15000:15600] = 2                                     # and one stretch dense enough for windows of several hundred sites
+    loci = (np.cumsum(gap) + 1000).astype(np.uint32)
+    slices = []
+    for _ in range(3):
+        cov = rng.integers(0, 60, n)
+        lvl = np.repeat(rng.random(n // 40 + 1), 40)[:n]
+        meth = rng.binomial(cov, lvl)
+        slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
+    return slices, loci
+
+
+def carry_world(n):
+    """n dense sites (~2 bp apart), 2 samples with a tenth of the sites uncovered -> (slices, loci)"""
+    rng = np.random.default_rng(1800)
+    loci = (np.cumsum(rng.integers(1, 4, n)) + 5000).astype(np.uint32)
+    slices = []
+    for _ in range(2):
+        cov = rng.integers(0, 256, n)
+        cov[rng.random(n) < 0.1] = 0
+        meth = np.minimum(cov, rng.integers(0, 256, n))
+        slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
+    return slices, loci
+
+
 def lbeta_twin(data):
     """uint16 [n, 2] twin of a uint8 beta array for the .lbeta-input cases: (meth, cov) of site i times k(i) = 1 + (i * 2654435761 mod 997)
     (<= 54 * 997 < 65536; keeps meth <= cov)."""

@@ -1,6 +1,12 @@
 """GPU parity tests: the HIP path (through the C ABI, libwgbsseg.so) against the oracle, the committed golden
 vectors and numpy, stage by stage so that a failure names the kernel at fault.  Bit-exact everywhere
-(integer / byte / index work, and IEEE arithmetic restated exactly — no tolerance)."""
+(integer / byte / index work, and IEEE arithmetic restated exactly — no tolerance).
+
+Most tests here compare border lists, and a border list forgives a cost that is wrong in its last bits.  The scored blocks
+(fp64 bit patterns) and the back-pointers themselves are compared with the oracle's in tests/test_gpu_intermediates.py: every
+CHUNK_CASES entry but two, every forced tile shape and division core, the worlds of test_16 / test_17 / test_18 chunk by chunk
+in their batches, every recurrence build and staging.  Borders only, still: `default_chunk` and `deep_long` (the oracle's
+debug band is ~480 MB for each) and the full-size runs (test_gpu_fullsize.py)."""
 import ctypes as C
 import os
 
@@ -8,21 +14,11 @@ import numpy as np
 import pytest
 
 import cases
+from intermediates import _first_diff, _numpy_windows
 from oracle import oracle
 from wgbs_tools_amd import _lib, synth
 
 pytestmark = pytest.mark.gpu
-
-
-def _first_diff(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    if a.shape != b.shape:
-        return 'shape %s vs %s' % (a.shape, b.shape)
-    d = np.flatnonzero(a != b)
-    if d.size == 0:
-        return None
-    i = int(d[0])
-    return '%d mismatches, first at %d: got %r want %r' % (d.size, i, a.flat[i], b.flat[i])
 
 
 @pytest.fixture(scope='module')
@@ -282,15 +278,6 @@ def test_04b_validation_pass_sees_every_site_of_every_chunk_and_nothing_else(pie
 # ---------------------------------------------------------------------------------------------------------
 # 3. window extents, scored blocks, recurrence — against the oracle's intermediates
 # ---------------------------------------------------------------------------------------------------------
-def _numpy_windows(loci, max_cpg, max_bp):
-    """forward window F_k: number of admissible ends i >= k of a block starting at k (segmentor.cpp:111-117)"""
-    l = loci.astype(np.int64)
-    k = np.arange(l.size)
-    hi = np.searchsorted(l, l + max_bp, 'right') - 1
-    hi = np.minimum(np.minimum(hi, k + max_cpg - 1), l.size - 1)
-    return (hi - k + 1).astype(np.int64)
-
-
 @pytest.mark.parametrize('name', ['tiny', 'max_cpg_binds', 'dense_w_gt_64', 'equal_loci', 'zero_stretch', 'island_mix', 'deep'])
 def test_05_intermediates_match_oracle(name, golden_chunks):
     os.environ['WGBSSEG_FORCE_STAGES'] = '1'
@@ -718,21 +705,8 @@ def test_16_medium_tiles_match_oracle_and_wide_tiles(monkeypatch, n_samples, cov
     the #meth into the #cov field, wrap at 2^32) while a block's own counts (<= 252 * 255) still fit — the case the medium tiles'
     difference-of-dwords rests on.  Chunks start off the 8-site vector grid, end inside a unit, and (40 samples) take two LDS sample
     groups.  Borders == oracle, with the medium class on, off (the wide tiles take those units), and cut at 124."""
-    rng = np.random.default_rng(1600 + n_samples)
-    n = 9000
-    loci = (np.cumsum(rng.integers(1, 4, n)) + 5000).astype(np.uint32)              # ~2 bp apart: max_bp decides nothing below
-    slices = []
-    for _ in range(n_samples):
-        if cov_mode == 'sat':
-            cov = np.full(n, 255)
-            meth = np.where(rng.random(n) < 0.5, 255, 0)
-            meth[2000:2600] = 255                                               # 600 saturated sites in a row
-        else:
-            cov = rng.integers(0, 256, n)
-            cov[rng.random(n) < 0.1] = 0
-            meth = np.minimum(cov, rng.integers(0, 256, n))
-        slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
-    chunks = [(0, 3000), (1999, 1203), (2005, 700), (4103, 1531), (8000, 1000), (8737, 263), (5, 253)]
+    slices, loci = cases.medium_tile_world(n_samples, cov_mode)
+    chunks = cases.MEDIUM_WORLD_CHUNKS
     starts, lens = [c[0] for c in chunks], [c[1] for c in chunks]
     params = [(15.0, 252), (15.0, 253), (15.0, 61), (1.0, 130), (0.25, 200), (0.0, 252), (7.77, 189), (15.0, 1000)]
     wants = [oracle.segment_chunks(slices, loci, starts, lens, pcount, max_cpg, 10**6, threads=os.cpu_count() or 1) for pcount, max_cpg in params]
@@ -754,23 +728,10 @@ def test_17_lean_step_in_the_narrow_batches_of_a_wide_job(monkeypatch):
     Worlds that alternate open sea (windows ~20), islands (windows 61 .. 250: the second register is live when narrow batches
     follow) and very dense stretches (windows > 128: the ring), at chunk offsets that put the batch boundaries on both lane halves;
     borders == oracle, and == the generic step (WGBSSEG_DP_WLEAN=0)."""
-    rng = np.random.default_rng(1717)
-    n = 20000
-    gap = np.full(n, 100)
-    for a in range(300, n - 700, 900):                       # an island every 900 sites, 80 .. 500 sites long, 4 .. 12 bp apart
-        ln = int(rng.integers(80, 500))
-        gap[a:a + ln] = rng.integers(4, 13)
-    gap[15000:15600] = 2                                     # and one stretch dense enough for windows of several hundred sites
-    loci = (np.cumsum(gap) + 1000).astype(np.uint32)
-    slices = []
-    for _ in range(3):
-        cov = rng.integers(0, 60, n)
-        lvl = np.repeat(rng.random(n // 40 + 1), 40)[:n]
-        meth = rng.binomial(cov, lvl)
-        slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
-    chunks = [(0, 9000), (37, 9003), (4096 + 32, 8000), (9000, 11000), (14000, 3000), (123, 700)]
+    slices, loci = cases.lean_step_world()
+    chunks = cases.LEAN_WORLD_CHUNKS
     starts, lens = [c[0] for c in chunks], [c[1] for c in chunks]
-    params = [(15.0, 1000, 2000), (15.0, 200, 2000), (1.0, 100, 1200), (0.5, 1000, 900), (15.0, 65, 2000)]
+    params = cases.LEAN_WORLD_PARAMS
     wants = [oracle.segment_chunks(slices, loci, starts, lens, pcount, max_cpg, max_bp, threads=os.cpu_count() or 1) for pcount, max_cpg, max_bp in params]
     for want in wants:
         assert max(int(w.size) for w in want) > 10
@@ -795,15 +756,7 @@ def test_18_carries_staged_in_lds_and_stored_directly_in_one_batch():
     """k_scan keeps the carries of a row in LDS (512 groups of 128 sites) and writes them when the row is done; a chunk of more groups
     — more than 65,000 sites — stores them from inside its loop.  One batch holds both kinds, at offsets off the vector grid, with
     windows of 300 sites (wide scoring tiles: the consumers of the carries); borders == oracle."""
-    rng = np.random.default_rng(1800)
-    n = 70400
-    loci = (np.cumsum(rng.integers(1, 4, n)) + 5000).astype(np.uint32)
-    slices = []
-    for _ in range(2):
-        cov = rng.integers(0, 256, n)
-        cov[rng.random(n) < 0.1] = 0
-        meth = np.minimum(cov, rng.integers(0, 256, n))
-        slices.append(np.stack([meth, cov], axis=1).astype(np.uint8))
+    slices, loci = cases.carry_world(70400)
     chunks = [(7, 70001), (100, 60000), (0, 65536), (129, 65409), (3, 300)]          # 548, 470, 512, 512 and 3 carry groups
     starts, lens = [c[0] for c in chunks], [c[1] for c in chunks]
     want = oracle.segment_chunks(slices, loci, starts, lens, 15.0, 300, 10**6, threads=os.cpu_count() or 1)

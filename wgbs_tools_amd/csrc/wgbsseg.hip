@@ -155,6 +155,11 @@ struct wgbsseg_ctx {
     int64_t last_sites = 0, last_pairs = 0;
     int32_t last_stages = 0;
     bool last_valid = false;
+    // the last batch's chunk table, for wgbsseg_debug_fetch: where each chunk lies in the job-site arrays (every chunk from a multiple of 8 entries on) and,
+    // for a one-stage job, in the cost buffer (first row and blocks: read back from the stage plan at the first fetch of "cost")
+    struct LastChunk { int64_t site_off; int32_t len; int64_t cost_row0, cost_rows; };
+    std::vector<LastChunk> last_chunks;
+    bool last_cost_rows_known = false;
     long long cost_budget_bytes = 0;
     int force_stages = 0;
     bool counted_live = false;
@@ -1627,6 +1632,9 @@ int Batch::timings(char* err, size_t errlen)
     T.n_stages = std::max<int32_t>(T.n_stages, n_stages); T.scan_launches += 1;
     if (plan.term_mode[0] == 2 && c->divs_enabled && c->divs_ok && c->divs_pc == P.pseudo_count) T.div_short = 1;
     c->last_sites = J; c->last_pairs = total_pairs; c->last_stages = n_stages; c->last_valid = true;
+    c->last_chunks.resize((size_t)nC);
+    for (int i = 0; i < nC; i++) c->last_chunks[(size_t)i] = {job.h[(size_t)i].site_off, job.h[(size_t)i].len, 0, 0};
+    c->last_cost_rows_known = false;
     c->batch_open = false;
     if (marks) {
         hm[7] = wall_s();
@@ -2471,18 +2479,67 @@ int wgbsseg_get_timings(const wgbsseg_ctx* c, wgbsseg_timings* out)
 int64_t wgbsseg_debug_fetch(wgbsseg_ctx* c, const char* what, void* out, int64_t cap_bytes)
 {
     if (!c || !what || !out || !c->last_valid) return WGBSSEG_E_STATE;
-    const void* src = nullptr;
-    int64_t bytes = 0;
-    if (!strcmp(what, "window")) { src = c->W16.p; bytes = c->last_sites * 2; }
-    else if (!strcmp(what, "cum")) { src = c->cum32.p; bytes = c->last_sites * 4; }
-    else if (!strcmp(what, "back")) { src = c->back16.p; bytes = c->last_sites * 2; }
-    else if (!strcmp(what, "dpstate")) { src = c->dpstate.p; bytes = c->last_dp_chunks * c->last_dp_stride * 8; }
-    else if (!strcmp(what, "cost")) { if (c->last_stages != 1) return WGBSSEG_E_STATE; src = c->cost[0].p; bytes = c->last_pairs * 8; }
-    else return WGBSSEG_E_ARG;
+    const std::vector<wgbsseg_ctx::LastChunk>& tab = c->last_chunks;
+    const DevBuf* sites = nullptr;         // one of the job-site arrays: every chunk from entry site_off (a multiple of 8) on
+    int64_t elem = 0;
+    if (!strcmp(what, "window")) { sites = &c->W16; elem = 2; }
+    else if (!strcmp(what, "cum")) { sites = &c->cum32; elem = 4; }
+    else if (!strcmp(what, "back")) { sites = &c->back16; elem = 2; }
+    if (sites) {
+        // dense: chunk after chunk in the caller's order, the padding between the chunks' slices left out
+        if (tab.empty()) return WGBSSEG_E_STATE;
+        const int64_t bytes = c->last_sites * elem;
+        const int64_t padded = (tab.back().site_off + tab.back().len) * elem;
+        if (bytes > cap_bytes) return WGBSSEG_E_CAPACITY;
+        if ((size_t)padded > sites->cap) return WGBSSEG_E_STATE;
+        if (hipSetDevice(c->device) != hipSuccess) return WGBSSEG_E_HIP;
+        if (tab.size() == 1) {
+            if (hipMemcpy(out, sites->p, (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+            return bytes;
+        }
+        std::vector<char> host((size_t)padded);
+        if (hipMemcpy(host.data(), sites->p, (size_t)padded, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+        int64_t at = 0;
+        for (const auto& ch : tab) {
+            memcpy(static_cast<char*>(out) + at, host.data() + ch.site_off * elem, (size_t)(ch.len * elem));
+            at += ch.len * elem;
+        }
+        return at == bytes ? bytes : (int64_t)WGBSSEG_E_STATE;
+    }
+    if (!strcmp(what, "dpstate")) {
+        const int64_t bytes = c->last_dp_chunks * c->last_dp_stride * 8;
+        if (bytes > cap_bytes) return WGBSSEG_E_CAPACITY;
+        if (hipSetDevice(c->device) != hipSuccess) return WGBSSEG_E_HIP;
+        if (hipMemcpy(out, c->dpstate.p, (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+        return bytes;
+    }
+    if (strcmp(what, "cost")) return WGBSSEG_E_ARG;
+    // the scored blocks of a one-stage job: the rows of chunk 0, then of chunk 1, ...; where a chunk's rows lie in the cost buffer is the stage
+    // plan's business (k_stage_plan: row 0 of plan_cbase), how many blocks it has the windows pass's (chunk_pairs)
+    if (c->last_stages != 1 || tab.empty()) return WGBSSEG_E_STATE;
+    const int64_t bytes = c->last_pairs * 8;
     if (bytes > cap_bytes) return WGBSSEG_E_CAPACITY;
     if (hipSetDevice(c->device) != hipSuccess) return WGBSSEG_E_HIP;
-    if (hipMemcpy(out, src, (size_t)bytes, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
-    return bytes;
+    if (!c->last_cost_rows_known) {
+        const size_t nC = tab.size();
+        if (nC * 8 > c->plan_cbase.cap || nC * 8 > c->chunk_pairs.cap) return WGBSSEG_E_STATE;
+        std::vector<int64_t> row0(nC), rows(nC);
+        if (hipMemcpy(row0.data(), c->plan_cbase.p, nC * 8, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+        if (hipMemcpy(rows.data(), c->chunk_pairs.p, nC * 8, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+        for (size_t i = 0; i < nC; i++) { c->last_chunks[i].cost_row0 = row0[i]; c->last_chunks[i].cost_rows = rows[i]; }
+        c->last_cost_rows_known = true;
+    }
+    int64_t at = 0;
+    for (size_t i = 0; i < tab.size();) {                        // (chunks that follow each other in the buffer come home in one copy)
+        size_t j = i;
+        int64_t run = 0;
+        while (j < tab.size() && tab[j].cost_row0 == tab[i].cost_row0 + run) { run += tab[j].cost_rows; j++; }
+        if (tab[i].cost_row0 < 0 || run < 0 || at + run > c->last_pairs || (size_t)((tab[i].cost_row0 + run) * 8) > c->cost[0].cap) return WGBSSEG_E_STATE;
+        if (run > 0 && hipMemcpy(static_cast<char*>(out) + at * 8, c->cost[0].as<double>() + tab[i].cost_row0, (size_t)run * 8, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+        at += run;
+        i = j;
+    }
+    return at == c->last_pairs ? bytes : (int64_t)WGBSSEG_E_STATE;
 }
 
 int wgbsseg_debug_sample_terms(wgbsseg_ctx* c, const float* nmeth, const float* ntotal, int64_t count, float pseudo_count, float* out)
