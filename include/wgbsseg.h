@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 330            /* 0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 340            /* 0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -734,6 +734,17 @@ double wgbsseg_fraglen_inflate_ms(wgbsseg_fraglen* h);
  * line, "failed in view: file K: count < 1 at byte N" — the reference collapses every file by itself before it merges them, so a run
  * whose sum is <= 0 vanishes there while it would be summed into the other files' runs here; with counts of at least 1 the two agree.
  * Without a next_file() call everything is as described above.  WGBSSEG_E_STATE after finish().
+ *
+ * Hidden sites (`wgbstools mask_pat`: src/pat2beta/mask_pat.cpp:12-104): set_mask() once, after create() and before the first feed() /
+ * feed_bgzf() (WGBSSEG_E_STATE otherwise).  The hidden sites are the union of the blocks [start_cpg[k], end_cpg[k]), which may come in
+ * any order and may overlap, nest and repeat; WGBSSEG_E_ARG, with the block's index in the message, for start_cpg < 1, end_cpg <=
+ * start_cpg, end_cpg >= 2^31, and for an empty list.  The blocks become a bitmap on the device, built on the feed's stream before the
+ * call returns.  Every read is then cut as above with one step between STRICT and STRIP: every pattern byte that is not '.' and whose
+ * site rs + i is hidden becomes '.' — selection looks at the read as the file has it, STRIP / min_len / NO_GAPS at the read as the mask
+ * leaves it (mask_pat itself is STRIP | SORT with min_len 1).  With a mask finish() refuses a count below 1 in a single file too,
+ * "failed in view: count < 1 at byte N", for the reason above: the reference collapses once before it masks.  mask_info(): out[3] =
+ * hidden sites (the reference's `loaded N sites`), words of the bitmap, 1 when a mask is set; mask_ms(): device time of the launch that
+ * built the bitmap.  Without a set_mask() call everything is as described above.
  */
 #define WGBSSEG_VIEW_STRICT 1
 #define WGBSSEG_VIEW_STRIP 2
@@ -752,6 +763,9 @@ double wgbsseg_patview_inflate_ms(wgbsseg_patview* v);
 void wgbsseg_patview_phase_ms(const wgbsseg_patview* v, double* sort_ms, double* emit_ms, double* deflate_ms);
 void wgbsseg_patview_info(const wgbsseg_patview* v, int64_t* out);
 int wgbsseg_patview_next_file(wgbsseg_patview* v, char* err, size_t errlen);
+int wgbsseg_patview_set_mask(wgbsseg_patview* v, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, char* err, size_t errlen);
+void wgbsseg_patview_mask_info(const wgbsseg_patview* v, int64_t* out);
+double wgbsseg_patview_mask_ms(const wgbsseg_patview* v);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

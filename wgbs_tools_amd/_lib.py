@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 330          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 340          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -51,7 +51,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_bgzf_deflate', 'wgbsseg_bgzf_deflate_bound', 'wgbsseg_beta2bed_bgzf', 'wgbsseg_bgzf_deflate_ms', 'wgbsseg_bgzf_deflate_pass_ms',
            'wgbsseg_patview_create', 'wgbsseg_patview_feed', 'wgbsseg_patview_feed_bgzf', 'wgbsseg_patview_finish', 'wgbsseg_patview_read',
            'wgbsseg_patview_destroy', 'wgbsseg_patview_kernel_ms', 'wgbsseg_patview_inflate_ms', 'wgbsseg_patview_phase_ms', 'wgbsseg_patview_info',
-           'wgbsseg_patview_next_file', 'wgbsseg_merge_rows', 'wgbsseg_last_merge_rows_ms']
+           'wgbsseg_patview_next_file', 'wgbsseg_merge_rows', 'wgbsseg_last_merge_rows_ms',
+           'wgbsseg_patview_set_mask', 'wgbsseg_patview_mask_info', 'wgbsseg_patview_mask_ms']
 
 
 class NativeLibraryError(RuntimeError):
@@ -327,6 +328,12 @@ def load():
     L.wgbsseg_patview_info.argtypes = [vp, vp]
     L.wgbsseg_patview_next_file.restype = i32
     L.wgbsseg_patview_next_file.argtypes = [vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_set_mask.restype = i32
+    L.wgbsseg_patview_set_mask.argtypes = [vp, vp, vp, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_mask_info.restype = None
+    L.wgbsseg_patview_mask_info.argtypes = [vp, vp]
+    L.wgbsseg_patview_mask_ms.restype = C.c_double
+    L.wgbsseg_patview_mask_ms.argtypes = [vp]
     L.wgbsseg_merge_rows.restype = i32
     L.wgbsseg_merge_rows.argtypes = [vp, vp, i32, i32, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_last_merge_rows_ms.restype = C.c_double
@@ -856,15 +863,39 @@ class PatView(_PatFeed):
     """wgbsseg_patview: pat text -> the pat text of `wgbstools view` for the CpG interval [start_cpg, end_cpg) on one GPU: the reads it
     lets through, cut (strict, strip, min_len, no_gaps), sorted when sort=True, adjacent equal lines collapsed.  finish() -> (lines,
     bytes) of the result, which stays on the device (as BGZF with deflate=True); read() / chunks() fetch it.  initial_records: the first
-    size of the record table (<= 0: the library's; a small value is the tests' hook for growth)."""
+    size of the record table (<= 0: the library's; a small value is the tests' hook for growth).  mask: (starts, ends) handed to
+    set_mask()."""
     _abi = 'patview'
     STRICT, STRIP, NO_GAPS, SORT = 1, 2, 4, 8                    # include/wgbsseg.h WGBSSEG_VIEW_*
 
-    def __init__(self, start_cpg, end_cpg, strict=False, strip=False, no_gaps=False, sort=False, min_len=1, device=0, initial_records=0):
+    def __init__(self, start_cpg, end_cpg, strict=False, strip=False, no_gaps=False, sort=False, min_len=1, device=0, initial_records=0, mask=None):
         super().__init__()
         flags = (self.STRICT if strict else 0) | (self.STRIP if strip else 0) | (self.NO_GAPS if no_gaps else 0) | (self.SORT if sort else 0)
         self.n_lines = self.n_bytes = None
         self._call('create', int(device), int(start_cpg), int(end_cpg), flags, int(min_len), int(initial_records), C.byref(self._h))
+        if mask is not None:
+            try:
+                self.set_mask(*mask)
+            except Exception:
+                self.close()
+                raise
+
+    def set_mask(self, starts, ends):
+        """the sites of the blocks [starts[k], ends[k]) (any order; they may overlap) are hidden from every read: their bytes become
+        '.' after the selection and before strip / min_len / no_gaps (`wgbstools mask_pat`).  Once, before the first feed."""
+        s = np.ascontiguousarray(starts, dtype=np.int64)
+        e = np.ascontiguousarray(ends, dtype=np.int64)
+        if s.shape != e.shape or s.ndim != 1:
+            raise ValueError('starts / ends: one value per block')
+        self._call('set_mask', self._h, s.ctypes.data if s.size else None, e.ctypes.data if e.size else None, s.size)
+
+    def mask_info(self):
+        """hidden sites, words of the bitmap, whether a mask is set; mask_ms: device time of the launch that built the bitmap"""
+        out = np.zeros(3, dtype=np.int64)
+        self._L.wgbsseg_patview_mask_info(self._h, out.ctypes.data)
+        d = dict(zip(('hidden_sites', 'mask_words', 'masked'), out.tolist()))
+        d['mask_ms'] = float(self._L.wgbsseg_patview_mask_ms(self._h))
+        return d
 
     def finish(self, deflate=False):
         lines, nbytes = C.c_int64(0), C.c_int64(0)

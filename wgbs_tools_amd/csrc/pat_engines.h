@@ -878,6 +878,11 @@ struct wgbsseg_patview {
     ViewPlan plan;
     DevBuf recs, arena, tiles, totals, state, prev;              // state: bad, desc (8 bytes each), unsorted, too_big (4 bytes each), low (8 bytes)
     ViewFiles files;                                              // the boundaries next_file() has recorded (view_plan.h)
+    MaskPlan mask;                                                // set_mask(): the union of the hidden blocks (mask_plan.h) ...
+    DevBuf mask_words, mask_iv;                                   // ... its bitmap on the device, and the intervals it was filled from
+    bool masked = false, fed_any = false;                         // set_mask() has been called; feed() / feed_bgzf() has been called
+    Event mask_ev[2];                                             // around k_view_mask_fill
+    double mask_ms = 0.0;
     int64_t bgzf_left = 0;                                        // bytes the last feed_bgzf did not take
     DevBuf perm[2], head, wg, run_end, run_tail, run_sum, text, slots, meta, dense;
     PinnedBuf host_tot, fetch;
@@ -894,6 +899,7 @@ struct wgbsseg_patview {
     bool timed[3] = {false, false, false};
     double phase_ms[3] = {0.0, 0.0, 0.0};
     wg_view_args args() const { return {plan.s, plan.e, plan.min_len, plan.flags & (WG_VIEW_STRICT | WG_VIEW_STRIP | WG_VIEW_NO_GAPS)}; }
+    wg_view_mask hidden() const { return {mask_words.as<const uint32_t>(), mask.lo, mask.hi}; }
     ~wgbsseg_patview() { feed.drain(); }
 };
 
@@ -957,12 +963,21 @@ static int view_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& s
     long long *out = v->prev.as<long long>() + (v->chunks & 1), *in = v->prev.as<long long>() + ((v->chunks & 1) ^ 1);
     HIP_TRY(hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, f.st));
     HIP_TRY(f.span_begin());
-    hipLaunchKernelGGL(k_view_measure, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), tile_recs, tile_bytes,
-                       v->state.as<unsigned long long>(), v->state.as<unsigned long long>() + 1, v->state.as<unsigned long long>() + 3, in, out, f.fed);
+    unsigned long long* state = v->state.as<unsigned long long>();
+    if (v->masked)
+        hipLaunchKernelGGL(k_view_measure_masked, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), v->hidden(), tile_recs, tile_bytes,
+                           state, state + 1, state + 3, in, out, f.fed);
+    else
+        hipLaunchKernelGGL(k_view_measure, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), tile_recs, tile_bytes,
+                           state, state + 1, state + 3, in, out, f.fed);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_recs, tile_bytes, gx, rec_base, tot);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_bytes, tile_bytes, gx, arena_base, tot + 2);
-    hipLaunchKernelGGL(k_view_pack, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), rec_base, arena_base,
-                       (uint64_t)v->n_recs, (uint64_t)v->n_arena, v->recs.as<wg_view_rec>(), v->arena.as<char>());
+    if (v->masked)
+        hipLaunchKernelGGL(k_view_pack_masked, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), v->hidden(), rec_base, arena_base,
+                           (uint64_t)v->n_recs, (uint64_t)v->n_arena, v->recs.as<wg_view_rec>(), v->arena.as<char>());
+    else
+        hipLaunchKernelGGL(k_view_pack, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), rec_base, arena_base,
+                           (uint64_t)v->n_recs, (uint64_t)v->n_arena, v->recs.as<wg_view_rec>(), v->arena.as<char>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(f.span_end());
     HIP_TRY(hipMemcpyAsync(v->host_tot.p, tot, 16, hipMemcpyDeviceToHost, f.st));
@@ -1110,13 +1125,55 @@ int wgbsseg_patview_create(int device, int64_t start_cpg, int64_t end_cpg, int32
 
 void wgbsseg_patview_destroy(wgbsseg_patview* v) { delete v; }
 
+// The site mask of `wgbstools mask_pat`: plan (mask_plan.h) -> the intervals to the device -> k_view_mask_fill on the feed's stream, in
+// front of the first chunk's kernels.  Once, before anything has been fed: every read is cut by the same rule.
+int wgbsseg_patview_set_mask(wgbsseg_patview* v, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, char* err, size_t errlen)
+{
+    if (!v) { set_err(err, errlen, "bad arguments to patview_set_mask"); return WGBSSEG_E_ARG; }
+    if (v->masked) { set_err(err, errlen, "patview_set_mask: called twice"); return WGBSSEG_E_STATE; }
+    if (v->fed_any || v->finished) { set_err(err, errlen, "patview_set_mask: called after the first feed"); return WGBSSEG_E_STATE; }
+    MaskPlan plan;
+    std::string msg;
+    const int rc = plan_mask(start_cpg, end_cpg, n_blocks, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    const hipStream_t st = v->feed.st;
+    HIP_TRY(hipSetDevice(v->feed.device));
+    const size_t nk = (size_t)plan.n_intervals();
+    HIP_TRY(v->mask_iv.ensure(2 * nk * 8)); HIP_TRY(v->mask_words.ensure((size_t)plan.n_words * 4));
+    int64_t *starts = v->mask_iv.as<int64_t>(), *ends = starts + nk;
+    HIP_TRY(hipMemcpyAsync(starts, plan.starts.data(), nk * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ends, plan.ends.data(), nk * 8, hipMemcpyHostToDevice, st));
+    for (auto& e : v->mask_ev) HIP_TRY(e.create());
+    HIP_TRY(hipEventRecord(v->mask_ev[0], st));
+    hipLaunchKernelGGL(k_view_mask_fill, dim3((unsigned)((plan.n_words + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, starts, ends, (int64_t)nk, plan.lo,
+                       plan.n_words, v->mask_words.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(v->mask_ev[1], st));
+    HIP_TRY(hipStreamSynchronize(st));                             // (the host vectors of the plan are pageable: the copies have left them)
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, v->mask_ev[0], v->mask_ev[1]) == hipSuccess) v->mask_ms = (double)ms;
+    v->mask = std::move(plan);
+    v->masked = true;
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_patview_mask_info(const wgbsseg_patview* v, int64_t* out)
+{
+    if (!v || !out) return;
+    out[0] = v->mask.n_hidden; out[1] = v->mask.n_words; out[2] = v->masked ? 1 : 0;
+}
+
+double wgbsseg_patview_mask_ms(const wgbsseg_patview* v) { return v ? v->mask_ms : -1.0; }
+
 int wgbsseg_patview_feed(wgbsseg_patview* v, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
+    if (v) v->fed_any = true;
     return PatFeed::feed_text("patview", v, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
 }
 
 int wgbsseg_patview_feed_bgzf(wgbsseg_patview* v, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
+    if (v) v->fed_any = true;
     const int rc = PatFeed::feed_bgzf("patview", v, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
     if (rc == WGBSSEG_OK) v->bgzf_left = n_bytes - *consumed;
     return rc;
@@ -1174,6 +1231,10 @@ int wgbsseg_patview_finish(wgbsseg_patview* v, int64_t* n_lines, int64_t* n_byte
         return WGBSSEG_E_ARG;
     }
     if (pat_refused(PatRefusal::unsorted, refused[1], "failed in view:", err, errlen)) return WGBSSEG_E_ARG;
+    if (v->masked && low != ~0ULL) {                               // a mask: a count below 1 is refused in a single file too (merge's reason)
+        set_err(err, errlen, "failed in view: count < 1 at byte %llu", low);
+        return WGBSSEG_E_ARG;
+    }
     const int64_t n = v->n_recs;
     int64_t lines = 0, bytes = 0;
     if (n) {

@@ -58,6 +58,69 @@ WG_HD wg_view_cut wg_view_cut_read(int64_t rs, int64_t plen, Pat&& pat, int64_t 
     return c;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// `wgbstools mask_pat` (mask_pat.cpp:78-104): sites hidden from the reads.  The hidden sites are a bitmap of 32-bit words over the sites
+// [lo, hi): bit k of word w stands for site lo + 32 w + k; the bits of the last word at or behind hi are 0; a site outside [lo, hi) is
+// not hidden.  An empty view (lo == hi) hides nothing.
+// ------------------------------------------------------------------------------------------------------------
+struct wg_view_mask {
+    const uint32_t* words;             // (hi - lo + 31) / 32 of them
+    int64_t lo, hi;
+};
+
+WG_HD int64_t wg_view_mask_words(int64_t lo, int64_t hi) { return (hi - lo + 31) >> 5; }
+
+WG_HD bool wg_view_hidden(const wg_view_mask& m, int64_t site)
+{
+    if (site < m.lo || site >= m.hi) return false;
+    const int64_t k = site - m.lo;
+    return (m.words[k >> 5] >> (k & 31)) & 1u;
+}
+
+// the hidden bits of the 64 sites from `site` on (bit i: site + i), from at most three words of the bitmap; `site` may lie anywhere
+WG_HD uint64_t wg_view_hidden64(const wg_view_mask& m, int64_t site)
+{
+    if (site >= m.hi || site + 64 <= m.lo) return 0;                // (sites are below 2^31: no overflow)
+    const int64_t k = site - m.lo, w0 = k >> 5, nw = wg_view_mask_words(m.lo, m.hi);    // (>>: the floor, also of a negative k)
+    const int sh = (int)(k & 31);
+    const uint64_t a = w0 >= 0 && w0 < nw ? m.words[w0] : 0u, b = w0 + 1 >= 0 && w0 + 1 < nw ? m.words[w0 + 1] : 0u;
+    const uint64_t low = a | (b << 32);
+    if (!sh) return low;
+    const uint64_t c = w0 + 2 >= 0 && w0 + 2 < nw ? m.words[w0 + 2] : 0u;
+    return (low >> sh) | (c << (64 - sh));
+}
+
+// A read's hidden bits, 64 sites at a time: the window that holds byte i of the read is fetched when i leaves the one at hand, so a
+// read of a few sites costs one fetch and a read of 1,500 loops over its windows.  at: the window's number in the read (-1: none yet).
+struct wg_view_window {
+    int64_t at;
+    uint64_t bits;
+};
+
+// is byte i of the read that starts at site rs hidden?
+WG_HD bool wg_view_hidden_at(const wg_view_mask& m, wg_view_window& w, int64_t rs, int64_t i)
+{
+    const int64_t k = i >> 6;
+    if (k != w.at) { w.at = k; w.bits = wg_view_hidden64(m, rs + (k << 6)); }
+    return (w.bits >> (i & 63)) & 1u;
+}
+
+// byte i of the read as mask_pat leaves it: '.' where the site rs + i is hidden
+template <class Pat>
+WG_HD char wg_view_masked_byte(const wg_view_mask& m, wg_view_window& w, int64_t rs, int64_t i, Pat&& pat)
+{
+    return wg_view_hidden_at(m, w, rs, i) ? '.' : pat(i);
+}
+
+// The masked cut: wg_view_cut_read on the read as the mask leaves it.  The mask comes after steps 1-2 — selection and --strict look at the
+// read's start and length only, which the mask does not change — and before steps 3-5, which see a hidden site as '.'.
+template <class Pat>
+WG_HD wg_view_cut wg_view_cut_read_masked(int64_t rs, int64_t plen, Pat&& pat, const wg_view_mask& m, int64_t s, int64_t e, int flags, int64_t min_len)
+{
+    wg_view_window w = {-1, 0};
+    return wg_view_cut_read(rs, plen, [&](int64_t i) { return wg_view_masked_byte(m, w, rs, i, pat); }, s, e, flags, min_len);
+}
+
 // bytes [0, la) of a against [0, lb) of b as strcmp orders them, a prefix first: < 0, 0, > 0
 WG_HD int wg_view_cmp_bytes(const char* a, uint32_t la, const char* b, uint32_t lb)
 {

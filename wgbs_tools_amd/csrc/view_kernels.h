@@ -15,6 +15,11 @@
 //   (k_bed_scan)     twice: the tiles' first record and first arena byte in the chunk
 //   k_view_pack      parses again and writes every survivor's record and bytes (chromosome, cut pattern) at tile offset + prefix inside
 //                    the tile: input order, no atomics — the unsorted modes and the tie-break of the sort rest on it
+// With a site mask (`wgbstools mask_pat`, wgbsseg_patview_set_mask):
+//   k_view_mask_fill once: the bitmap of hidden sites (view_core.h wg_view_mask) from the disjoint intervals of mask_plan.h
+//   k_view_measure_masked / k_view_pack_masked   the same two bodies (template <bool MASKED>) with view_core.h's masked cut: both see a
+//                    hidden site as '.', so they agree on survivors and arena bytes, and the pack pass writes the '.'.  A read takes its
+//                    hidden bits 64 sites at a time (wg_view_hidden64: at most three words of a bitmap that lives in L2).
 // At finish, over the n records:
 //   k_view_inorder   is the input order already the sorted one?  (then the sort is skipped)
 //   k_view_sort_runs every workgroup sorts WG_VIEW_RUN indices in LDS (bitonic network; wg_view_less is a strict total order, so the
@@ -31,6 +36,7 @@
 #include "bed_kernels.h"
 #include "view_core.h"
 #include "view_plan.h"
+#include "mask_plan.h"
 
 static_assert(WG_BED_BLOCK == WG_BLOCK, "k_bed_scan's totals and the view kernels' workgroups are both 256 wide");
 static_assert(WG_VIEW_RUN == 2 * WG_BLOCK, "one compare-exchange per thread and step of the network");
@@ -48,7 +54,8 @@ struct wg_view_line {
 
 // the line that begins at byte p: malformed (fewer than four fields, a site / count that is not a number, an empty pattern, any byte
 // between the count's digits and the newline), or parsed and cut
-__device__ __forceinline__ wg_view_line wg_view_eval(const PatText& T, int64_t p, int64_t n, const wg_view_args& a)
+template <bool MASKED>
+__device__ __forceinline__ wg_view_line wg_view_eval(const PatText& T, int64_t p, int64_t n, const wg_view_args& a, const wg_view_mask& m)
 {
     wg_view_line L = {};
     int64_t plen = 0, count = 0;
@@ -59,7 +66,8 @@ __device__ __forceinline__ wg_view_line wg_view_eval(const PatText& T, int64_t p
     L.ok = true;
     L.count = (int32_t)count;
     const int64_t ps = L.ps;
-    L.cut = wg_view_cut_read(L.site, plen, [&](int64_t k) { return T.at(ps + k); }, a.s, a.e, a.flags, a.min_len);
+    if constexpr (MASKED) L.cut = wg_view_cut_read_masked(L.site, plen, [&](int64_t k) { return T.at(ps + k); }, m, a.s, a.e, a.flags, a.min_len);
+    else L.cut = wg_view_cut_read(L.site, plen, [&](int64_t k) { return T.at(ps + k); }, a.s, a.e, a.flags, a.min_len);
     L.keep = L.cut.len > 0;
     if (L.keep) {
         int64_t c = p;
@@ -88,9 +96,10 @@ __device__ __forceinline__ uint64_t wg_view_block_incl_u64(uint64_t v, uint64_t*
     return before + incl;
 }
 
-__global__ __launch_bounds__(WG_BLOCK) void k_view_measure(const char* __restrict__ text, int64_t n, wg_view_args a, uint64_t* __restrict__ tile_recs,
-                                                           uint64_t* __restrict__ tile_bytes, unsigned long long* bad, unsigned long long* desc,
-                                                           unsigned long long* low, const long long* prev_in, long long* prev_out, unsigned long long chunk_off)
+template <bool MASKED>
+__device__ __forceinline__ void wg_view_measure(const char* __restrict__ text, int64_t n, const wg_view_args& a, const wg_view_mask& m, uint64_t* __restrict__ tile_recs,
+                                                uint64_t* __restrict__ tile_bytes, unsigned long long* bad, unsigned long long* desc,
+                                                unsigned long long* low, const long long* prev_in, long long* prev_out, unsigned long long chunk_off)
 {
     __shared__ PatTile tile;
     __shared__ long long s_last[WG_BLOCK / 64];              // the start of every wavefront's last line in the round (WG_PAT_NO_SITE: no line / malformed)
@@ -107,7 +116,7 @@ __global__ __launch_bounds__(WG_BLOCK) void k_view_measure(const char* __restric
         wg_view_line L = {};
         if (l < total) {
             const int64_t p = base + tile.lstart[l];
-            L = wg_view_eval(T, p, n, a);
+            L = wg_view_eval<MASKED>(T, p, n, a, m);
             if (!L.ok) atomicMin(bad, chunk_off + (unsigned long long)p);
             else if (L.count < 1) atomicMin(low, chunk_off + (unsigned long long)p);
         }
@@ -130,10 +139,25 @@ __global__ __launch_bounds__(WG_BLOCK) void k_view_measure(const char* __restric
     if (tid == 0) { tile_recs[blockIdx.x] = recs; tile_bytes[blockIdx.x] = bytes; }
 }
 
+__global__ __launch_bounds__(WG_BLOCK) void k_view_measure(const char* __restrict__ text, int64_t n, wg_view_args a, uint64_t* __restrict__ tile_recs,
+                                                           uint64_t* __restrict__ tile_bytes, unsigned long long* bad, unsigned long long* desc,
+                                                           unsigned long long* low, const long long* prev_in, long long* prev_out, unsigned long long chunk_off)
+{
+    wg_view_measure<false>(text, n, a, wg_view_mask{nullptr, 0, 0}, tile_recs, tile_bytes, bad, desc, low, prev_in, prev_out, chunk_off);
+}
+
+__global__ __launch_bounds__(WG_BLOCK) void k_view_measure_masked(const char* __restrict__ text, int64_t n, wg_view_args a, wg_view_mask m, uint64_t* __restrict__ tile_recs,
+                                                                  uint64_t* __restrict__ tile_bytes, unsigned long long* bad, unsigned long long* desc,
+                                                                  unsigned long long* low, const long long* prev_in, long long* prev_out, unsigned long long chunk_off)
+{
+    wg_view_measure<true>(text, n, a, m, tile_recs, tile_bytes, bad, desc, low, prev_in, prev_out, chunk_off);
+}
+
 // rec_base / arena_base: the scans of k_view_measure's totals; rec0 / arena0: what the chunks before left in the two buffers
-__global__ __launch_bounds__(WG_BLOCK) void k_view_pack(const char* __restrict__ text, int64_t n, wg_view_args a, const uint64_t* __restrict__ rec_base,
-                                                        const uint64_t* __restrict__ arena_base, uint64_t rec0, uint64_t arena0,
-                                                        wg_view_rec* __restrict__ recs, char* __restrict__ arena)
+template <bool MASKED>
+__device__ __forceinline__ void wg_view_pack(const char* __restrict__ text, int64_t n, const wg_view_args& a, const wg_view_mask& m, const uint64_t* __restrict__ rec_base,
+                                             const uint64_t* __restrict__ arena_base, uint64_t rec0, uint64_t arena0,
+                                             wg_view_rec* __restrict__ recs, char* __restrict__ arena)
 {
     __shared__ PatTile tile;
     __shared__ uint64_t sh[WG_BLOCK / 64];
@@ -148,7 +172,7 @@ __global__ __launch_bounds__(WG_BLOCK) void k_view_pack(const char* __restrict__
         int64_t p = 0;
         if (l < total) {
             p = base + tile.lstart[l];
-            L = wg_view_eval(T, p, n, a);
+            L = wg_view_eval<MASKED>(T, p, n, a, m);
         }
         const uint64_t mine = L.keep ? (uint64_t)L.clen + (uint64_t)L.cut.len : 0u;
         uint64_t rr, bb;
@@ -167,10 +191,39 @@ __global__ __launch_bounds__(WG_BLOCK) void k_view_pack(const char* __restrict__
             for (uint32_t j = 0; j < L.clen; j++) dst[j] = T.at(p + j);
             dst += L.clen;
             const int64_t from = L.ps + L.cut.first;               // (a 1,500-CpG read: past the staged bytes T.at reads global memory)
-            for (int64_t j = 0; j < L.cut.len; j++) dst[j] = T.at(from + j);
+            if constexpr (MASKED) {                                // byte cut.first + j of the read: '.' where its site is hidden
+                wg_view_window w = {-1, 0};
+                for (int64_t j = 0; j < L.cut.len; j++) dst[j] = wg_view_hidden_at(m, w, L.site, L.cut.first + j) ? '.' : T.at(from + j);
+            } else {
+                for (int64_t j = 0; j < L.cut.len; j++) dst[j] = T.at(from + j);
+            }
         }
         r_at += rr; a_at += bb;
     }
+}
+
+__global__ __launch_bounds__(WG_BLOCK) void k_view_pack(const char* __restrict__ text, int64_t n, wg_view_args a, const uint64_t* __restrict__ rec_base,
+                                                        const uint64_t* __restrict__ arena_base, uint64_t rec0, uint64_t arena0,
+                                                        wg_view_rec* __restrict__ recs, char* __restrict__ arena)
+{
+    wg_view_pack<false>(text, n, a, wg_view_mask{nullptr, 0, 0}, rec_base, arena_base, rec0, arena0, recs, arena);
+}
+
+__global__ __launch_bounds__(WG_BLOCK) void k_view_pack_masked(const char* __restrict__ text, int64_t n, wg_view_args a, wg_view_mask m, const uint64_t* __restrict__ rec_base,
+                                                               const uint64_t* __restrict__ arena_base, uint64_t rec0, uint64_t arena0,
+                                                               wg_view_rec* __restrict__ recs, char* __restrict__ arena)
+{
+    wg_view_pack<true>(text, n, a, m, rec_base, arena_base, rec0, arena0, recs, arena);
+}
+
+// One thread per word of the bitmap over [lo, lo + 32 n_words): the word is composed in registers from the disjoint ascending intervals
+// (mask_plan.h wg_mask_word: a binary search, then the intervals that reach into the word) and written with one ordinary store.  No
+// atomics: the bitmap does not depend on scheduling.
+__global__ __launch_bounds__(WG_BLOCK) void k_view_mask_fill(const int64_t* __restrict__ starts, const int64_t* __restrict__ ends, int64_t n_intervals, int64_t lo,
+                                                             int64_t n_words, uint32_t* __restrict__ words)
+{
+    const int64_t w = (int64_t)blockIdx.x * WG_BLOCK + threadIdx.x;
+    if (w < n_words) words[w] = wg_mask_word(starts, ends, n_intervals, lo, w);
 }
 
 // ------------------------------------------------------------------------------------------------------------

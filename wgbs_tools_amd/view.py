@@ -70,10 +70,11 @@ def check_interval(s, e, min_len=1):
 
 
 def view_pats(pats, s, e, sink, strict=False, strip=False, no_gaps=False, min_len=1, sort=True, device=0, inflate='host', deflate=False,
-              initial_records=0, timings=None):
+              initial_records=0, timings=None, mask=None):
     """the view of the reads of several pat files over [s, e) as if they were one file's (what `merge` is): every file is fed to ONE
     engine, next_file() between two of them; every piece of the result to sink(bytes) -> (lines, bytes).  A refusal of the engine
-    names the file by its index in `pats` (from 0) once there is more than one; the message here adds its path in front."""
+    names the file by its index in `pats` (from 0) once there is more than one; the message here adds its path in front.
+    mask: (starts, ends) of blocks whose sites are hidden from every read (`mask_pat`: _lib.PatView.set_mask)."""
     from . import _lib
     check_interval(s, e, min_len)
     t = timings if timings is not None else {}
@@ -81,7 +82,7 @@ def view_pats(pats, s, e, sink, strict=False, strip=False, no_gaps=False, min_le
     at = 0
     try:
         with _lib.PatView(s, e, strict=strict, strip=strip, no_gaps=no_gaps, sort=sort, min_len=min_len, device=device,
-                          initial_records=initial_records) as v:
+                          initial_records=initial_records, mask=mask) as v:
             for at, pat in enumerate(pats):
                 if at:
                     v.next_file()
@@ -95,6 +96,8 @@ def view_pats(pats, s, e, sink, strict=False, strip=False, no_gaps=False, min_le
             t['kernel_ms'] = v.kernel_ms()
             t['sort_ms'], t['emit_ms'], t['deflate_ms'] = v.phase_ms()
             t.update(v.info())
+            if mask is not None:
+                t.update(v.mask_info())
             for piece in v.chunks():
                 sink(piece)
     except _lib.SegmentorError as err:
