@@ -318,7 +318,15 @@ def test_deflate_on_the_device(tmp_path, capfd, genome, golden):
     plain = run(text, 1, 1000)
     packed = run(text, 1, 1000, deflate=True)
     assert packed.endswith(BGZF_EOF) and gzip.decompress(packed) == plain and len(plain) > 2 * 65280
-    assert run(b'', 1, 1000, deflate=True) == BGZF_EOF
+    assert len(plain) % 65280                                         # (the last member is a short one)
+    assert packed == _lib.bgzf_deflate(plain)                         # view and the stand-alone call: one member rule, the same kernels
+    assert run(b'', 1, 1000, deflate=True) == BGZF_EOF == _lib.bgzf_deflate(b'')
+    for deflate in (True, False):                                     # the deflate phase is timed when it runs, and only then
+        with _lib.PatView(1, 1000) as v:
+            v.feed(text)
+            v.finish(deflate=deflate)
+            ms = v.phase_ms()[2]
+            assert ms > 0 if deflate else ms == 0
 
 
 # ---- random worlds ----

@@ -1,4 +1,4 @@
-// deflate_plan.h — the host plan of text that becomes BGZF (wgbsseg_bgzf_deflate, wgbsseg_beta2bed_bgzf): the cut into members, the
+// deflate_plan.h — the host plan of text that becomes BGZF (wgbsseg_bgzf_deflate, wgbsseg_beta2bed_bgzf, wgbsseg_patview_finish): the cut into members, the
 // slot pitch of the member buffer k_bgzf_deflate writes and k_bgzf_pack reads, the bound on the bytes that come out, the end-of-file
 // member, and the argument checks with their messages.  No HIP here: g++ compiles it alone, tests/native/deflate_host.cpp hands it to the
 // tests.

@@ -1,5 +1,5 @@
 // pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_fraglen, wgbsseg_bimodal, wgbsseg_patview), the feed they share
-// and their extern "C" entry points.  Part of wgbsseg.hip, which includes it once set_err, HIP_TRY, check_device and the owners are
+// (PatFeed, PrevRead), the stand-alone wgbsseg_bgzf_inflate and their extern "C" entry points.  Part of wgbsseg.hip, which includes it once set_err, HIP_TRY, check_device and the owners are
 // in scope; what an engine decides on the host is in homog_plan.h, frag_plan.h, bimodal_plan.h and view_plan.h, this file stages, launches and fetches.
 #pragma once
 
@@ -143,37 +143,37 @@ struct PatFeed {
         HIP_TRY(f.chunk_queued(n_bytes));
         return WGBSSEG_OK;
     }
-    // A feed call with text: the checks, then chunk(n_bytes, tiles, stage) — the engine's work on a chunk that stage() puts on the device.
-    // Not called for a chunk that is refused or empty.
-    template <class Engine, class Chunk>
-    static int feed_text(const char* name, Engine* e, const char* host, int64_t n_bytes, char* err, size_t errlen, Chunk&& chunk)
+    // A feed call with text: the checks, then pat_chunk(engine, n_bytes, tiles, stage, err, errlen) — the engine's work on a chunk that stage() puts on the
+    // device: an overload per engine, declared behind it and found here by argument-dependent lookup.  Engine::name begins the messages.  Not called for a chunk that is refused or empty.
+    template <class Engine>
+    static int feed_text(Engine* e, const char* host, int64_t n_bytes, char* err, size_t errlen)
     {
-        const int64_t gx = tiles(name, e, host, n_bytes, err, errlen);
+        const int64_t gx = tiles(Engine::name, e, host, n_bytes, err, errlen);
         if (gx <= 0) return gx < 0 ? WGBSSEG_E_ARG : WGBSSEG_OK;
         PatFeed& f = e->feed;
-        const int rc = f.claim(TEXT, name, err, errlen);
+        const int rc = f.claim(TEXT, Engine::name, err, errlen);
         if (rc != WGBSSEG_OK) return rc;
-        return chunk(n_bytes, gx, [&](const char** dev) { return f.stage_chunk(host, n_bytes, dev, err, errlen); });
+        return pat_chunk(e, n_bytes, gx, [&](const char** dev) { return f.stage_chunk(host, n_bytes, dev, err, errlen); }, err, errlen);
     }
-    // A feed call with BGZF bytes: the plan (members, line rule), then the same chunk() over the complete lines of carry + members, staged
+    // A feed call with BGZF bytes: the plan (members, line rule), then the same pat_chunk over the complete lines of carry + members, staged
     // by stage_bgzf; the text behind the last newline becomes the carry.  *consumed: the bytes of the complete members.
-    template <class Engine, class Chunk>
-    static int feed_bgzf(const char* name, Engine* e, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen, Chunk&& chunk)
+    template <class Engine>
+    static int feed_bgzf(Engine* e, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
     {
-        if (!e || !consumed || n_bytes < 0 || (n_bytes && !bytes)) { set_err(err, errlen, "bad arguments to %s_feed_bgzf", name); return WGBSSEG_E_ARG; }
+        if (!e || !consumed || n_bytes < 0 || (n_bytes && !bytes)) { set_err(err, errlen, "bad arguments to %s_feed_bgzf", Engine::name); return WGBSSEG_E_ARG; }
         *consumed = 0;
         PatFeed& f = e->feed;
-        int rc = f.claim(BGZF, name, err, errlen);
+        int rc = f.claim(BGZF, Engine::name, err, errlen);
         if (rc != WGBSSEG_OK) return rc;
         BgzfPlan p;
         std::string msg;
         rc = plan_bgzf(static_cast<const uint8_t*>(bytes), n_bytes, f.file_off, f.carry, p, msg);
         if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
         if (p.n_text > 0) {
-            const int64_t gx = tiles_of(name, p.n_text, err, errlen);
+            const int64_t gx = tiles_of(Engine::name, p.n_text, err, errlen);
             if (gx < 0) return WGBSSEG_E_ARG;
             HIP_TRY(hipSetDevice(f.device));
-            rc = chunk(p.n_text, gx, [&](const char** dev) { return f.stage_bgzf(bytes, p, dev, err, errlen); });
+            rc = pat_chunk(e, p.n_text, gx, [&](const char** dev) { return f.stage_bgzf(bytes, p, dev, err, errlen); }, err, errlen);
             if (rc != WGBSSEG_OK) return rc;
         }
         f.carry = std::move(p.carry);
@@ -182,16 +182,16 @@ struct PatFeed {
         return WGBSSEG_OK;
     }
     // finish(): a last line without its newline is still in the carry; it is fed as text, with the newline (as pat_chunks does)
-    template <class Chunk>
-    int flush_carry(const char* name, Chunk&& chunk, char* err, size_t errlen)
+    template <class Engine>
+    static int flush_carry(Engine* e, char* err, size_t errlen)
     {
-        if (carry.empty()) return WGBSSEG_OK;
+        if (e->feed.carry.empty()) return WGBSSEG_OK;
         std::string last;
-        last.swap(carry);
+        last.swap(e->feed.carry);
         last.push_back('\n');
-        const int64_t n = (int64_t)last.size(), gx = tiles_of(name, n, err, errlen);
+        const int64_t n = (int64_t)last.size(), gx = tiles_of(Engine::name, n, err, errlen);
         if (gx < 0) return WGBSSEG_E_ARG;
-        return chunk(n, gx, [&](const char** dev) { return stage_chunk(last.data(), n, dev, err, errlen); });      // (copied before this returns)
+        return pat_chunk(e, n, gx, [&](const char** dev) { return e->feed.stage_chunk(last.data(), n, dev, err, errlen); }, err, errlen);      // (copied before this returns)
     }
     // finish(): a member k_bgzf_inflate refused comes before any refusal of the text.  Waits for the stream.
     int inflate_refused(char* err, size_t errlen)
@@ -239,8 +239,23 @@ static bool pat_refused(PatRefusal why, unsigned long long off, const char* pref
     return true;
 }
 
+// The last read of the chunks so far (homog, fraglen and view refuse a descending read): two slots on the device, 16 bytes
+struct PrevRead {
+    DevBuf slots;
+    unsigned long long chunks = 0;                               // chunks launched so far: the slots swap with each
+    long long* in() const { return slots.as<long long>() + ((chunks & 1) ^ 1); }      // chunk c's kernel reads slot (c + 1) & 1 ...
+    long long* out() const { return slots.as<long long>() + (chunks & 1); }           // ... and writes slot c & 1, which carry() has given in's value: kept when the chunk holds no read
+    hipError_t carry(hipStream_t st) const { return hipMemcpyAsync(out(), in(), 8, hipMemcpyDeviceToDevice, st); }      // in front of a chunk's launch
+    hipError_t reset() const                                     // no read yet (a blocking copy)
+    {
+        const long long none[2] = {WG_PAT_NO_SITE, WG_PAT_NO_SITE};
+        return hipMemcpy(slots.p, none, sizeof(none), hipMemcpyHostToDevice);
+    }
+};
+
 // pat -> beta accumulator: counts on one device; k_pat_count is timed.
 struct wgbsseg_patbeta {
+    static constexpr const char* name = "patbeta";
     PatFeed feed;
     int64_t start = 1, end = 1;
     DevBuf meth, cov, outb, bad;
@@ -249,7 +264,7 @@ struct wgbsseg_patbeta {
 
 // a staged chunk of n_bytes / gx tiles: k_pat_count over it
 template <class Stage>
-static int patbeta_chunk(wgbsseg_patbeta* p, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+static int pat_chunk(wgbsseg_patbeta* p, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
 {
     return PatFeed::one_launch(p, n_bytes, gx, stage, err, errlen, [] { return hipSuccess; }, [&](unsigned gx, const char* dtext) {
         hipLaunchKernelGGL(k_pat_count, dim3(gx), dim3(WG_BLOCK), 0, p->feed.st, dtext, n_bytes, p->start, p->end,
@@ -282,12 +297,12 @@ void wgbsseg_patbeta_destroy(wgbsseg_patbeta* p) { delete p; }
 
 int wgbsseg_patbeta_feed(wgbsseg_patbeta* p, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    return PatFeed::feed_text("patbeta", p, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return patbeta_chunk(p, n, gx, stage, err, errlen); });
+    return PatFeed::feed_text(p, text, n_bytes, err, errlen);
 }
 
 int wgbsseg_patbeta_feed_bgzf(wgbsseg_patbeta* p, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
-    return PatFeed::feed_bgzf("patbeta", p, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return patbeta_chunk(p, n, gx, stage, err, errlen); });
+    return PatFeed::feed_bgzf(p, bytes, n_bytes, consumed, err, errlen);
 }
 
 int wgbsseg_patbeta_finish(wgbsseg_patbeta* p, int32_t lbeta, void* out, char* err, size_t errlen)
@@ -295,7 +310,7 @@ int wgbsseg_patbeta_finish(wgbsseg_patbeta* p, int32_t lbeta, void* out, char* e
     if (!p || !out) { set_err(err, errlen, "bad arguments to patbeta_finish"); return WGBSSEG_E_ARG; }
     const hipStream_t st = p->feed.st;
     HIP_TRY(hipSetDevice(p->feed.device));
-    int rc = p->feed.flush_carry("patbeta", [&](int64_t n, int64_t gx, auto&& stage) { return patbeta_chunk(p, n, gx, stage, err, errlen); }, err, errlen);
+    int rc = PatFeed::flush_carry(p, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     const int64_t n = p->end - p->start;
     const size_t ob = (size_t)n * (lbeta ? 4 : 2);
@@ -328,32 +343,26 @@ double wgbsseg_patbeta_inflate_ms(wgbsseg_patbeta* p)
 
 // `wgbstools homog` accumulator: (block, bin) read counts on one device; k_homog_count is timed.
 struct wgbsseg_homog {
+    static constexpr const char* name = "homog";
     PatFeed feed;
     int64_t n_blocks = 0, last_end = 0;
     int n_bins = 0, min_cpgs = 0, inclusive = 0;
-    DevBuf bstart, bend, bpmax, range, counts, bad, desc, prev;
-    unsigned long long chunks = 0;
+    DevBuf bstart, bend, bpmax, range, counts, bad, desc;
+    PrevRead prev;
     ~wgbsseg_homog() { feed.drain(); }
 };
 
 // a staged chunk of n_bytes / gx tiles: k_homog_count over it
 template <class Stage>
-static int homog_chunk(wgbsseg_homog* h, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+static int pat_chunk(wgbsseg_homog* h, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
 {
-    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
-    long long *in = nullptr, *out = nullptr;
-    return PatFeed::one_launch(h, n_bytes, gx, stage, err, errlen,
-        [&] {
-            out = h->prev.as<long long>() + (h->chunks & 1); in = h->prev.as<long long>() + ((h->chunks & 1) ^ 1);
-            return hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, h->feed.st);
-        },
-        [&](unsigned gx, const char* dtext) {
-            hipLaunchKernelGGL(k_homog_count, dim3(gx), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes,
-                               h->bstart.as<int32_t>(), h->bend.as<int32_t>(), h->bpmax.as<int32_t>(), h->n_blocks, h->last_end,
-                               h->range.as<float>(), h->n_bins, h->min_cpgs, h->inclusive, h->counts.as<int32_t>(),
-                               h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), in, out, h->feed.fed);
-            h->chunks += 1;                                       // (the slots swap for the next chunk)
-        });
+    return PatFeed::one_launch(h, n_bytes, gx, stage, err, errlen, [&] { return h->prev.carry(h->feed.st); }, [&](unsigned gx, const char* dtext) {
+        hipLaunchKernelGGL(k_homog_count, dim3(gx), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes,
+                           h->bstart.as<int32_t>(), h->bend.as<int32_t>(), h->bpmax.as<int32_t>(), h->n_blocks, h->last_end,
+                           h->range.as<float>(), h->n_bins, h->min_cpgs, h->inclusive, h->counts.as<int32_t>(),
+                           h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), h->prev.in(), h->prev.out(), h->feed.fed);
+        h->prev.chunks += 1;                                      // (the slots swap for the next chunk)
+    });
 }
 
 extern "C" {
@@ -378,13 +387,12 @@ int wgbsseg_homog_create(int device, const int64_t* start_cpg, const int64_t* en
     const size_t nb4 = (size_t)n_blocks * 4, cb = (size_t)n_blocks * (size_t)n_bins * 4;
     HIP_TRY(h->bstart.ensure(nb4)); HIP_TRY(h->bend.ensure(nb4)); HIP_TRY(h->bpmax.ensure(nb4));
     HIP_TRY(h->range.ensure(sizeof(float) * (size_t)(n_bins + 1))); HIP_TRY(h->counts.ensure(cb));
-    HIP_TRY(h->bad.ensure(8)); HIP_TRY(h->desc.ensure(8)); HIP_TRY(h->prev.ensure(16));
+    HIP_TRY(h->bad.ensure(8)); HIP_TRY(h->desc.ensure(8)); HIP_TRY(h->prev.slots.ensure(16));
     HIP_TRY(hipMemcpy(h->bstart.p, plan.s32.data(), nb4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->bend.p, plan.e32.data(), nb4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->bpmax.p, plan.pmax.data(), nb4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->range.p, range, sizeof(float) * (size_t)(n_bins + 1), hipMemcpyHostToDevice));
-    const long long none[2] = {WG_HOMOG_NO_SITE, WG_HOMOG_NO_SITE};
-    HIP_TRY(hipMemcpy(h->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    HIP_TRY(h->prev.reset());
     HIP_TRY(hipMemsetAsync(h->counts.p, 0, cb, st));
     HIP_TRY(hipMemsetAsync(h->bad.p, 0xff, 8, st));
     HIP_TRY(hipMemsetAsync(h->desc.p, 0xff, 8, st));
@@ -396,12 +404,12 @@ void wgbsseg_homog_destroy(wgbsseg_homog* h) { delete h; }
 
 int wgbsseg_homog_feed(wgbsseg_homog* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    return PatFeed::feed_text("homog", h, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return homog_chunk(h, n, gx, stage, err, errlen); });
+    return PatFeed::feed_text(h, text, n_bytes, err, errlen);
 }
 
 int wgbsseg_homog_feed_bgzf(wgbsseg_homog* h, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
-    return PatFeed::feed_bgzf("homog", h, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return homog_chunk(h, n, gx, stage, err, errlen); });
+    return PatFeed::feed_bgzf(h, bytes, n_bytes, consumed, err, errlen);
 }
 
 int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t errlen)
@@ -409,7 +417,7 @@ int wgbsseg_homog_finish(wgbsseg_homog* h, int32_t* counts, char* err, size_t er
     if (!h || !counts) { set_err(err, errlen, "bad arguments to homog_finish"); return WGBSSEG_E_ARG; }
     const hipStream_t st = h->feed.st;
     HIP_TRY(hipSetDevice(h->feed.device));
-    int rc = h->feed.flush_carry("homog", [&](int64_t n, int64_t gx, auto&& stage) { return homog_chunk(h, n, gx, stage, err, errlen); }, err, errlen);
+    int rc = PatFeed::flush_carry(h, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     unsigned long long bad = 0, desc = 0;
     HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, st));
@@ -472,31 +480,25 @@ int wgbsseg_debug_bimodal_terms(const uint32_t* a, const uint32_t* b, int64_t co
 
 // `wgbstools frag_len` accumulator: the histogram of the selected reads' lengths on one device; k_frag_hist is timed.
 struct wgbsseg_fraglen {
+    static constexpr const char* name = "fraglen";
     PatFeed feed;
     FragPlan plan;
-    DevBuf bstart, bpmax, hist, bad, desc, prev;
-    unsigned long long chunks = 0;
+    DevBuf bstart, bpmax, hist, bad, desc;
+    PrevRead prev;
     ~wgbsseg_fraglen() { feed.drain(); }
 };
 
 // a staged chunk of n_bytes / gx tiles: k_frag_hist over it, min(gx, plan.groups) workgroups walking the tiles
 template <class Stage>
-static int fraglen_chunk(wgbsseg_fraglen* h, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+static int pat_chunk(wgbsseg_fraglen* h, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
 {
-    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
-    long long *in = nullptr, *out = nullptr;
-    return PatFeed::one_launch(h, n_bytes, gx, stage, err, errlen,
-        [&] {
-            out = h->prev.as<long long>() + (h->chunks & 1); in = h->prev.as<long long>() + ((h->chunks & 1) ^ 1);
-            return hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, h->feed.st);
-        },
-        [&](unsigned gx, const char* dtext) {
-            const unsigned grid = std::min<unsigned>(gx, (unsigned)h->plan.groups);
-            hipLaunchKernelGGL(k_frag_hist, dim3(grid), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes, (int64_t)gx,
-                               h->bstart.as<int32_t>(), h->bpmax.as<int32_t>(), h->plan.n_blocks, h->plan.end_last, (int)h->plan.max_frag,
-                               h->hist.as<unsigned long long>(), h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), in, out, h->feed.fed);
-            h->chunks += 1;                                       // (the slots swap for the next chunk)
-        });
+    return PatFeed::one_launch(h, n_bytes, gx, stage, err, errlen, [&] { return h->prev.carry(h->feed.st); }, [&](unsigned gx, const char* dtext) {
+        const unsigned grid = std::min<unsigned>(gx, (unsigned)h->plan.groups);
+        hipLaunchKernelGGL(k_frag_hist, dim3(grid), dim3(WG_BLOCK), 0, h->feed.st, dtext, n_bytes, (int64_t)gx,
+                           h->bstart.as<int32_t>(), h->bpmax.as<int32_t>(), h->plan.n_blocks, h->plan.end_last, (int)h->plan.max_frag,
+                           h->hist.as<unsigned long long>(), h->bad.as<unsigned long long>(), h->desc.as<unsigned long long>(), h->prev.in(), h->prev.out(), h->feed.fed);
+        h->prev.chunks += 1;                                      // (the slots swap for the next chunk)
+    });
 }
 
 extern "C" {
@@ -520,13 +522,12 @@ int wgbsseg_fraglen_create(int device, int32_t max_frag, const int64_t* start_cp
     const hipStream_t st = h->feed.st;
     const size_t nb4 = std::max<size_t>((size_t)n_blocks, 1) * 4, hb = (size_t)max_frag * 8;
     HIP_TRY(h->bstart.ensure(nb4)); HIP_TRY(h->bpmax.ensure(nb4)); HIP_TRY(h->hist.ensure(hb));
-    HIP_TRY(h->bad.ensure(8)); HIP_TRY(h->desc.ensure(8)); HIP_TRY(h->prev.ensure(16));
+    HIP_TRY(h->bad.ensure(8)); HIP_TRY(h->desc.ensure(8)); HIP_TRY(h->prev.slots.ensure(16));
     if (n_blocks) {
         HIP_TRY(hipMemcpy(h->bstart.p, h->plan.start.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(h->bpmax.p, h->plan.pmax.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice));
     }
-    const long long none[2] = {WG_PAT_NO_SITE, WG_PAT_NO_SITE};
-    HIP_TRY(hipMemcpy(h->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    HIP_TRY(h->prev.reset());
     HIP_TRY(hipMemsetAsync(h->hist.p, 0, hb, st));
     HIP_TRY(hipMemsetAsync(h->bad.p, 0xff, 8, st));
     HIP_TRY(hipMemsetAsync(h->desc.p, 0xff, 8, st));
@@ -538,12 +539,12 @@ void wgbsseg_fraglen_destroy(wgbsseg_fraglen* h) { delete h; }
 
 int wgbsseg_fraglen_feed(wgbsseg_fraglen* h, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    return PatFeed::feed_text("fraglen", h, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return fraglen_chunk(h, n, gx, stage, err, errlen); });
+    return PatFeed::feed_text(h, text, n_bytes, err, errlen);
 }
 
 int wgbsseg_fraglen_feed_bgzf(wgbsseg_fraglen* h, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
-    return PatFeed::feed_bgzf("fraglen", h, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return fraglen_chunk(h, n, gx, stage, err, errlen); });
+    return PatFeed::feed_bgzf(h, bytes, n_bytes, consumed, err, errlen);
 }
 
 // the carry, then a refused BGZF member before a malformed line before a descending read, then the histogram
@@ -552,7 +553,7 @@ int wgbsseg_fraglen_finish(wgbsseg_fraglen* h, int64_t* hist, char* err, size_t 
     if (!h || !hist) { set_err(err, errlen, "bad arguments to fraglen_finish"); return WGBSSEG_E_ARG; }
     const hipStream_t st = h->feed.st;
     HIP_TRY(hipSetDevice(h->feed.device));
-    int rc = h->feed.flush_carry("fraglen", [&](int64_t n, int64_t gx, auto&& stage) { return fraglen_chunk(h, n, gx, stage, err, errlen); }, err, errlen);
+    int rc = PatFeed::flush_carry(h, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     unsigned long long bad = 0, desc = 0;
     HIP_TRY(hipMemcpyAsync(&bad, h->bad.p, 8, hipMemcpyDeviceToHost, st));
@@ -589,6 +590,7 @@ double wgbsseg_fraglen_inflate_ms(wgbsseg_fraglen* h)
 // launch is timed.
 struct wgbsseg_bimodal {
     struct Table { DevBuf start, len, cnt, woff, words; };
+    static constexpr const char* name = "bimodal";
     PatFeed feed;
     BimodalPlan plan;
     int strict = 0, min_len = 1;
@@ -723,7 +725,7 @@ static int bim_parse_chunk(wgbsseg_bimodal* b, const wg_bim_state& s, Stage&& st
 // a chunk of n_bytes / gx tiles that stage() puts on the device:
 // sync (the previous chunk is parsed and checked) -> reserve -> retire -> drop -> parse; every host decision is the plan's
 template <class Stage>
-static int bim_chunk(wgbsseg_bimodal* b, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+static int pat_chunk(wgbsseg_bimodal* b, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
 {
     HIP_TRY(hipSetDevice(b->feed.device));
     int rc = bim_sync_state(b, err, errlen);
@@ -777,19 +779,19 @@ void wgbsseg_bimodal_destroy(wgbsseg_bimodal* b) { delete b; }
 
 int wgbsseg_bimodal_feed(wgbsseg_bimodal* b, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    return PatFeed::feed_text("bimodal", b, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return bim_chunk(b, n, gx, stage, err, errlen); });
+    return PatFeed::feed_text(b, text, n_bytes, err, errlen);
 }
 
 int wgbsseg_bimodal_feed_bgzf(wgbsseg_bimodal* b, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
-    return PatFeed::feed_bgzf("bimodal", b, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return bim_chunk(b, n, gx, stage, err, errlen); });
+    return PatFeed::feed_bgzf(b, bytes, n_bytes, consumed, err, errlen);
 }
 
 int wgbsseg_bimodal_finish(wgbsseg_bimodal* b, double* ll, int64_t* counts, char* err, size_t errlen)
 {
     if (!b || !ll || !counts) { set_err(err, errlen, "bad arguments to bimodal_finish"); return WGBSSEG_E_ARG; }
     HIP_TRY(hipSetDevice(b->feed.device));
-    int rc = b->feed.flush_carry("bimodal", [&](int64_t n, int64_t gx, auto&& stage) { return bim_chunk(b, n, gx, stage, err, errlen); }, err, errlen);
+    int rc = PatFeed::flush_carry(b, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     rc = bim_sync_state(b, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
@@ -872,11 +874,21 @@ int wgbsseg_bgzf_inflate(int device, const void* bytes, int64_t n_bytes, void* o
 // A chunk first waits for the chunk before it (the caller inflated this one meanwhile) and takes its totals, so the two buffers are
 // sized by what they hold plus what this chunk can add (view_plan.h).  The chunk launches are the LAUNCHES span; the phases of finish()
 // have events of their own.
+struct wg_view_state {                                            // what the view's kernels leave on the device for the host (they take a pointer to each field)
+    unsigned long long bad, desc;                                 // input offset of the first malformed line | of the first descending read; ~0: none
+    uint32_t unsorted, too_big;                                   // k_view_inorder: a record lies before the one in front | k_view_runs: a count of 10^15 or more
+    unsigned long long low;                                       // input offset of the first count below 1; ~0: none
+};
+static_assert(sizeof(wg_view_state) == 32 && offsetof(wg_view_state, desc) == 8 && offsetof(wg_view_state, unsorted) == 16 && offsetof(wg_view_state, too_big) == 20 && offsetof(wg_view_state, low) == 24, "the offsets the kernels' pointers were taken at");
+
 struct wgbsseg_patview {
     enum { SORT = 0, EMIT = 1, DEFLATE = 2 };
+    static constexpr const char* name = "patview";
     PatFeed feed;
     ViewPlan plan;
-    DevBuf recs, arena, tiles, totals, state, prev;              // state: bad, desc (8 bytes each), unsorted, too_big (4 bytes each), low (8 bytes)
+    DevBuf recs, arena, tiles, totals, state;
+    wg_view_state* dev_state() const { return state.as<wg_view_state>(); }
+    PrevRead prev;
     ViewFiles files;                                              // the boundaries next_file() has recorded (view_plan.h)
     MaskPlan mask;                                                // set_mask(): the union of the hidden blocks (mask_plan.h) ...
     DevBuf mask_words, mask_iv;                                   // ... its bitmap on the device, and the intervals it was filled from
@@ -891,7 +903,6 @@ struct wgbsseg_patview {
     bool pending = false;                                         // a chunk's totals are on their way to host_tot
     int64_t grown_recs = 0, grown_arena = 0;
     int passes = 0, order = 0;                                    // order: 0 no sort asked, 1 found in order, 2 sorted
-    unsigned long long chunks = 0;
     bool finished = false;
     const void* out = nullptr;                                    // the result on the device (text or dense) and its bytes
     int64_t out_bytes = 0;
@@ -941,7 +952,7 @@ static int view_reserve(wgbsseg_patview* v, int64_t recs, int64_t bytes, char* e
 
 // a staged chunk of n_bytes / gx tiles: totals of the chunk before -> reserve -> measure, scan, scan, pack -> its totals on their way
 template <class Stage>
-static int view_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+static int pat_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
 {
     PatFeed& f = v->feed;
     HIP_TRY(hipSetDevice(f.device));
@@ -959,17 +970,15 @@ static int view_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& s
     if (rc != WGBSSEG_OK) return rc;
     uint64_t *tile_recs = v->tiles.as<uint64_t>(), *tile_bytes = tile_recs + gx, *rec_base = tile_bytes + gx, *arena_base = rec_base + gx;
     uint64_t* tot = v->totals.as<uint64_t>();
-    // the last read of the chunks so far: slot (c + 1) & 1 in, slot c & 1 out (carried over when this chunk holds no read)
-    long long *out = v->prev.as<long long>() + (v->chunks & 1), *in = v->prev.as<long long>() + ((v->chunks & 1) ^ 1);
-    HIP_TRY(hipMemcpyAsync(out, in, 8, hipMemcpyDeviceToDevice, f.st));
+    HIP_TRY(v->prev.carry(f.st));
     HIP_TRY(f.span_begin());
-    unsigned long long* state = v->state.as<unsigned long long>();
+    wg_view_state* s = v->dev_state();
     if (v->masked)
         hipLaunchKernelGGL(k_view_measure_masked, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), v->hidden(), tile_recs, tile_bytes,
-                           state, state + 1, state + 3, in, out, f.fed);
+                           &s->bad, &s->desc, &s->low, v->prev.in(), v->prev.out(), f.fed);
     else
         hipLaunchKernelGGL(k_view_measure, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), tile_recs, tile_bytes,
-                           state, state + 1, state + 3, in, out, f.fed);
+                           &s->bad, &s->desc, &s->low, v->prev.in(), v->prev.out(), f.fed);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_recs, tile_bytes, gx, rec_base, tot);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_bytes, tile_bytes, gx, arena_base, tot + 2);
     if (v->masked)
@@ -982,7 +991,7 @@ static int view_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& s
     HIP_TRY(f.span_end());
     HIP_TRY(hipMemcpyAsync(v->host_tot.p, tot, 16, hipMemcpyDeviceToHost, f.st));
     v->pending = true;
-    v->chunks += 1;                                               // (the slots swap for the next chunk)
+    v->prev.chunks += 1;                                          // (the slots swap for the next chunk)
     HIP_TRY(f.chunk_queued(n_bytes));
     return WGBSSEG_OK;
 }
@@ -999,7 +1008,7 @@ static int view_sort(wgbsseg_patview* v, int64_t n, const uint32_t** perm, char*
     const hipStream_t st = v->feed.st;
     const wg_view_rec* recs = v->recs.as<wg_view_rec>();
     const char* arena = v->arena.as<char>();
-    uint32_t* unsorted = v->state.as<uint32_t>() + 4;
+    uint32_t* unsorted = &v->dev_state()->unsorted;
     *perm = nullptr;
     HIP_TRY(view_phase(v, wgbsseg_patview::SORT, 0));
     hipLaunchKernelGGL(k_view_inorder, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, recs, arena, n, unsorted);
@@ -1037,7 +1046,7 @@ static int view_emit(wgbsseg_patview* v, int64_t n, const uint32_t* perm, int64_
     HIP_TRY(v->run_end.ensure((size_t)n * 8)); HIP_TRY(v->run_tail.ensure((size_t)n * 4)); HIP_TRY(v->run_sum.ensure((size_t)n * 8));
     uint64_t *wg_counts = v->wg.as<uint64_t>(), *wg_heads = wg_counts + nb, *count_base = wg_heads + nb, *head_base = count_base + nb;
     uint64_t *wg_bytes = head_base + nb, *wg_lines = wg_bytes + nb, *line_base = wg_lines + nb, *tot = line_base + nb;      // tot: 3 pairs
-    uint32_t* too_big = v->state.as<uint32_t>() + 5;
+    uint32_t* too_big = &v->dev_state()->too_big;
     const dim3 grid((unsigned)nb), block(WG_BLOCK);
     HIP_TRY(view_phase(v, wgbsseg_patview::EMIT, 0));
     hipLaunchKernelGGL(k_view_heads, grid, block, 0, st, recs, arena, perm, n, v->head.as<uint8_t>(), wg_counts, wg_heads);
@@ -1110,15 +1119,14 @@ int wgbsseg_patview_create(int device, int64_t start_cpg, int64_t end_cpg, int32
     if (rc != WGBSSEG_OK) return rc;
     v->plan = plan;
     for (auto& p : v->ph) for (auto& e : p) HIP_TRY(e.create());
-    HIP_TRY(v->totals.ensure(32)); HIP_TRY(v->state.ensure(32)); HIP_TRY(v->prev.ensure(16));
+    HIP_TRY(v->totals.ensure(32)); HIP_TRY(v->state.ensure(sizeof(wg_view_state))); HIP_TRY(v->prev.slots.ensure(16));
     if (!v->host_tot.ensure(16)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
     rc = view_reserve(v.get(), plan.initial_records, plan.initial_records * 16, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
-    const long long none[2] = {WG_PAT_NO_SITE, WG_PAT_NO_SITE};
-    HIP_TRY(hipMemcpy(v->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(v->state.p, 0xff, 16, v->feed.st));
-    HIP_TRY(hipMemsetAsync(v->state.as<char>() + 16, 0, 8, v->feed.st));
-    HIP_TRY(hipMemsetAsync(v->state.as<char>() + 24, 0xff, 8, v->feed.st));
+    HIP_TRY(v->prev.reset());
+    HIP_TRY(hipMemsetAsync(&v->dev_state()->bad, 0xff, offsetof(wg_view_state, unsorted), v->feed.st));        // bad, desc: none
+    HIP_TRY(hipMemsetAsync(&v->dev_state()->unsorted, 0, offsetof(wg_view_state, low) - offsetof(wg_view_state, unsorted), v->feed.st));
+    HIP_TRY(hipMemsetAsync(&v->dev_state()->low, 0xff, sizeof(wg_view_state::low), v->feed.st));
     *out = v.release();
     return WGBSSEG_OK;
 }
@@ -1168,13 +1176,13 @@ double wgbsseg_patview_mask_ms(const wgbsseg_patview* v) { return v ? v->mask_ms
 int wgbsseg_patview_feed(wgbsseg_patview* v, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
     if (v) v->fed_any = true;
-    return PatFeed::feed_text("patview", v, text, n_bytes, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
+    return PatFeed::feed_text(v, text, n_bytes, err, errlen);
 }
 
 int wgbsseg_patview_feed_bgzf(wgbsseg_patview* v, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
     if (v) v->fed_any = true;
-    const int rc = PatFeed::feed_bgzf("patview", v, bytes, n_bytes, consumed, err, errlen, [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); });
+    const int rc = PatFeed::feed_bgzf(v, bytes, n_bytes, consumed, err, errlen);
     if (rc == WGBSSEG_OK) v->bgzf_left = n_bytes - *consumed;
     return rc;
 }
@@ -1190,12 +1198,11 @@ int wgbsseg_patview_next_file(wgbsseg_patview* v, char* err, size_t errlen)
     if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
     PatFeed& f = v->feed;
     HIP_TRY(hipSetDevice(f.device));
-    rc = f.flush_carry("patview", [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); }, err, errlen);
+    rc = PatFeed::flush_carry(v, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     rc = view_take_totals(v, err, errlen);                         // (waits for the stream: the records of the file are counted)
     if (rc != WGBSSEG_OK) return rc;
-    const long long none[2] = {WG_PAT_NO_SITE, WG_PAT_NO_SITE};    // the next file may begin below where this one ended
-    HIP_TRY(hipMemcpy(v->prev.p, none, sizeof(none), hipMemcpyHostToDevice));
+    HIP_TRY(v->prev.reset());                                      // the next file may begin below where this one ended
     f.mode = 0; f.file_off = 0; f.carry.clear();
     v->bgzf_left = 0;
     v->files.close((int64_t)f.fed, v->n_recs);
@@ -1210,12 +1217,12 @@ int wgbsseg_patview_finish(wgbsseg_patview* v, int64_t* n_lines, int64_t* n_byte
     if (v->finished) { set_err(err, errlen, "patview_finish: called twice"); return WGBSSEG_E_STATE; }
     const hipStream_t st = v->feed.st;
     HIP_TRY(hipSetDevice(v->feed.device));
-    int rc = v->feed.flush_carry("patview", [&](int64_t n, int64_t gx, auto&& stage) { return view_chunk(v, n, gx, stage, err, errlen); }, err, errlen);
+    int rc = PatFeed::flush_carry(v, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     v->finished = true;
     unsigned long long refused[2] = {0, 0}, low = 0;
-    HIP_TRY(hipMemcpyAsync(refused, v->state.p, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&low, v->state.as<unsigned long long>() + 3, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(refused, &v->dev_state()->bad, sizeof(refused), hipMemcpyDeviceToHost, st));      // bad, desc
+    HIP_TRY(hipMemcpyAsync(&low, &v->dev_state()->low, sizeof(low), hipMemcpyDeviceToHost, st));
     rc = view_take_totals(v, err, errlen);                         // (waits for the stream)
     if (rc != WGBSSEG_OK) return rc;
     rc = v->feed.inflate_refused(err, errlen);

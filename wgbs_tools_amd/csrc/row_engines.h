@@ -1,5 +1,5 @@
 // row_engines.h — the calls that work on the context's resident rows (wgbsseg_block_sums, _marker_stats, _sample_stats, _merge_rows, _pair_ranges,
-// _pair_hist, _beta2bed, _convert_regions, _site_counts, _site_table), the helpers they share and their extern "C" entry points.  Part of wgbsseg.hip, which includes
+// _pair_hist, _beta2bed, _beta2bed_bgzf, _convert_regions, _site_counts, _site_table), the stand-alone wgbsseg_bgzf_deflate, the helpers they share and their extern "C" entry points.  Part of wgbsseg.hip, which includes
 // it once set_err, HIP_TRY, the owners and the context are in scope; what a call decides on the host is in block_plan.h, stats_plan.h, merge_plan.h,
 // pair_plan.h, bed_plan.h and array_plan.h, this file stages, launches and fetches.
 #pragma once
@@ -501,14 +501,6 @@ int BedRun::finish(int io, int64_t* lines_written, int64_t* bytes_written)
     if (lines_written) *lines_written = lines;
     return WGBSSEG_OK;
 }
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
 
 // state checks -> plan (bed_plan.h) -> the slab pipeline: while the device emits slab k and measures slab k+1, the host writes slab k-1.
 // bgzf: slab k's text is deflated and packed on the device behind its emit pass; what comes home and is written are its BGZF members,
