@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 340            /* 0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 350            /* 0.3.5: wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -745,6 +745,24 @@ double wgbsseg_fraglen_inflate_ms(wgbsseg_fraglen* h);
  * "failed in view: count < 1 at byte N", for the reason above: the reference collapses once before it masks.  mask_info(): out[3] =
  * hidden sites (the reference's `loaded N sites`), words of the bitmap, 1 when a mask is set; mask_ms(): device time of the launch that
  * built the bitmap.  Without a set_mask() call everything is as described above.
+ *
+ * Sources and labels (`wgbstools mix_pat`: src/python/mix_pat.py, merge.py:17-100, src/pat_sampler/sampler.cpp): set_labels() once, after
+ * create() and before the first feed (WGBSSEG_E_STATE otherwise, and on an engine that has a mask; set_mask() is refused after it), on an
+ * engine created with WGBSSEG_VIEW_SORT.  labels: n <= 255 distinct names, each non-empty and of printable ASCII without white space,
+ * '/', '&' and '\' (WGBSSEG_E_ARG otherwise).  A label's rank is its place among them in byte order, a prefix first; label_rank(k): the
+ * rank of labels[k] (-1: no such label).  From then on every file needs set_source() — after create() or next_file() and before the
+ * file's first feed (WGBSSEG_E_STATE otherwise; a feed of a file without one is WGBSSEG_E_STATE too); WGBSSEG_E_ARG for reps < 1 or above
+ * 2^20, T > 2^30, a rank at or above the number of labels (so also without labels).  A read of the file that the cut lets through is
+ * thinned: of n = count * reps draws, draw j succeeds when word j & 3 of Philox4x32-10(counter {off lo32, off hi32, j >> 2, stream},
+ * key {seed lo32, seed hi32}) is below T = floor(p * 2^32); off is the byte offset of the line in its file's text, so the result does
+ * not depend on how the file is cut into calls nor on where it is inflated.  The read goes on with the number of successes as its count,
+ * and not at all when that is 0; its line gets the file's label as a fifth column.  finish(): the label is the last key of the order and
+ * of the collapse, so lines of two labels never merge; the lines that tie in start, pattern and chromosome — at most one per label — come
+ * in the order of the reference's `sort -m -k2,2n -k3,3`: by the decimal text of their sums, a prefix first ("1" < "10" < "9"), then by
+ * label.  The text is "chrom\trs\tpattern\tsum\tlabel\n".  A count below 1 is refused as with a mask; a line with count * reps above
+ * 2^20 is refused, "failed in view: [file K: ]count * reps above 2^20 at byte N".  sample_info(): out[3] = the reads that reached the
+ * sampler, the reads it dropped, the sum of the counts it kept (waits for the stream).  Without these calls everything is as described
+ * above.
  */
 #define WGBSSEG_VIEW_STRICT 1
 #define WGBSSEG_VIEW_STRIP 2
@@ -766,6 +784,10 @@ int wgbsseg_patview_next_file(wgbsseg_patview* v, char* err, size_t errlen);
 int wgbsseg_patview_set_mask(wgbsseg_patview* v, const int64_t* start_cpg, const int64_t* end_cpg, int64_t n_blocks, char* err, size_t errlen);
 void wgbsseg_patview_mask_info(const wgbsseg_patview* v, int64_t* out);
 double wgbsseg_patview_mask_ms(const wgbsseg_patview* v);
+int wgbsseg_patview_set_labels(wgbsseg_patview* v, const char* const* labels, int64_t n, char* err, size_t errlen);
+int32_t wgbsseg_patview_label_rank(const wgbsseg_patview* v, int64_t label);
+int wgbsseg_patview_set_source(wgbsseg_patview* v, int32_t label_rank, uint32_t T, int32_t reps, uint64_t seed, uint32_t stream, char* err, size_t errlen);
+void wgbsseg_patview_sample_info(wgbsseg_patview* v, int64_t* out);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 340          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 350          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -52,7 +52,8 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_patview_create', 'wgbsseg_patview_feed', 'wgbsseg_patview_feed_bgzf', 'wgbsseg_patview_finish', 'wgbsseg_patview_read',
            'wgbsseg_patview_destroy', 'wgbsseg_patview_kernel_ms', 'wgbsseg_patview_inflate_ms', 'wgbsseg_patview_phase_ms', 'wgbsseg_patview_info',
            'wgbsseg_patview_next_file', 'wgbsseg_merge_rows', 'wgbsseg_last_merge_rows_ms',
-           'wgbsseg_patview_set_mask', 'wgbsseg_patview_mask_info', 'wgbsseg_patview_mask_ms']
+           'wgbsseg_patview_set_mask', 'wgbsseg_patview_mask_info', 'wgbsseg_patview_mask_ms',
+           'wgbsseg_patview_set_labels', 'wgbsseg_patview_label_rank', 'wgbsseg_patview_set_source', 'wgbsseg_patview_sample_info']
 
 
 class NativeLibraryError(RuntimeError):
@@ -334,6 +335,14 @@ def load():
     L.wgbsseg_patview_mask_info.argtypes = [vp, vp]
     L.wgbsseg_patview_mask_ms.restype = C.c_double
     L.wgbsseg_patview_mask_ms.argtypes = [vp]
+    L.wgbsseg_patview_set_labels.restype = i32
+    L.wgbsseg_patview_set_labels.argtypes = [vp, C.POINTER(C.c_char_p), i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_label_rank.restype = i32
+    L.wgbsseg_patview_label_rank.argtypes = [vp, i64]
+    L.wgbsseg_patview_set_source.restype = i32
+    L.wgbsseg_patview_set_source.argtypes = [vp, i32, C.c_uint32, i32, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_sample_info.restype = None
+    L.wgbsseg_patview_sample_info.argtypes = [vp, vp]
     L.wgbsseg_merge_rows.restype = i32
     L.wgbsseg_merge_rows.argtypes = [vp, vp, i32, i32, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_last_merge_rows_ms.restype = C.c_double
@@ -864,7 +873,7 @@ class PatView(_PatFeed):
     lets through, cut (strict, strip, min_len, no_gaps), sorted when sort=True, adjacent equal lines collapsed.  finish() -> (lines,
     bytes) of the result, which stays on the device (as BGZF with deflate=True); read() / chunks() fetch it.  initial_records: the first
     size of the record table (<= 0: the library's; a small value is the tests' hook for growth).  mask: (starts, ends) handed to
-    set_mask()."""
+    set_mask().  set_labels() / set_source(): the reads of every file thinned and labelled (`wgbstools mix_pat`)."""
     _abi = 'patview'
     STRICT, STRIP, NO_GAPS, SORT = 1, 2, 4, 8                    # include/wgbsseg.h WGBSSEG_VIEW_*
 
@@ -896,6 +905,30 @@ class PatView(_PatFeed):
         d = dict(zip(('hidden_sites', 'mask_words', 'masked'), out.tolist()))
         d['mask_ms'] = float(self._L.wgbsseg_patview_mask_ms(self._h))
         return d
+
+    def set_labels(self, labels):
+        """the labels of `wgbstools mix_pat` (str or bytes; at most 255, distinct, printable ASCII without white space, '/', '&', '\\'):
+        once, before the first feed, on a sorting engine -> the rank of every label (its place in byte order, a prefix first), which
+        set_source() takes.  From here on every file needs a set_source()."""
+        names = [x if isinstance(x, bytes) else str(x).encode() for x in labels]
+        arr = (C.c_char_p * max(len(names), 1))(*names)
+        self._call('set_labels', self._h, arr, len(names))
+        return [int(self._L.wgbsseg_patview_label_rank(self._h, k)) for k in range(len(names))]
+
+    def set_source(self, label_rank, T, reps, seed, stream):
+        """the file about to be fed (after create / next_file, before its first feed): its reads get the label of that rank and are
+        thinned — of count * reps draws those below T = floor(p * 2^32) succeed (p <= 0.25), the bits from (seed, stream, the line's
+        byte offset in the file)"""
+        T, stream, seed = int(T), int(stream), int(seed)
+        if not (0 <= T < 2 ** 32 and 0 <= stream < 2 ** 32 and 0 <= seed < 2 ** 64 and -2 ** 31 <= int(reps) < 2 ** 31 and -2 ** 31 <= int(label_rank) < 2 ** 31):
+            raise SegmentorError(-1, 'patview_set_source: T and stream are 32 bits, seed is 64 bits')
+        self._call('set_source', self._h, int(label_rank), T, int(reps), seed, stream)
+
+    def sample_info(self):
+        """reads that reached the sampler, reads it dropped, the sum of the counts it kept"""
+        out = np.zeros(3, dtype=np.int64)
+        self._L.wgbsseg_patview_sample_info(self._h, out.ctypes.data)
+        return dict(zip(('sampled_reads', 'sampled_dropped', 'sampled_kept'), out.tolist()))
 
     def finish(self, deflate=False):
         lines, nbytes = C.c_int64(0), C.c_int64(0)

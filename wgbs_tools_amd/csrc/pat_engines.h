@@ -881,6 +881,11 @@ struct wg_view_state {                                            // what the vi
 };
 static_assert(sizeof(wg_view_state) == 32 && offsetof(wg_view_state, desc) == 8 && offsetof(wg_view_state, unsorted) == 16 && offsetof(wg_view_state, too_big) == 20 && offsetof(wg_view_state, low) == 24, "the offsets the kernels' pointers were taken at");
 
+struct wg_view_sample_state {                                     // with a source: what k_view_measure_sampled leaves
+    unsigned long long over;                                      // input offset of the first line with count * reps above the cap; ~0: none
+    unsigned long long stats[3];                                  // reads that reached the sampler, reads it dropped, the sum of the counts it kept
+};
+
 struct wgbsseg_patview {
     enum { SORT = 0, EMIT = 1, DEFLATE = 2 };
     static constexpr const char* name = "patview";
@@ -896,7 +901,12 @@ struct wgbsseg_patview {
     Event mask_ev[2];                                             // around k_view_mask_fill
     double mask_ms = 0.0;
     int64_t bgzf_left = 0;                                        // bytes the last feed_bgzf did not take
-    DevBuf perm[2], head, wg, run_end, run_tail, run_sum, text, slots, meta, dense;
+    ViewLabels labels;                                            // set_labels(): ranks and the table by rank (view_plan.h) ...
+    DevBuf label_tab, sample;                                     // ... its offsets and bytes on the device | wg_view_sample_state
+    bool labelled = false, file_fed = false;                      // set_labels() has been called; the open file has been fed
+    int64_t source_file = -1;                                     // the file set_source() was last called for
+    wg_view_source source = {};                                   // what it said (at / over / stats: filled per chunk)
+    DevBuf perm[2], head, wg, run_end, run_tail, run_sum, tie_sum, tie_tail, text, slots, meta, dense;
     PinnedBuf host_tot, fetch;
     int64_t cap_recs = 0, cap_arena = 0;                          // what recs / arena have room for
     int64_t n_recs = 0, n_arena = 0;                              // what they hold (the chunks whose totals have been taken)
@@ -911,6 +921,9 @@ struct wgbsseg_patview {
     double phase_ms[3] = {0.0, 0.0, 0.0};
     wg_view_args args() const { return {plan.s, plan.e, plan.min_len, plan.flags & (WG_VIEW_STRICT | WG_VIEW_STRIP | WG_VIEW_NO_GAPS)}; }
     wg_view_mask hidden() const { return {mask_words.as<const uint32_t>(), mask.lo, mask.hi}; }
+    wg_view_labels label_table() const { return {label_tab.as<const char>() + (labels.n() + 1) * 4, label_tab.as<const uint32_t>()}; }
+    wg_view_sample_state* dev_sample() const { return sample.as<wg_view_sample_state>(); }
+    bool sampled() const { return labelled; }                    // with labels every file has a source (pat_chunk refuses a file without)
     ~wgbsseg_patview() { feed.drain(); }
 };
 
@@ -950,6 +963,14 @@ static int view_reserve(wgbsseg_patview* v, int64_t recs, int64_t bytes, char* e
     return WGBSSEG_OK;
 }
 
+// with labels every file needs a source before anything of it is fed
+static int view_source_missing(const wgbsseg_patview* v, char* err, size_t errlen)
+{
+    if (!v->labelled || v->source_file == v->files.open_file()) return WGBSSEG_OK;
+    set_err(err, errlen, "patview_feed: labels are set and file %lld has no source (patview_set_source)", (long long)v->files.open_file());
+    return WGBSSEG_E_STATE;
+}
+
 // a staged chunk of n_bytes / gx tiles: totals of the chunk before -> reserve -> measure, scan, scan, pack -> its totals on their way
 template <class Stage>
 static int pat_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
@@ -957,7 +978,9 @@ static int pat_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& st
     PatFeed& f = v->feed;
     HIP_TRY(hipSetDevice(f.device));
     if (v->finished) { set_err(err, errlen, "patview_feed: finish() has been called"); return WGBSSEG_E_STATE; }
-    int rc = view_take_totals(v, err, errlen);
+    int rc = view_source_missing(v, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    rc = view_take_totals(v, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     std::string msg;
     rc = plan_view_chunk(v->n_recs, n_bytes, msg);
@@ -973,7 +996,15 @@ static int pat_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& st
     HIP_TRY(v->prev.carry(f.st));
     HIP_TRY(f.span_begin());
     wg_view_state* s = v->dev_state();
-    if (v->masked)
+    wg_view_source q = v->source;
+    if (v->sampled()) {                                            // the chunk's first byte inside its file; where the sampler reports
+        q.at = f.fed - (v->files.several() ? (uint64_t)v->files.end_bytes.back() : 0u);
+        q.over = &v->dev_sample()->over; q.stats = v->dev_sample()->stats;
+    }
+    if (v->sampled())
+        hipLaunchKernelGGL(k_view_measure_sampled, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), q, tile_recs, tile_bytes,
+                           &s->bad, &s->desc, &s->low, v->prev.in(), v->prev.out(), f.fed);
+    else if (v->masked)
         hipLaunchKernelGGL(k_view_measure_masked, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), v->hidden(), tile_recs, tile_bytes,
                            &s->bad, &s->desc, &s->low, v->prev.in(), v->prev.out(), f.fed);
     else
@@ -981,7 +1012,10 @@ static int pat_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& st
                            &s->bad, &s->desc, &s->low, v->prev.in(), v->prev.out(), f.fed);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_recs, tile_bytes, gx, rec_base, tot);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, f.st, tile_bytes, tile_bytes, gx, arena_base, tot + 2);
-    if (v->masked)
+    if (v->sampled())
+        hipLaunchKernelGGL(k_view_pack_sampled, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), q, rec_base, arena_base,
+                           (uint64_t)v->n_recs, (uint64_t)v->n_arena, v->recs.as<wg_view_rec>(), v->arena.as<char>());
+    else if (v->masked)
         hipLaunchKernelGGL(k_view_pack_masked, dim3((unsigned)gx), dim3(WG_BLOCK), 0, f.st, dtext, n_bytes, v->args(), v->hidden(), rec_base, arena_base,
                            (uint64_t)v->n_recs, (uint64_t)v->n_arena, v->recs.as<wg_view_rec>(), v->arena.as<char>());
     else
@@ -1011,7 +1045,8 @@ static int view_sort(wgbsseg_patview* v, int64_t n, const uint32_t** perm, char*
     uint32_t* unsorted = &v->dev_state()->unsorted;
     *perm = nullptr;
     HIP_TRY(view_phase(v, wgbsseg_patview::SORT, 0));
-    hipLaunchKernelGGL(k_view_inorder, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, recs, arena, n, unsorted);
+    const bool lab = v->labelled;                                  // the label rank as the last key: the _labelled instantiations
+    hipLaunchKernelGGL(lab ? k_view_inorder_labelled : k_view_inorder, dim3((unsigned)((n + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, recs, arena, n, unsorted);
     HIP_TRY(hipGetLastError());
     uint32_t flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, unsorted, 4, hipMemcpyDeviceToHost, st));
@@ -1020,12 +1055,12 @@ static int view_sort(wgbsseg_patview* v, int64_t n, const uint32_t** perm, char*
     if (flag) {
         HIP_TRY(v->perm[0].ensure((size_t)n * 4)); HIP_TRY(v->perm[1].ensure((size_t)n * 4));
         int cur = 0;
-        hipLaunchKernelGGL(k_view_sort_runs, dim3((unsigned)wg_view_runs(n)), dim3(WG_BLOCK), 0, st, recs, arena, n, v->perm[0].as<uint32_t>());
+        hipLaunchKernelGGL(lab ? k_view_sort_runs_labelled : k_view_sort_runs, dim3((unsigned)wg_view_runs(n)), dim3(WG_BLOCK), 0, st, recs, arena, n, v->perm[0].as<uint32_t>());
         const int passes = wg_view_merge_passes(n);
         int64_t run = WG_VIEW_RUN;
         const int64_t threads = (n + WG_VIEW_MERGE_ITEMS - 1) / WG_VIEW_MERGE_ITEMS;
         for (int k = 0; k < passes; k++, run *= 2, cur ^= 1)
-            hipLaunchKernelGGL(k_view_merge, dim3((unsigned)((threads + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, recs, arena, n, run,
+            hipLaunchKernelGGL(lab ? k_view_merge_labelled : k_view_merge, dim3((unsigned)((threads + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st, recs, arena, n, run,
                                v->perm[cur].as<const uint32_t>(), v->perm[cur ^ 1].as<uint32_t>());
         HIP_TRY(hipGetLastError());
         v->passes = passes;
@@ -1049,12 +1084,21 @@ static int view_emit(wgbsseg_patview* v, int64_t n, const uint32_t* perm, int64_
     uint32_t* too_big = &v->dev_state()->too_big;
     const dim3 grid((unsigned)nb), block(WG_BLOCK);
     HIP_TRY(view_phase(v, wgbsseg_patview::EMIT, 0));
-    hipLaunchKernelGGL(k_view_heads, grid, block, 0, st, recs, arena, perm, n, v->head.as<uint8_t>(), wg_counts, wg_heads);
+    hipLaunchKernelGGL(v->labelled ? k_view_heads_labelled : k_view_heads, grid, block, 0, st, recs, arena, perm, n, v->head.as<uint8_t>(), wg_counts, wg_heads);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, wg_counts, wg_heads, nb, count_base, tot);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, wg_heads, wg_heads, nb, head_base, tot + 2);
     hipLaunchKernelGGL(k_view_tails, grid, block, 0, st, recs, perm, n, v->head.as<const uint8_t>(), count_base, head_base, v->run_end.as<int64_t>(), v->run_tail.as<uint32_t>());
-    hipLaunchKernelGGL(k_view_runs, grid, block, 0, st, recs, perm, tot + 2, v->run_end.as<const int64_t>(), v->run_tail.as<const uint32_t>(), v->run_sum.as<int64_t>(),
-                       wg_bytes, wg_lines, too_big);
+    const int64_t* sums = v->run_sum.as<const int64_t>();
+    const uint32_t* tails = v->run_tail.as<const uint32_t>();
+    if (v->labelled) {                                             // the runs of a group of tied lines into the reference's order, then the lengths with the labels
+        HIP_TRY(v->tie_sum.ensure((size_t)n * 8)); HIP_TRY(v->tie_tail.ensure((size_t)n * 4));
+        hipLaunchKernelGGL(k_view_run_sums, grid, block, 0, st, tot + 2, v->run_end.as<const int64_t>(), v->run_sum.as<int64_t>(), too_big);
+        hipLaunchKernelGGL(k_view_tie_order, grid, block, 0, st, recs, arena, perm, tot + 2, sums, tails, v->tie_sum.as<int64_t>(), v->tie_tail.as<uint32_t>());
+        sums = v->tie_sum.as<const int64_t>(); tails = v->tie_tail.as<const uint32_t>();
+        hipLaunchKernelGGL(k_view_runs_labelled, grid, block, 0, st, recs, perm, tot + 2, sums, tails, v->label_table(), wg_bytes, wg_lines);
+    } else
+        hipLaunchKernelGGL(k_view_runs, grid, block, 0, st, recs, perm, tot + 2, v->run_end.as<const int64_t>(), v->run_tail.as<const uint32_t>(), v->run_sum.as<int64_t>(),
+                           wg_bytes, wg_lines, too_big);
     hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, wg_bytes, wg_lines, nb, line_base, tot + 4);
     HIP_TRY(hipGetLastError());
     uint64_t got[2] = {0, 0};
@@ -1067,7 +1111,10 @@ static int view_emit(wgbsseg_patview* v, int64_t n, const uint32_t* perm, int64_
         return WGBSSEG_E_ARG;
     }
     HIP_TRY(v->text.ensure((size_t)got[0] + 16));
-    hipLaunchKernelGGL(k_view_emit, grid, block, 0, st, recs, arena, perm, tot + 2, v->run_sum.as<const int64_t>(), v->run_tail.as<const uint32_t>(), line_base, v->text.as<char>());
+    if (v->labelled)
+        hipLaunchKernelGGL(k_view_emit_labelled, grid, block, 0, st, recs, arena, perm, tot + 2, sums, tails, v->label_table(), line_base, v->text.as<char>());
+    else
+        hipLaunchKernelGGL(k_view_emit, grid, block, 0, st, recs, arena, perm, tot + 2, v->run_sum.as<const int64_t>(), v->run_tail.as<const uint32_t>(), line_base, v->text.as<char>());
     HIP_TRY(hipGetLastError());
     HIP_TRY(view_phase(v, wgbsseg_patview::EMIT, 1));
     *bytes = (int64_t)got[0]; *lines = (int64_t)got[1];
@@ -1140,6 +1187,7 @@ int wgbsseg_patview_set_mask(wgbsseg_patview* v, const int64_t* start_cpg, const
     if (!v) { set_err(err, errlen, "bad arguments to patview_set_mask"); return WGBSSEG_E_ARG; }
     if (v->masked) { set_err(err, errlen, "patview_set_mask: called twice"); return WGBSSEG_E_STATE; }
     if (v->fed_any || v->finished) { set_err(err, errlen, "patview_set_mask: called after the first feed"); return WGBSSEG_E_STATE; }
+    if (v->labelled) { set_err(err, errlen, "patview_set_mask: the engine has labels: a mask and sources do not go together"); return WGBSSEG_E_STATE; }
     MaskPlan plan;
     std::string msg;
     const int rc = plan_mask(start_cpg, end_cpg, n_blocks, plan, msg);
@@ -1173,15 +1221,79 @@ void wgbsseg_patview_mask_info(const wgbsseg_patview* v, int64_t* out)
 
 double wgbsseg_patview_mask_ms(const wgbsseg_patview* v) { return v ? v->mask_ms : -1.0; }
 
+// The labels of `wgbstools mix_pat`: plan (view_plan.h: the checks, the ranks) -> the table by rank to the device, once; the sampler's
+// state beside it.  Once, before anything has been fed; from here on every file needs a source.
+int wgbsseg_patview_set_labels(wgbsseg_patview* v, const char* const* labels, int64_t n, char* err, size_t errlen)
+{
+    if (!v) { set_err(err, errlen, "bad arguments to patview_set_labels"); return WGBSSEG_E_ARG; }
+    if (v->labelled) { set_err(err, errlen, "patview_set_labels: called twice"); return WGBSSEG_E_STATE; }
+    if (v->fed_any || v->finished) { set_err(err, errlen, "patview_set_labels: called after the first feed"); return WGBSSEG_E_STATE; }
+    if (v->masked) { set_err(err, errlen, "patview_set_labels: the engine has a mask: a mask and sources do not go together"); return WGBSSEG_E_STATE; }
+    ViewLabels plan;
+    std::string msg;
+    const int rc = plan_view_labels(labels, n, v->plan.flags, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    const hipStream_t st = v->feed.st;
+    HIP_TRY(hipSetDevice(v->feed.device));
+    const size_t ob = plan.off.size() * 4;
+    HIP_TRY(v->label_tab.ensure(ob + plan.bytes.size())); HIP_TRY(v->sample.ensure(sizeof(wg_view_sample_state)));
+    HIP_TRY(hipMemcpyAsync(v->label_tab.p, plan.off.data(), ob, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(v->label_tab.as<char>() + ob, plan.bytes.data(), plan.bytes.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(&v->dev_sample()->over, 0xff, sizeof(wg_view_sample_state::over), st));
+    HIP_TRY(hipMemsetAsync(v->dev_sample()->stats, 0, sizeof(wg_view_sample_state::stats), st));
+    HIP_TRY(hipStreamSynchronize(st));                             // (the plan's vectors are pageable: the copies have left them)
+    v->labels = std::move(plan);
+    v->labelled = true;
+    return WGBSSEG_OK;
+}
+
+int32_t wgbsseg_patview_label_rank(const wgbsseg_patview* v, int64_t label)
+{
+    return v && label >= 0 && label < v->labels.n() ? (int32_t)v->labels.rank[(size_t)label] : -1;
+}
+
+// The source of the file about to be fed: host state only — the chunks of the file take it as a kernel argument.
+int wgbsseg_patview_set_source(wgbsseg_patview* v, int32_t label_rank, uint32_t T, int32_t reps, uint64_t seed, uint32_t stream, char* err, size_t errlen)
+{
+    if (!v) { set_err(err, errlen, "bad arguments to patview_set_source"); return WGBSSEG_E_ARG; }
+    if (v->finished) { set_err(err, errlen, "patview_set_source: finish() has been called"); return WGBSSEG_E_STATE; }
+    if (v->file_fed) { set_err(err, errlen, "patview_set_source: file %lld has been fed already", (long long)v->files.open_file()); return WGBSSEG_E_STATE; }
+    if (v->masked) { set_err(err, errlen, "patview_set_source: the engine has a mask: a mask and sources do not go together"); return WGBSSEG_E_STATE; }
+    std::string msg;
+    const int rc = plan_view_source(label_rank, T, reps, stream, v->labels.n(), msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    v->source = wg_view_source{seed, 0u, T, stream, (uint32_t)reps, (uint32_t)label_rank, nullptr, nullptr};
+    v->source_file = v->files.open_file();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_patview_sample_info(wgbsseg_patview* v, int64_t* out)
+{
+    if (!v || !out) return;
+    out[0] = out[1] = out[2] = 0;
+    if (!v->labelled || hipSetDevice(v->feed.device) != hipSuccess || hipStreamSynchronize(v->feed.st) != hipSuccess) return;
+    unsigned long long got[3] = {0, 0, 0};
+    if (hipMemcpy(got, v->dev_sample()->stats, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) return;
+    for (int k = 0; k < 3; k++) out[k] = (int64_t)got[k];
+}
+
 int wgbsseg_patview_feed(wgbsseg_patview* v, const char* text, int64_t n_bytes, char* err, size_t errlen)
 {
-    if (v) v->fed_any = true;
+    if (v) {
+        const int rc = view_source_missing(v, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        v->fed_any = v->file_fed = true;
+    }
     return PatFeed::feed_text(v, text, n_bytes, err, errlen);
 }
 
 int wgbsseg_patview_feed_bgzf(wgbsseg_patview* v, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
 {
-    if (v) v->fed_any = true;
+    if (v) {
+        const int rc = view_source_missing(v, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        v->fed_any = v->file_fed = true;
+    }
     const int rc = PatFeed::feed_bgzf(v, bytes, n_bytes, consumed, err, errlen);
     if (rc == WGBSSEG_OK) v->bgzf_left = n_bytes - *consumed;
     return rc;
@@ -1205,6 +1317,7 @@ int wgbsseg_patview_next_file(wgbsseg_patview* v, char* err, size_t errlen)
     HIP_TRY(v->prev.reset());                                      // the next file may begin below where this one ended
     f.mode = 0; f.file_off = 0; f.carry.clear();
     v->bgzf_left = 0;
+    v->file_fed = false;
     v->files.close((int64_t)f.fed, v->n_recs);
     return WGBSSEG_OK;
 }
@@ -1220,7 +1333,8 @@ int wgbsseg_patview_finish(wgbsseg_patview* v, int64_t* n_lines, int64_t* n_byte
     int rc = PatFeed::flush_carry(v, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     v->finished = true;
-    unsigned long long refused[2] = {0, 0}, low = 0;
+    unsigned long long refused[2] = {0, 0}, low = 0, over = ~0ULL;
+    if (v->labelled) HIP_TRY(hipMemcpyAsync(&over, &v->dev_sample()->over, sizeof(over), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(refused, &v->dev_state()->bad, sizeof(refused), hipMemcpyDeviceToHost, st));      // bad, desc
     HIP_TRY(hipMemcpyAsync(&low, &v->dev_state()->low, sizeof(low), hipMemcpyDeviceToHost, st));
     rc = view_take_totals(v, err, errlen);                         // (waits for the stream)
@@ -1238,10 +1352,11 @@ int wgbsseg_patview_finish(wgbsseg_patview* v, int64_t* n_lines, int64_t* n_byte
         return WGBSSEG_E_ARG;
     }
     if (pat_refused(PatRefusal::unsorted, refused[1], "failed in view:", err, errlen)) return WGBSSEG_E_ARG;
-    if (v->masked && low != ~0ULL) {                               // a mask: a count below 1 is refused in a single file too (merge's reason)
+    if ((v->masked || v->labelled) && low != ~0ULL) {              // a mask, labels: a count below 1 is refused in a single file too (merge's reason)
         set_err(err, errlen, "failed in view: count < 1 at byte %llu", low);
         return WGBSSEG_E_ARG;
     }
+    if (over != ~0ULL) { set_err(err, errlen, "%s", wg_view_over_refusal(v->files, over).c_str()); return WGBSSEG_E_ARG; }
     const int64_t n = v->n_recs;
     int64_t lines = 0, bytes = 0;
     if (n) {

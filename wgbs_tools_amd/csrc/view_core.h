@@ -1,7 +1,8 @@
 // view_core.h — the rules of `wgbstools view` / `cview` on pat reads, one set of functions for host and device (like bed_fmt.h and
 // deflate_core.h): what is cut from a read (cview.cpp:8-17,:87-167 with one block; patter_utils.cpp:260-280), the order of
 // `LC_ALL=C sort -k2,2n -k3,3` over the surviving lines, when two adjacent lines collapse (collapse_pat.pl) and how long an output
-// line is.  No HIP needed: g++ compiles it alone (tests/native/view_host.cpp hands it to the tests).
+// line is; for `wgbstools mix_pat` the counter-based generator, the sample rule and the order of tied, labelled lines (at the end).  No HIP
+// needed: g++ compiles it alone (tests/native/view_host.cpp and mix_host.cpp hand it to the tests).
 //
 // A surviving read is a record: its start after the cut, its count, and where its bytes lie in an arena — the chromosome's name
 // followed by the cut pattern.  Everything below reads a record's bytes through a pointer to that arena.
@@ -22,7 +23,7 @@ struct wg_view_rec {
     int64_t rs;                        // the first CpG of the cut pattern
     int32_t count;
     uint32_t clen, plen;
-    uint32_t line;                     // reserved (0)
+    uint32_t line;                     // the rank of the read's label (wgbsseg_patview_set_labels); 0 without labels
 };
 
 // what is left of a read
@@ -143,15 +144,32 @@ WG_HD int wg_view_cmp(const wg_view_rec& x, const wg_view_rec& y, const char* ar
     return wg_view_cmp_bytes(ax, x.clen, ay, y.clen);
 }
 
+// the same with the label rank (wg_view_rec.line) as the last key, for an engine with labels: lines of two labels never collapse
+WG_HD int wg_view_cmp_labelled(const wg_view_rec& x, const wg_view_rec& y, const char* arena)
+{
+    const int d = wg_view_cmp(x, y, arena);
+    if (d) return d;
+    return x.line != y.line ? (x.line < y.line ? -1 : 1) : 0;
+}
+
+template <bool LABELS>
+WG_HD int wg_view_cmp_as(const wg_view_rec& x, const wg_view_rec& y, const char* arena)
+{
+    if constexpr (LABELS) return wg_view_cmp_labelled(x, y, arena);
+    else return wg_view_cmp(x, y, arena);
+}
+
 // the strict order of the sort: record ix before record iy (their input positions break the ties that cannot show)
+template <bool LABELS = false>
 WG_HD bool wg_view_less(const wg_view_rec* recs, uint32_t ix, uint32_t iy, const char* arena)
 {
-    const int d = wg_view_cmp(recs[ix], recs[iy], arena);
+    const int d = wg_view_cmp_as<LABELS>(recs[ix], recs[iy], arena);
     return d ? d < 0 : ix < iy;
 }
 
 // does the line y, which follows the line x, begin a new run (collapse_pat.pl: any of chrom, start, pattern differs)?
-WG_HD bool wg_view_run_head(const wg_view_rec& x, const wg_view_rec& y, const char* arena) { return wg_view_cmp(x, y, arena) != 0; }
+template <bool LABELS = false>
+WG_HD bool wg_view_run_head(const wg_view_rec& x, const wg_view_rec& y, const char* arena) { return wg_view_cmp_as<LABELS>(x, y, arena) != 0; }
 
 // the text of a start (a read that hangs over the genome's front starts below 1, possibly below 0): its length, and its bytes at dst
 WG_HD int wg_view_int_len(int64_t v) { return v < 0 ? 1 + wg_dec_len((uint64_t)(-v)) : wg_dec_len((uint64_t)v); }
@@ -169,4 +187,67 @@ WG_HD uint32_t wg_view_line_len(const wg_view_rec& r, int64_t sum)
 {
     if (sum <= 0) return 0;
     return r.clen + 1 + (uint32_t)wg_view_int_len(r.rs) + 1 + r.plen + 1 + (uint32_t)wg_dec_len((uint64_t)sum) + 1;
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// `wgbstools mix_pat`: reads thinned by a binomial draw (src/pat_sampler/sampler.cpp), a label column, and the order `sort -m -k2,2n -k3,3`
+// gives lines of several labels that tie in start, pattern and chromosome.  The reference seeds a fresh engine from the clock for every
+// line; here the bits come from a counter-based generator keyed by the line's place in its file, so a draw depends on nothing but
+// (seed, stream, byte offset of the line, count * reps, T) — not on chunks, tiles, threads or the order of the work.
+// ------------------------------------------------------------------------------------------------------------
+#define WG_VIEW_MAX_DRAWS (1LL << 20)  // count * reps of one line: more is refused, not looped over
+#define WG_VIEW_MAX_T (1u << 30)       // T = floor(p * 2^32) with p <= 0.25
+#define WG_VIEW_MAX_LABELS 255
+
+// Philox4x32 with 10 rounds (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): out = the four words of the block
+WG_HD void wg_philox4x32_10(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4])
+{
+    uint32_t c0 = counter[0], c1 = counter[1], c2 = counter[2], c3 = counter[3], k0 = key[0], k1 = key[1];
+    for (int r = 0; r < 10; r++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// The successes among n = count * reps draws (0 <= n <= WG_VIEW_MAX_DRAWS: the caller refuses more): draw j is word j & 3 of the block
+// with counter {off, j >> 2, stream} under the key `seed`, a success when below T.  off: the byte offset of the line in its file's text.
+WG_HD int64_t wg_view_sample(int64_t count, int64_t reps, uint32_t T, uint64_t seed, uint32_t stream, uint64_t off)
+{
+    const int64_t n = count * reps;
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t counter[4] = {(uint32_t)off, (uint32_t)(off >> 32), 0u, stream}, w[4];
+    int64_t got = 0;
+    for (int64_t j = 0; j < n; j += 4) {
+        counter[2] = (uint32_t)(j >> 2);
+        wg_philox4x32_10(counter, key, w);
+        const int64_t m = n - j < 4 ? n - j : 4;
+        for (int64_t k = 0; k < m; k++) got += w[k] < T ? 1 : 0;
+    }
+    return got;
+}
+
+// the decimal texts of two sums (both > 0) as bytes, a prefix first ("1" < "10" < "9"): < 0, 0, > 0
+WG_HD int wg_view_cmp_dec_text(int64_t a, int64_t b)
+{
+    char ta[20], tb[20];
+    const int la = wg_dec_put(ta, (uint64_t)a), lb = wg_dec_put(tb, (uint64_t)b);
+    return wg_view_cmp_bytes(ta, (uint32_t)la, tb, (uint32_t)lb);
+}
+
+// Two collapsed lines that tie in start, pattern and chromosome: sort's last-resort comparison of the whole lines reaches the count's
+// text, then the label's bytes (its rank says the same).  Strict: the labels of two such lines differ.
+WG_HD bool wg_view_tie_less(int64_t sum_x, uint32_t rank_x, int64_t sum_y, uint32_t rank_y)
+{
+    const int d = wg_view_cmp_dec_text(sum_x, sum_y);
+    return d ? d < 0 : rank_x < rank_y;
+}
+
+// the output line of a run with a label of lab_len bytes: "... sum \t label \n"
+WG_HD uint32_t wg_view_line_len_labelled(const wg_view_rec& r, int64_t sum, uint32_t lab_len)
+{
+    const uint32_t plain = wg_view_line_len(r, sum);
+    return plain ? plain + 1 + lab_len : 0;
 }

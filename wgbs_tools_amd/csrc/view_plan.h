@@ -1,6 +1,7 @@
 // view_plan.h — the host plan of `wgbstools view` (wgbsseg_patview_*): the argument checks with their messages, the limits of the
 // record table and its arena, how the two grow, the sort's run length and number of merge passes, the slabs of the fetch, and the table
-// of file boundaries of a view over several files (`wgbstools merge`) with the messages that name a file.  No HIP
+// of file boundaries of a view over several files (`wgbstools merge`) with the messages that name a file, and the labels and sources of
+// `wgbstools mix_pat`: the checks of the names, their ranks, the table the device takes, the checks of a file's source.  No HIP
 // here (like frag_plan.h): g++ compiles it alone, tests/native/view_host.cpp hands it to the tests.
 //
 // Limits.  A record is 32 bytes (view_core.h); their number stays below 2^31, so a permutation entry is a uint32.  A survivor puts
@@ -96,6 +97,54 @@ inline int plan_view_next_file(bool finished, int64_t left, int64_t file, std::s
     return WGBSSEG_OK;
 }
 
+// The labels of `wgbstools mix_pat` (wgbsseg_patview_set_labels): at most WG_VIEW_MAX_LABELS, distinct, each non-empty and of printable
+// ASCII without white space, '/', '&' and '\' (a label goes through the reference's `sed 's/$/\tLABEL/'` untouched only without them).
+// rank[k]: the place of label k in byte order, a prefix first — the order `sort` gives lines that differ in their label only; bytes /
+// off: the labels in that order, one after the other, and their n + 1 offsets, as the device takes them.
+struct ViewLabels {
+    std::vector<uint32_t> rank, off;                                // rank: one per label as given | off: n + 1 offsets into bytes, by rank
+    std::string bytes;
+    int64_t n() const { return (int64_t)rank.size(); }
+};
+
+inline int plan_view_labels(const char* const* labels, int64_t n, int flags, ViewLabels& p, std::string& msg)
+{
+    p = ViewLabels();
+    if (n < 1 || n > WG_VIEW_MAX_LABELS || !labels) return wg_plan_refuse(msg, "view: %lld labels (1 to %d)", (long long)n, WG_VIEW_MAX_LABELS);
+    if (!(flags & WG_VIEW_SORT)) return wg_plan_refuse(msg, "view: labels need a sorted view (WGBSSEG_VIEW_SORT): the order of tied lines is defined on it");
+    std::vector<std::string> names;
+    for (int64_t k = 0; k < n; k++) {
+        if (!labels[k] || !labels[k][0]) return wg_plan_refuse(msg, "view: label %lld is empty", (long long)k);
+        names.emplace_back(labels[k]);
+        for (const char c : names.back())
+            if (c <= ' ' || c > '~' || c == '/' || c == '&' || c == '\\')
+                return wg_plan_refuse(msg, "view: label %lld holds the byte 0x%02x (printable ASCII without white space, '/', '&' and '\\')", (long long)k, (unsigned)(unsigned char)c);
+    }
+    std::vector<uint32_t> order((size_t)n);
+    for (uint32_t k = 0; k < (uint32_t)n; k++) order[k] = k;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });      // (std::string: bytes as unsigned char, a prefix first)
+    for (int64_t k = 1; k < n; k++)
+        if (names[order[(size_t)k]] == names[order[(size_t)k - 1]]) return wg_plan_refuse(msg, "view: the label %s is given twice", names[order[(size_t)k]].c_str());
+    p.rank.resize((size_t)n);
+    p.off.push_back(0u);
+    for (uint32_t r = 0; r < (uint32_t)n; r++) {
+        p.rank[order[r]] = r;
+        p.bytes += names[order[r]];
+        p.off.push_back((uint32_t)p.bytes.size());
+    }
+    return WGBSSEG_OK;
+}
+
+// the source of a file (wgbsseg_patview_set_source): the rank of its label, T = floor(p * 2^32) with p <= 0.25, reps >= 1
+inline int plan_view_source(int64_t label_rank, uint64_t T, int64_t reps, uint64_t stream, int64_t n_labels, std::string& msg)
+{
+    if (label_rank < 0 || label_rank >= n_labels) return wg_plan_refuse(msg, "view: label rank %lld of %lld labels", (long long)label_rank, (long long)n_labels);
+    if (T > WG_VIEW_MAX_T) return wg_plan_refuse(msg, "view: T = %llu (at most 2^30: a rate of 0.25)", (unsigned long long)T);
+    if (reps < 1 || reps > WG_VIEW_MAX_DRAWS) return wg_plan_refuse(msg, "view: reps = %lld (1 to 2^20)", (long long)reps);
+    if (stream > 0xffffffffULL) return wg_plan_refuse(msg, "view: stream %llu (below 2^32)", (unsigned long long)stream);
+    return WGBSSEG_OK;
+}
+
 // What finish() says of a refused line once next_file() has been called: the file (0-based, in feed order) and the byte offset inside it.
 enum class ViewRefusal { bad_line, unsorted, low_count };
 inline std::string wg_view_file_refusal(const ViewFiles& files, ViewRefusal why, uint64_t off)
@@ -110,6 +159,20 @@ inline std::string wg_view_file_refusal(const ViewFiles& files, ViewRefusal why,
         snprintf(buf, sizeof buf, "failed in view: file %lld: the pat file is not sorted: the read at byte offset %llu of the file starts before the read before it", (long long)file, (unsigned long long)inside);
     else
         snprintf(buf, sizeof buf, "failed in view: file %lld: count < 1 at byte %llu", (long long)file, (unsigned long long)inside);
+    return buf;
+}
+
+// a line whose count * reps is above WG_VIEW_MAX_DRAWS: "failed in view: [file K: ]count * reps above 2^20 at byte N"
+inline std::string wg_view_over_refusal(const ViewFiles& files, uint64_t off)
+{
+    int64_t file = 0;
+    uint64_t inside = off;
+    char buf[128];
+    if (files.several()) {
+        files.locate(off, file, inside);
+        snprintf(buf, sizeof buf, "failed in view: file %lld: count * reps above 2^20 at byte %llu", (long long)file, (unsigned long long)inside);
+    } else
+        snprintf(buf, sizeof buf, "failed in view: count * reps above 2^20 at byte %llu", (unsigned long long)inside);
     return buf;
 }
 

@@ -34,7 +34,7 @@ Deliberate deviations from the reference:
   6. --no_gaps, --no_sort, --shuffle and -np are accepted and change nothing, as in the reference, whose extract_view_flags drops them;
      one line on stderr says so.  -T is accepted and unused: nothing is sorted on disk.
 
-Out of scope: --labels, -L and `mix_pat`; writing an index; starting the merge passes of the sort from whole-file runs instead of
+Out of scope: --labels and -L (`mix_pat`, which does label its reads, is mix_pat.py); writing an index; starting the merge passes of the sort from whole-file runs instead of
 512-record runs (profiles/view_mi355x.txt: 8.0 M records sort in 7.1 ms beside hundreds of ms of feed).
 """
 import argparse

@@ -70,22 +70,33 @@ def check_interval(s, e, min_len=1):
 
 
 def view_pats(pats, s, e, sink, strict=False, strip=False, no_gaps=False, min_len=1, sort=True, device=0, inflate='host', deflate=False,
-              initial_records=0, timings=None, mask=None):
+              initial_records=0, timings=None, mask=None, sources=None):
     """the view of the reads of several pat files over [s, e) as if they were one file's (what `merge` is): every file is fed to ONE
     engine, next_file() between two of them; every piece of the result to sink(bytes) -> (lines, bytes).  A refusal of the engine
     names the file by its index in `pats` (from 0) once there is more than one; the message here adds its path in front.
-    mask: (starts, ends) of blocks whose sites are hidden from every read (`mask_pat`: _lib.PatView.set_mask)."""
+    mask: (starts, ends) of blocks whose sites are hidden from every read (`mask_pat`: _lib.PatView.set_mask).
+    sources: ([(label, T, reps) per file], seed, rep) — every file's reads thinned and labelled (`mix_pat`: _lib.PatView.set_labels /
+    set_source with stream = rep << 16 | file); None: nothing of it."""
     from . import _lib
     check_interval(s, e, min_len)
     t = timings if timings is not None else {}
     spent = {}
     at = 0
+    if sources is not None:
+        per_file, seed, rep_no = sources
+        if len(per_file) != len(pats):
+            raise IllegalArgumentError(f'view: {len(per_file)} sources for {len(pats)} files')
+        if not (0 <= int(rep_no) < 65536 and len(pats) <= 65536):
+            raise IllegalArgumentError(f'view: repetition {rep_no} of {len(pats)} files (both below 65536)')
     try:
         with _lib.PatView(s, e, strict=strict, strip=strip, no_gaps=no_gaps, sort=sort, min_len=min_len, device=device,
                           initial_records=initial_records, mask=mask) as v:
+            ranks = v.set_labels([x[0] for x in per_file]) if sources is not None else None
             for at, pat in enumerate(pats):
                 if at:
                     v.next_file()
+                if ranks is not None:
+                    v.set_source(ranks[at], per_file[at][1], per_file[at][2], seed, (int(rep_no) << 16) | at)
                 one = {}
                 feed_pat(v, pat, one, inflate=inflate)
                 for key, val in one.items():                     # (inflate_ms is the engine's running total)
@@ -98,6 +109,8 @@ def view_pats(pats, s, e, sink, strict=False, strip=False, no_gaps=False, min_le
             t.update(v.info())
             if mask is not None:
                 t.update(v.mask_info())
+            if sources is not None:
+                t.update(v.sample_info())
             for piece in v.chunks():
                 sink(piece)
     except _lib.SegmentorError as err:
