@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 350            /* 0.3.5: wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 351            /* 0.3.5.1: wgbsseg_debug_last_plan (test hook: the staging form of the last call); wgbsseg_debug_fetch("cost") serves staged calls with n_stages <= nbuf.  0.3.5:wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -798,8 +798,12 @@ int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
  *   "cum"     uint32[sites]   exclusive prefix of F inside each chunk (row offset of start site k; chunk-relative: 0 at
  *                             every chunk's first site)
  *   "back"    uint16[sites]   i+1-argmax_k of M[i+1]
- *   "cost"    double[pairs]   scored blocks, only if the call ran as a single stage (WGBSSEG_FORCE_STAGES=1 makes it so;
- *                             WGBSSEG_E_STATE otherwise)
+ *   "cost"    double[pairs]   scored blocks, only if every stage of the call kept a buffer to itself: one stage
+ *                             (WGBSSEG_FORCE_STAGES=1 makes it so), two stages, or three gated ones (n_stages <= nbuf of
+ *                             wgbsseg_debug_last_plan; WGBSSEG_E_STATE otherwise: a later stage has overwritten an earlier
+ *                             one's blocks).  A staged call's rows are put together on the host, stage after stage: the
+ *                             whole row of a start site lies in the buffer of the stage that holds the START, also when
+ *                             its blocks end beyond the stage bound.
  * Layout, for a call of any number of chunks: DENSE, chunk after chunk in the caller's order.  sites = the sum of the
  * chunks' lengths, and chunk c's entries begin at the sum of the lengths before it — the padding the library keeps
  * between the chunks' slices of its own arrays (each begins at a multiple of 8 entries) is left out.  pairs = the sum
@@ -807,12 +811,24 @@ int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
  * them in its cost buffer.  Inside a chunk the rows are start-major: row k (at the chunk's "cum"[k]) holds the blocks
  * that start at site k and end at k .. k+F_k-1.
  * Returns the number of bytes written, or a negative code (WGBSSEG_E_CAPACITY: cap_bytes is less than that).
+ * wgbsseg_debug_last_plan reports the form the LAST wgbsseg_segment_chunks() call took, as the library decided and
+ * launched it (copied when the call ended; the hook launches nothing and touches no stream).  With S = out[0]:
+ *   out[0] n_stages   out[1] gated (the stages alternated between the scoring streams behind the gate)
+ *   out[2] nbuf (scored-block buffers)   out[3] last_pct (length of the last stage in percent of the others')
+ *   out[4] dp_mode   out[5] all_narrow (no window beyond the narrow tiles')
+ *   out[6] contexts alive on the device when the plan was made   out[7] chunks of the call
+ *   out[8 .. 8+S]          the S + 1 stage bounds (chunk-relative sites)
+ *   out[9+S .. 8+2S]       per stage: 1 when its recurrence ran as k_dp16
+ *   out[9+2S .. 8+5S]      tiles per stage and class: [3 * stage + class], classes 0 narrow, 1 wide, 2 medium
+ * Returns the 9 + 5 S entries written, WGBSSEG_E_CAPACITY when cap (in entries) is less, WGBSSEG_E_STATE when there is
+ * no finished call to report (none yet, or the rows or loci changed since).
  * wgbsseg_debug_sample_terms evaluates the per-(block,sample) term on the device for arrays of (nmeth, ntotal).
  * wgbsseg_debug_log2 evaluates the device arithmetic for `count` consecutive float bit patterns p starting at
  * `first_bits`: out_f = uint32 bits of log2f(p); out_d = uint64 bits of the exact log2(1.0-(double)p) restatement;
  * out_fast = uint64 bits of the bounded-error fast log2 the scoring kernel tries first (any of them may be NULL).
  */
 int64_t wgbsseg_debug_fetch(wgbsseg_ctx* ctx, const char* what, void* out, int64_t cap_bytes);
+int64_t wgbsseg_debug_last_plan(const wgbsseg_ctx* ctx, int64_t* out, int64_t cap);
 int wgbsseg_debug_sample_terms(wgbsseg_ctx* ctx, const float* nmeth, const float* ntotal, int64_t count,
                                float pseudo_count, float* out);
 int wgbsseg_debug_log2(wgbsseg_ctx* ctx, uint32_t first_bits, int64_t count, uint32_t* out_f, uint64_t* out_d,

@@ -14,6 +14,7 @@ import pytest
 
 import cases
 import intermediates as im
+import staging
 from wgbs_tools_amd import _lib
 
 pytestmark = pytest.mark.gpu
@@ -88,6 +89,11 @@ def _run(sg, world, whats, label):
     return sg.timings()
 
 
+def _form(sg, world, label='', **claims):
+    """the last call's plan against the form the test claims (staging.assert_form) -> plan"""
+    return staging.assert_form(sg.last_plan(), max(c[1] for c in world[2]), label=label, **claims)
+
+
 # ---------------------------------------------------------------------------------------------------------
 # a. every case, the launcher's own choice of form
 # ---------------------------------------------------------------------------------------------------------
@@ -104,6 +110,7 @@ def test_a_every_case_default_form(seg1, worlds, golden_chunks, name):
     world = _golden_case(worlds, name)
     t = _run(seg1, world, ALL, name)
     assert t['n_stages'] == 1
+    _form(seg1, world, name, stages=1, gated=0, dp_mode=staging.auto_dp_mode(t['max_window']))
     assert world[4][0].borders.tolist() == golden_chunks[name]['borders']
 
 
@@ -125,6 +132,7 @@ def test_b_narrow_tile_shapes_and_division_cores(worlds, ti, ns, div_short):
             t = _run(sg, _golden_case(worlds, name), ('cost', 'back'), '%s, TI %d NS %d DIV_SHORT %r' % (name, ti, ns, div_short))
             print('%s TI %d NS %d: short division core %s, widest window %d' % (name, ti, ns, 'on' if t['div_short'] else 'off', t['max_window']))
             assert t['n_stages'] == 1
+            _form(sg, _golden_case(worlds, name), name, stages=1, gated=0)
             if div_short == 0:
                 assert t['div_short'] == 0
 
@@ -147,6 +155,7 @@ def test_c_class_boundaries_in_one_batch(worlds, n_samples, cov_mode, pcount, ma
         with _segmenter(FORCE_STAGES=1, MEDIUM_WMAX=wm) as sg:
             t = _run(sg, world, ALL, '%d samples (%s), pcount %r max_cpg %d, medium <= %s' % (n_samples, cov_mode, pcount, max_cpg, wm))
             assert t['max_window'] == max_cpg and t['n_stages'] == 1
+            assert _form(sg, world, 'medium <= %s' % wm, stages=1, gated=0)['all_narrow'] == (max_cpg <= 60)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -166,33 +175,113 @@ def test_d_wide_tiles_on_carries(seg1, worlds):
     seg1.segment_chunks([5, 2001, 4099], [1900, 2000, 2500], 100.0, 200, 10**6)
     t = _run(seg1, world, ALL, 'carry world')
     assert t['max_window'] == 300 and t['n_stages'] == 1
+    plan = _form(seg1, world, 'carry world', stages=1, gated=0, dp_mode=1)
+    assert all(row[1] > 0 for row in plan['stage_tiles'])          # wide tiles, the consumers of the carries
 
 
 # ---------------------------------------------------------------------------------------------------------
 # e. the recurrence builds, the lean step, staging
 # ---------------------------------------------------------------------------------------------------------
+# the gate axis: WGBSSEG_STAGE_GATE=0 (no gate: every stage's scoring on one stream), and the gate lifted over the one-context rule
+# (WGBSSEG_STAGE_GATE_SHARED=1: this module's `seg1` is alive beside every context made here) with a slack of 1 tile (a stage waits for all
+# tiles of the stage before but one) and of 4096 (more than any stage here has: the count to wait for clamps to 1, the gate opens at once
+# and neighbouring stages overlap as much as they can)
+GATES = {'off': dict(STAGE_GATE=0), 'slack1': dict(STAGE_GATE=1, STAGE_GATE_SHARED=1), 'slack4096': dict(STAGE_GATE=4096, STAGE_GATE_SHARED=1)}
+
+# chunk lengths of 1 (mod 64), the longest not first.  The stage bounds of a 1025-site job are 576 (two equal stages), 320 (two stages, the
+# last of 300 percent), 384 / 768, 448 / 896 and 256 / 512 (three stages, the last of 100, 40 and 300 percent): for every bound b a chunk of
+# b + 1 sites, whose last stage is ONE start site and whose last site the bound falls on; 65 and 1 end before any second stage begins.
+STAGED_LENGTHS = [577, 1025, 65, 257, 321, 385, 449, 513, 769, 897, 1]
+STAGED_WORLDS = {
+    # no window beyond the narrow tiles' 60 sites (open sea of ~20, islands cut at 60): the host's own tile counts, k_dp16 in the early stages
+    'narrow': (lambda: cases.lean_step_world(), [37, 4131, 123, 9001, 14003, 2005, 15001, 300, 7777, 11111, 19998], (15.0, 60, 2000)),
+    # test_c's world on the wide side of the 252 | 253 boundary with 40 samples (two LDS sample groups): wide tiles, medium and narrow ones towards every chunk's end
+    'classes': (lambda: cases.medium_tile_world(40, 'mix'), [3, 1999, 8737, 4103, 5, 2005, 6001, 7003, 101, 8000, 8999], (15.0, 253, 10**6)),
+    # test_d's world: windows of 300 sites, wide tiles on k_scan's carries, chunks on and off the 128-site carry groups
+    'carries': (lambda: cases.carry_world(20000), [7, 129, 3, 12000, 100, 4097, 8063, 16001, 2049, 5555, 19999], (15.0, 300, 10**6)),
+}
+
+
+def _staged_world(worlds, name):
+    def build():
+        make, starts, params = STAGED_WORLDS[name]
+        slices, loci = make()
+        return slices, loci, list(zip(starts, STAGED_LENGTHS)), params
+    return worlds('staged/' + name, build)
+
+
+def _default_last_pct(world):
+    """the last stage's length a gated job gets without WGBSSEG_LAST_STAGE_PCT (plan_stages): 300 percent up to 52,500 evaluations per step"""
+    pairs = sum(e.cost.size for e in world[4])
+    return 300 if float(pairs) * len(world[0]) / max(1.0, float(max(c[1] for c in world[2]))) <= 52500.0 else 100
+
+
+def _check_staged(sg, world, label, stages, gate, mode=None):
+    """One call on `world` under forced stages and a gate setting: windows, cum and back-pointers of every chunk, the scored blocks whenever
+    every stage kept its buffer (refused otherwise), and the form that ran."""
+    gated = int(bool(stages) and stages > 1 and 'STAGE_GATE_SHARED' in GATES[gate])
+    t = _run(sg, world, ('window', 'cum', 'back'), label)
+    plan = _form(sg, world, label, stages=stages, gated=gated, last_pct=_default_last_pct(world) if gated else 100,
+                 dp_mode=None if mode is None else max(mode, staging.auto_dp_mode(t['max_window'])))
+    assert plan['n_stages'] == t['n_stages'] and plan['nbuf'] == (1 if plan['n_stages'] == 1 else 3 if gated and plan['n_stages'] > 2 else 2), (label, plan)
+    assert plan['dp16'] == [int(plan['dp_mode'] == 0 and s + 1 < plan['n_stages']) for s in range(plan['n_stages'])], (label, plan)
+    if plan['n_stages'] <= plan['nbuf']:
+        im.check_call(sg, world[4], [e.borders for e in world[4]], ('cost',), label)
+    else:
+        with pytest.raises(_lib.SegmentorError) as e:              # a later stage has scored into an earlier one's buffer: refused
+            sg.debug_fetch('cost', np.float64, 16)
+        assert e.value.code == _lib.E_STATE
+    return t, plan
+
+
 @pytest.mark.parametrize('stages', [None, 2, 3, 7])
 @pytest.mark.parametrize('wlean', [1, 0])
 @pytest.mark.parametrize('mode', [0, 1, 2])
 def test_e_recurrence_builds(worlds, mode, wlean, stages):
     """Back-pointers (and the windows they rest on) under WGBSSEG_DP_MODE 0 / 1 / 2 (64-step batches; 32-step batches with a second pending
     register and the ring; the same with 15 worker waves), with the lean step on and off, in the launcher's own staging and in 2, 3 and 7
-    stages (k_dp16 in every stage but the last when the mode is 0): windows > 64, islands in open sea, windows of thousands of sites, and the
-    six chunks of test_17's world with its first two parameter sets."""
-    label = 'dp mode %d, lean %d, stages %r' % (mode, wlean, stages)
-    with _segmenter(DP_MODE=mode, DP_WLEAN=wlean, FORCE_STAGES=stages) as sg:
+    stages: windows > 64, islands in open sea, windows of thousands of sites, and the six chunks of test_17's world with its first two
+    parameter sets.  This is the UNGATED value of the gate axis (WGBSSEG_STAGE_GATE=0; test_e_gated_recurrence_builds has the other two):
+    without the switch the form would hang on how many other contexts are alive.  last_plan() shows that a world with a window > 64 never
+    runs k_dp16, whatever the mode asked for (the launcher only raises it): the all-narrow world of STAGED_WORLDS is here for that kernel."""
+    label = 'dp mode %d, lean %d, stages %r, ungated' % (mode, wlean, stages)
+    with _segmenter(DP_MODE=mode, DP_WLEAN=wlean, FORCE_STAGES=stages, **GATES['off']) as sg:
         for name in ('dense_w_gt_64', 'island_mix', 'deep'):
-            t = _run(sg, _golden_case(worlds, name), ('window', 'cum', 'back'), '%s, %s' % (name, label))
+            world = _golden_case(worlds, name)
+            t = _run(sg, world, ('window', 'cum', 'back'), '%s, %s' % (name, label))
+            plan = _form(sg, world, '%s, %s' % (name, label), stages=stages, gated=0, dp_mode=max(mode, staging.auto_dp_mode(t['max_window'])))
+            assert plan['dp16'] == [0] * plan['n_stages']
             if stages:
                 assert t['n_stages'] == stages
         for q in (0, 1):
-            t = _run(sg, _lean_world(worlds, q), ('window', 'cum', 'back'), 'lean-step world %r, %s' % (cases.LEAN_WORLD_PARAMS[q], label))
+            t, plan = _check_staged(sg, _lean_world(worlds, q), 'lean-step world %r, %s' % (cases.LEAN_WORLD_PARAMS[q], label), stages, 'off', mode)
             assert t['max_window'] > 64
             if stages:
                 assert t['n_stages'] == stages
-                with pytest.raises(_lib.SegmentorError) as e:          # the scored blocks of a staged job share their buffers: refused
-                    sg.debug_fetch('cost', np.float64, 16)
-                assert e.value.code == _lib.E_STATE
+        if stages:
+            t, plan = _check_staged(sg, _staged_world(worlds, 'narrow'), 'all-narrow world, ' + label, stages, 'off', mode)
+            assert plan['all_narrow'] == 1 and plan['dp_mode'] == mode and plan['gated'] == 0
+
+
+@pytest.mark.parametrize('stages', [2, 3, 7])
+@pytest.mark.parametrize('wlean', [1, 0])
+@pytest.mark.parametrize('mode', [0, 1, 2])
+@pytest.mark.parametrize('gate', ['slack1', 'slack4096'])
+def test_e_gated_recurrence_builds(worlds, gate, mode, wlean, stages):
+    """The gated values of test_e's gate axis, every form of it (2, 3 and 7 stages, the three recurrence builds, the lean step on and off): the
+    stages alternate between the two scoring streams behind k_stage_gate, a third scored-block buffer from three stages on, a last stage of
+    300 percent.  Pruned by WORLD: the many-chunk batches, where stages have narrow and wide tiles side by side (test_17's six chunks, both
+    parameter sets), one single chunk with windows > 64, and the all-narrow world (k_dp16 in every stage but the last in mode 0); island_mix
+    and deep stay with the ungated value.  Windows, cum and back-pointers of every chunk; the scored blocks too where the buffers survive
+    (2 stages, 3 gated stages)."""
+    label = 'dp mode %d, lean %d, stages %d, gate %s' % (mode, wlean, stages, gate)
+    with _segmenter(DP_MODE=mode, DP_WLEAN=wlean, FORCE_STAGES=stages, **GATES[gate]) as sg:
+        _check_staged(sg, _golden_case(worlds, 'dense_w_gt_64'), 'dense_w_gt_64, ' + label, stages, gate, mode)
+        for q in (0, 1):
+            t, plan = _check_staged(sg, _lean_world(worlds, q), 'lean-step world %r, %s' % (cases.LEAN_WORLD_PARAMS[q], label), stages, gate, mode)
+            assert t['n_stages'] == stages and plan['gated'] == 1 and plan['nbuf'] == (3 if stages > 2 else 2)
+        t, plan = _check_staged(sg, _staged_world(worlds, 'narrow'), 'all-narrow world, ' + label, stages, gate, mode)
+        assert plan['all_narrow'] == 1 and plan['gated'] == 1 and plan['dp16'] == [int(mode == 0)] * (plan['n_stages'] - 1) + [0]
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -209,6 +298,7 @@ def test_e2_chunks_on_carry_unit_and_tile_boundaries(seg1, worlds, golden_offset
     world = worlds('offset/' + name, build)
     assert [list(c) for c in world[2]] == [list(c) for c in golden_offsets[name]['chunks']]
     _run(seg1, world, ALL, name)
+    _form(seg1, world, name, stages=1, gated=0)
     for e, want in zip(world[4], golden_offsets[name]['borders']):
         assert e.borders.tolist() == want
 
@@ -233,6 +323,7 @@ def test_f_dense_fetch_of_a_batch_equals_the_chunks_fetched_alone(seg1, worlds):
         for w in ALL:
             alone[w].append(im.fetch(seg1, w, [e]))
     _run(seg1, world, ALL, 'the batch')
+    assert _form(seg1, world, 'the batch', stages=1, gated=0)['n_chunks'] == len(chunks)
     for w in ALL:
         got, want = im.fetch(seg1, w, exp), np.concatenate(alone[w])
         assert got.dtype == want.dtype and np.array_equal(got, want), '%s: %s' % (w, im._first_diff(got, want))
@@ -240,3 +331,99 @@ def test_f_dense_fetch_of_a_batch_equals_the_chunks_fetched_alone(seg1, worlds):
     with pytest.raises(_lib.SegmentorError) as e:
         seg1.debug_fetch('window', np.uint16, sum(c[1] for c in chunks) - 1)
     assert e.value.code == _lib.E_CAPACITY
+
+
+# ---------------------------------------------------------------------------------------------------------
+# g. the scored blocks of staged calls: every stage's tile plan, the three scored-block buffers, the gate's streams
+# ---------------------------------------------------------------------------------------------------------
+STAGED_FORMS = {
+    '2 ungated':        (2, 'off', None),
+    '2 gated':          (2, 'slack1', None),            # (the launcher's own last stage: _default_last_pct)
+    '3 gated, last 40': (3, 'slack1', 40),
+    '3 gated, last 100': (3, 'slack4096', 100),
+    '3 gated, last 300': (3, 'slack1', 300),
+}
+
+
+@pytest.mark.parametrize('form', list(STAGED_FORMS))
+@pytest.mark.parametrize('name', list(STAGED_WORLDS))
+def test_g_staged_scored_blocks(worlds, name, form):
+    """k_cost's output under staging, bit for bit: the tiles are cut at the stage bounds (k_tile_count, k_stage_plan, k_tile_emit per stage),
+    stage s scores into buffer s % nbuf, and "cost" puts the rows together again.  Eleven chunks of 1 (mod 64) sites in one batch (STAGED_LENGTHS:
+    a last stage of one start site for every bound of every form, two chunks that end before the second stage begins), on an all-narrow
+    world, on test_c's world with the three tile classes and two LDS sample groups, and on test_d's wide tiles fed by the carries.  Each call
+    runs twice on its context and once more behind a job of another shape: no counter, third buffer or event of an earlier call may show."""
+    stages, gate, pct = STAGED_FORMS[form]
+    world = _staged_world(worlds, name)
+    lengths = [c[1] for c in world[2]]
+    assert all(l % 64 == 1 for l in lengths) and max(lengths) != lengths[0]
+    gated = int(gate != 'off')
+    want_pct = pct if pct is not None else (_default_last_pct(world) if gated else 100)
+    with _segmenter(FORCE_STAGES=stages, LAST_STAGE_PCT=pct, **GATES[gate]) as sg:
+        for visit in ('first call', 'second call', 'after a job of another shape'):
+            if visit == 'after a job of another shape':
+                sg.segment_chunks([5, 2001, 4099], [1900, 2000, 2500], 100.0, 200, 10**6)
+                assert sg.last_plan()['bounds'] != staging.expected_bounds(1025, stages, want_pct)
+            label = '%s world, %s, %s' % (name, form, visit)
+            t = _run(sg, world, ('window', 'cum', 'back'), label)
+            plan = _form(sg, world, label, stages=stages, gated=gated, last_pct=want_pct, dp_mode=staging.auto_dp_mode(t['max_window']))
+            im.check_call(sg, world[4], [e.borders for e in world[4]], ('cost',), label)      # (after the form: three UNGATED stages would have no "cost")
+            assert plan['n_stages'] == stages and plan['nbuf'] == (3 if gated and stages == 3 else 2) and plan['n_chunks'] == len(lengths), (label, plan)
+            assert plan['all_narrow'] == (name == 'narrow') and plan['dp16'] == [int(name == 'narrow')] * (stages - 1) + [0], (label, plan)
+            for b in plan['bounds'][1:-1]:                     # a chunk whose last stage is the one start site at the bound, chunks with nothing behind it
+                assert b + 1 in lengths and min(lengths) < b, (label, plan)
+            if name != 'narrow':                               # wide tiles (and, on test_c's world, medium ones) beside the narrow ones
+                tiles = np.asarray(plan['stage_tiles']).sum(axis=0)
+                assert tiles[0] > 0 and tiles[1] > 0 and (name != 'classes' or tiles[2] > 0), (label, plan)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# h. the hooks on staged calls
+# ---------------------------------------------------------------------------------------------------------
+def test_h_last_plan_needs_a_finished_call(worlds):
+    """last_plan() before any call, and after set_betas (which invalidates what the last call left), is WGBSSEG_E_STATE; so is "cost" after a
+    call of seven stages, whose later stages have overwritten the earlier ones' blocks."""
+    world = _staged_world(worlds, 'narrow')
+    with _segmenter(FORCE_STAGES=7, **GATES['slack1']) as sg:
+        with pytest.raises(_lib.SegmentorError) as e:
+            sg.last_plan()
+        assert e.value.code == _lib.E_STATE
+        _run(sg, world, ('window', 'cum', 'back'), 'seven stages')
+        plan = _form(sg, world, 'seven stages', stages=7, gated=1, last_pct=_default_last_pct(world), dp_mode=0)
+        assert plan['n_stages'] > plan['nbuf'] == 3
+        with pytest.raises(_lib.SegmentorError) as e:
+            sg.debug_fetch('cost', np.float64, sum(x.cost.size for x in world[4]))
+        assert e.value.code == _lib.E_STATE
+        sg.set_betas(world[0])
+        with pytest.raises(_lib.SegmentorError) as e:
+            sg.last_plan()
+        assert e.value.code == _lib.E_STATE
+
+
+@pytest.mark.parametrize('gate', ['off', 'slack1'])
+def test_h_dense_cost_of_a_staged_batch_equals_the_chunks_fetched_alone(seg1, worlds, gate):
+    """test_f's property for a two-stage batch: chunks of 1, 7, 9, 1025 and 300 sites at odd offsets — the dense "cost" (and window / cum / back)
+    of the staged batch is the concatenation of the same chunks fetched from one-stage calls of one chunk each."""
+    def build():
+        slices, loci = cases.medium_tile_world(3, 'mix')
+        return slices, loci, [(3, 1), (11, 7), (101, 9), (777, 1025), (2501, 300)], (15.0, 100, 10**6)
+    world = worlds('hook', build)
+    slices, loci, chunks, params, exp = world
+    seg1.set_betas(slices)
+    seg1.set_loci(loci)
+    alone = {w: [] for w in ALL}
+    for (a, l), e in zip(chunks, exp):
+        seg1.segment_chunks([a], [l], *params)
+        assert seg1.last_plan()['n_stages'] == 1
+        for w in ALL:
+            alone[w].append(im.fetch(seg1, w, [e]))
+    with _segmenter(FORCE_STAGES=2, **GATES[gate]) as sg:
+        _run(sg, world, ALL, 'the batch in two stages')
+        plan = _form(sg, world, 'the batch in two stages', stages=2, gated=int(gate != 'off'), dp_mode=1)
+        assert plan['n_stages'] == 2 and plan['n_chunks'] == len(chunks)
+        for w in ALL:
+            got, want = im.fetch(sg, w, exp), np.concatenate(alone[w])
+            assert got.dtype == want.dtype and np.array_equal(got, want), '%s: %s' % (w, im._first_diff(got, want))
+        with pytest.raises(_lib.SegmentorError) as e:              # a buffer that is too small is refused, not cut
+            sg.debug_fetch('cost', np.float64, sum(x.cost.size for x in exp) - 1)
+        assert e.value.code == _lib.E_CAPACITY

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import cases
+import staging
 from intermediates import _first_diff, _numpy_windows
 from oracle import oracle
 from wgbs_tools_amd import _lib, synth
@@ -290,6 +291,7 @@ def test_05_intermediates_match_oracle(name, golden_chunks):
         slices, loci = _load_case(sg, spec)
         n, max_cpg = spec['n'], spec['max_cpg']
         got = sg.segment_chunks([0], [n], spec['pcount'], max_cpg, spec['max_bp'])[0]
+        staging.assert_form(sg.last_plan(), n, stages=1, gated=0, label=name)
         W = _numpy_windows(loci, max_cpg, spec['max_bp'])
         gW = sg.debug_fetch('window', np.uint16, n).astype(np.int64)
         assert _first_diff(gW, W) is None, 'window: ' + _first_diff(gW, W)
@@ -365,6 +367,10 @@ def test_07_staging_does_not_change_borders(stages, golden_chunks):
             got = sg.segment_chunks([0], [spec['n']], spec['pcount'], spec['max_cpg'], spec['max_bp'])[0]
             assert got.tolist() == g['borders'], '%s with %d stages: %s' % (name, stages, _first_diff(got, np.array(g['borders'])))
             assert sg.timings()['n_stages'] >= min(stages, 2)
+            # the form that ran: the bounds of `stages` forced stages; gated (the default switches) only with no other context alive on the device
+            plan = staging.assert_form(sg.last_plan(), spec['n'], stages=stages, dp_mode=staging.auto_dp_mode(sg.timings()['max_window']),
+                                       default_gate=True, label='%s, %d stages' % (name, stages))
+            assert plan['n_stages'] == sg.timings()['n_stages']
     finally:
         sg.close()
 
@@ -372,8 +378,10 @@ def test_07_staging_does_not_change_borders(stages, golden_chunks):
 @pytest.mark.parametrize('stages,slack,last_pct', [(3, 1, 100), (7, 8, 40), (8, 4096, 300), (5, 64, 200)])
 def test_07c_gated_stages_and_a_short_last_stage(stages, slack, last_pct, golden_chunks):
     """A staged all-narrow job with its stages alternating between the two scoring streams behind k_stage_gate (WGBSSEG_STAGE_GATE = tiles of
-    slack) and with a LAST stage shorter than the others (WGBSSEG_LAST_STAGE_PCT): only the timing may change.  Cases with wider windows take
-    the ungated path under the same switches."""
+    slack) and with a LAST stage shorter than the others (WGBSSEG_LAST_STAGE_PCT): only the timing may change.  Cases with wider windows
+    (dense_w_gt_64, deep) are gated under the same switches too, as last_plan() shows: WGBSSEG_STAGE_GATE_SHARED=1 lifts both the
+    one-context rule and the evaluations-per-step threshold that keeps a job with medium / wide tiles off the gate by default (plan_stages);
+    their recurrences are the 32-step builds, so no stage of theirs runs k_dp16."""
     os.environ['WGBSSEG_FORCE_STAGES'] = str(stages)
     os.environ['WGBSSEG_STAGE_GATE'] = str(slack)
     os.environ['WGBSSEG_LAST_STAGE_PCT'] = str(last_pct)
@@ -392,6 +400,9 @@ def test_07c_gated_stages_and_a_short_last_stage(stages, slack, last_pct, golden
                 got = sg.segment_chunks([0], [spec['n']], spec['pcount'], spec['max_cpg'], spec['max_bp'])[0]
                 assert got.tolist() == g['borders'], '%s with %d gated stages: %s' % (name, stages, _first_diff(got, np.array(g['borders'])))
                 assert sg.timings()['n_stages'] >= 2
+                plan = staging.assert_form(sg.last_plan(), spec['n'], stages=stages, gated=1, last_pct=last_pct,
+                                           dp_mode=staging.auto_dp_mode(sg.timings()['max_window']), label='%s, %d gated stages' % (name, stages))
+                assert plan['n_stages'] >= 2 and plan['all_narrow'] == (sg.timings()['max_window'] <= 60)
             g = golden_chunks['chr21']
             spec = g['spec']
             _load_case(sg, spec)
@@ -400,6 +411,8 @@ def test_07c_gated_stages_and_a_short_last_stage(stages, slack, last_pct, golden
             res = sg.segment_chunks(starts, lens, spec['pcount'], spec['max_cpg'], spec['max_bp'])
             for c, (got, want) in enumerate(zip(res, g['borders'])):
                 assert got.tolist() == want, 'chr21 chunk %d, %d gated stages: %s' % (c, stages, _first_diff(got, np.array(want)))
+            plan = staging.assert_form(sg.last_plan(), int(lens.max()), stages=stages, gated=1, last_pct=last_pct, label='chr21, %d gated stages' % stages)
+            assert plan['n_stages'] >= 2 and plan['n_chunks'] == len(starts)
     finally:
         sg.close()
 
@@ -423,6 +436,9 @@ def test_07b_wide_window_recurrence_on_every_case(mode, stages, golden_chunks):
             _load_case(sg, spec)
             got = sg.segment_chunks([0], [spec['n']], spec['pcount'], spec['max_cpg'], spec['max_bp'])[0]
             assert got.tolist() == g['borders'], '%s, dp mode %d, %d stages: %s' % (name, mode, stages, _first_diff(got, np.array(g['borders'])))
+            plan = staging.assert_form(sg.last_plan(), spec['n'], stages=stages or None, dp_mode=max(mode, staging.auto_dp_mode(sg.timings()['max_window'])),
+                                       default_gate=True, label='%s, dp mode %d, %d stages' % (name, mode, stages))
+            assert plan['dp16'] == [0] * plan['n_stages']            # a forced wide build: k_dp16 in no stage
         g = golden_chunks['chr21']
         spec = g['spec']
         _load_case(sg, spec)
@@ -431,6 +447,8 @@ def test_07b_wide_window_recurrence_on_every_case(mode, stages, golden_chunks):
         res = sg.segment_chunks(starts, lens, spec['pcount'], spec['max_cpg'], spec['max_bp'])
         for c, (got, want) in enumerate(zip(res, g['borders'])):
             assert got.tolist() == want, 'chr21 chunk %d, dp mode %d: %s' % (c, mode, _first_diff(got, np.array(want)))
+        staging.assert_form(sg.last_plan(), int(lens.max()), stages=stages or None, dp_mode=max(mode, staging.auto_dp_mode(sg.timings()['max_window'])),
+                            default_gate=True, label='chr21, dp mode %d, %d stages' % (mode, stages))
     finally:
         sg.close()
 

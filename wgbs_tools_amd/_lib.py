@@ -23,11 +23,11 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 350          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 351          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
-           'wgbsseg_get_timings', 'wgbsseg_debug_fetch', 'wgbsseg_debug_sample_terms', 'wgbsseg_debug_log2',
+           'wgbsseg_get_timings', 'wgbsseg_debug_fetch', 'wgbsseg_debug_last_plan', 'wgbsseg_debug_sample_terms', 'wgbsseg_debug_log2',
            'wgbsseg_debug_div', 'wgbsseg_debug_check_div', 'wgbsseg_debug_div_short', 'wgbsseg_add_loci', 'wgbsseg_add_loci_borders', 'wgbsseg_block_sums', 'wgbsseg_last_block_sums_ms',
            'wgbsseg_set_site_base', 'wgbsseg_stitch_regions', 'wgbsseg_group_create', 'wgbsseg_group_destroy', 'wgbsseg_group_size',
            'wgbsseg_group_plan', 'wgbsseg_group_load_host', 'wgbsseg_group_share_set_device', 'wgbsseg_group_segment_regions', 'wgbsseg_group_segment_region_range',
@@ -187,6 +187,8 @@ def load():
     L.wgbsseg_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.wgbsseg_debug_fetch.restype = i64
     L.wgbsseg_debug_fetch.argtypes = [vp, C.c_char_p, vp, i64]
+    L.wgbsseg_debug_last_plan.restype = i64
+    L.wgbsseg_debug_last_plan.argtypes = [vp, vp, i64]
     L.wgbsseg_debug_sample_terms.restype = i32
     L.wgbsseg_debug_sample_terms.argtypes = [vp, vp, vp, i64, C.c_float, vp]
     L.wgbsseg_debug_log2.restype = i32
@@ -716,6 +718,21 @@ class Segmenter:
         if got < 0:
             raise SegmentorError(int(got), 'debug_fetch(%s) failed' % what)
         return out[:got // out.itemsize]
+
+    def last_plan(self):
+        """The form the last segment_chunks call took (include/wgbsseg.h, wgbsseg_debug_last_plan): n_stages, gated, nbuf, last_pct, dp_mode,
+        all_narrow, live_contexts, n_chunks; bounds [n_stages + 1]; dp16 [n_stages]; stage_tiles [n_stages][3] (narrow, wide, medium)."""
+        out = np.empty(9 + 5 * 4096, dtype=np.int64)
+        got = self._L.wgbsseg_debug_last_plan(self._h, out.ctypes.data, out.size)
+        if got < 0:
+            raise SegmentorError(int(got), 'last_plan failed')
+        s = int(out[0])
+        assert got == 9 + 5 * s
+        plan = dict(zip(('n_stages', 'gated', 'nbuf', 'last_pct', 'dp_mode', 'all_narrow', 'live_contexts', 'n_chunks'), (int(x) for x in out[:8])))
+        plan['bounds'] = out[8:9 + s].tolist()
+        plan['dp16'] = out[9 + s:9 + 2 * s].tolist()
+        plan['stage_tiles'] = out[9 + 2 * s:9 + 5 * s].reshape(s, 3).tolist()
+        return plan
 
     def debug_sample_terms(self, nmeth, ntotal, pcount):
         nmeth = np.ascontiguousarray(nmeth, dtype=np.float32)

@@ -160,6 +160,13 @@ struct wgbsseg_ctx {
     struct LastChunk { int64_t site_off; int32_t len; int64_t cost_row0, cost_rows; };
     std::vector<LastChunk> last_chunks;
     bool last_cost_rows_known = false;
+    // the last batch's plan, for wgbsseg_debug_last_plan: the form plan_stages chose and Batch::stages launched, copied when the batch ends (like last_chunks)
+    struct LastPlan {
+        int32_t n_stages = 0, gated = 0, nbuf = 0, last_pct = 0, dp_mode = 0, all_narrow = 0, live_ctx = 0, n_chunks = 0;
+        std::vector<int32_t> sb;             // [n_stages + 1] stage bounds
+        std::vector<int32_t> dp16;           // [n_stages] 1: the stage's recurrence was k_dp16
+        std::vector<int64_t> stage_tiles;    // [3 * n_stages] tiles per stage and class
+    } last_plan;
     long long cost_budget_bytes = 0;
     int force_stages = 0;
     bool counted_live = false;
@@ -926,6 +933,7 @@ struct BatchPlan {
     int dp_mode = 0;               // k_dp: 0 64-step batches, 1 32-step batches, 2 the same with 15 worker waves (deep windows)
     int ringN = 0; int64_t state_stride = 0;   // k_dp's ring of pending maxima (0: none) and its state per chunk, in doubles
     int nbuf = 1;                  // scored-block buffers
+    int live_ctx = 0;              // contexts alive on the device when the plan was made (what `gated` saw)
 };
 
 // dynamic LDS of a k_cost tile of class cls with ti start sites and ns samples per LDS group
@@ -1050,8 +1058,9 @@ void plan_stages(wgbsseg_ctx* c, const Job& job, const JobStatus& st, BatchPlan&
     // A job with medium / wide tiles (its recurrences are the 32-step kernels with the full LDS footprint, which lived on the drains: a share of 8, x 32 with islands,
     // 5.95 -> 6.4 ms under the gate) is gated only when it is clearly scoring-bound (x 100 with islands: 14.0 -> 13.3 ms): from 100,000 evaluations per step on.
     const double evals_per_step = (double)total_pairs * c->n_samples / std::max<double>(1.0, (double)job.max_len);
+    p.live_ctx = g_live_ctx[c->device & 63].load(std::memory_order_relaxed);
     p.gated = c->stage_gate > 0 && n_stages > 1 && (p.all_narrow || evals_per_step >= c->stage_gate_wide_evals || c->stage_gate_shared) &&
-              (c->stage_gate_shared || g_live_ctx[c->device & 63].load(std::memory_order_relaxed) == 1);
+              (c->stage_gate_shared || p.live_ctx == 1);
     // equal stages but the last (gated jobs only): its recurrence is the only one that runs with the chip to itself, at twice the pace of the others.
     // Which length: the recurrences of the other stages take ~50 ns per step beside the scoring, so while the scoring of a stage lasts no longer than 1.5 x its
     // recurrence (at 7e11 evaluations/s: up to ~52,000 evaluations per step of the longest chunk) the chain of recurrences is what the step waits for, and a last
@@ -1119,6 +1128,7 @@ struct Batch {
     BatchPlan plan;
     CostArgs ca[3];                      // per tile class
     std::vector<int64_t> tile0[3];       // per tile class: first tile of every stage (+ the total)
+    std::vector<int32_t> ran_dp16;       // per stage: 1 when its recurrence was launched as k_dp16 (wgbsseg_debug_last_plan)
     DevBuf* outb = nullptr; size_t out_head = 0;   // the result on the device: the CSR offsets, then from out_head the border lists
     bool marks = false;                  // (WGBSSEG_PROFILE=2) host clock: entry, tables up, windows queued, statistics here, scoring queued, everything queued, results here, return
     double hm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1464,6 +1474,7 @@ int Batch::stages(char* err, size_t errlen)
     const bool divsA = c->divs_enabled && c->divs_ok && c->divs_pc == P.pseudo_count;
     const bool divsM = c->divs_enabled && c->divs_m_ok && c->divs_m_pc == P.pseudo_count;
     const int fast[3] = {p.term_mode[0] == 2 && divsA ? 3 : p.term_mode[0], p.term_mode[1], p.term_mode[2] == 2 && divsM ? 3 : p.term_mode[2]};
+    ran_dp16.assign((size_t)n_stages, 0);
     for (int stg = 0; stg < n_stages; stg++) {
         const int64_t* const nt = &p.stage_tiles[3 * (size_t)stg];      // the stage's tiles per class
         hipStream_t const sP = p.gated && (stg & 1) ? c->sA2 : c->sA;
@@ -1503,6 +1514,7 @@ int Batch::stages(char* err, size_t errlen)
         // of 10 VALU instructions.
         // the LAST stage's recurrence has the chip to itself: the 64-step-batch kernel is twice as fast there
         const bool dp16 = p.dp_mode == 0 && n_stages > 1 && stg + 1 < n_stages;
+        ran_dp16[(size_t)stg] = dp16;
         if (dp16)                                  hipLaunchKernelGGL((k_dp16<3>), dim3((unsigned)nC), dim3(64 * 4), (size_t)(2 * 16 * 64 * 8 + WG_DP_META_RING * 6), c->sB, v, sv, cbuf, dps, p.state_stride);
         else if (p.dp_mode == 0 && p.all_narrow)   hipLaunchKernelGGL((k_dp<7, 64, true>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, dps, p.state_stride);
         else if (p.dp_mode == 0)                   hipLaunchKernelGGL((k_dp<7, 64>), dim3((unsigned)nC), dim3(64 * 8), lds_dp, c->sB, v, sv, cbuf, da, dps, p.state_stride);
@@ -1635,6 +1647,12 @@ int Batch::timings(char* err, size_t errlen)
     c->last_chunks.resize((size_t)nC);
     for (int i = 0; i < nC; i++) c->last_chunks[(size_t)i] = {job.h[(size_t)i].site_off, job.h[(size_t)i].len, 0, 0};
     c->last_cost_rows_known = false;
+    wgbsseg_ctx::LastPlan& lp = c->last_plan;
+    lp.n_stages = n_stages; lp.gated = plan.gated; lp.nbuf = plan.nbuf; lp.last_pct = plan.last_pct; lp.dp_mode = plan.dp_mode;
+    lp.all_narrow = plan.all_narrow; lp.live_ctx = plan.live_ctx; lp.n_chunks = nC;
+    lp.sb.assign(plan.sb, plan.sb + n_stages + 1);
+    lp.dp16 = ran_dp16;
+    lp.stage_tiles = plan.stage_tiles;
     c->batch_open = false;
     if (marks) {
         hm[7] = wall_s();
@@ -2467,6 +2485,46 @@ int64_t wgbsseg_format_fixed(const double* v, int64_t n, int32_t digits, char* o
 #include "pat_engines.h"      // the engines that take pat text in chunks (pat2beta, homog, frag_len, test_bimodal, view) and their entry points
 
 // what is left of the segmenter context's calls: its timings and the wgbsseg_debug_* views of its buffers and arithmetic
+namespace {
+
+// wgbsseg_debug_fetch("cost") of a staged job whose stages each kept a buffer to themselves (n_stages <= nbuf: stage s scored into cost[s % nbuf]).
+// A stage holds the WHOLE rows of the start sites [sb[s], min(sb[s+1], len)) of every chunk — a block that ends beyond the bound lies with its start
+// (k_stage_plan: a chunk's blocks in a stage are cum[s1] - cum[s0]; k_cost, k_dp: row k at cbase[s][chunk] + cum[k] - cum0[s][chunk]) — so chunk c's dense rows
+// are, stage after stage, one run of cum[s1] - cum[s0] blocks at cbase[s][c].  What k_stage_plan left in plan_cum0 must be the chunk's cum at the bound.
+int64_t fetch_staged_cost(wgbsseg_ctx* c, double* out)
+{
+    const std::vector<wgbsseg_ctx::LastChunk>& tab = c->last_chunks;
+    const wgbsseg_ctx::LastPlan& lp = c->last_plan;
+    const size_t nC = tab.size(), nS = (size_t)c->last_stages;
+    if (lp.n_stages != c->last_stages || lp.sb.size() != nS + 1 || (size_t)lp.n_chunks != nC) return WGBSSEG_E_STATE;
+    const size_t padded = (size_t)(tab.back().site_off + tab.back().len);
+    if (nS * nC * 8 > c->plan_cbase.cap || nS * nC * 4 > c->plan_cum0.cap || nC * 8 > c->chunk_pairs.cap || padded * 4 > c->cum32.cap) return WGBSSEG_E_STATE;
+    std::vector<int64_t> cbase(nS * nC), pairs(nC);
+    std::vector<uint32_t> cum0(nS * nC), cum(padded);
+    if (hipMemcpy(cbase.data(), c->plan_cbase.p, nS * nC * 8, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+    if (hipMemcpy(cum0.data(), c->plan_cum0.p, nS * nC * 4, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+    if (hipMemcpy(pairs.data(), c->chunk_pairs.p, nC * 8, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+    if (hipMemcpy(cum.data(), c->cum32.p, padded * 4, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+    int64_t at = 0;                                               // dense row 0 of the chunk
+    for (size_t i = 0; i < nC; i++) {
+        const int64_t len = tab[i].len;
+        if (pairs[i] < 0 || at + pairs[i] > c->last_pairs) return WGBSSEG_E_STATE;
+        for (size_t s = 0; s < nS && lp.sb[s] < len; s++) {       // (a chunk that ends before a stage begins has nothing in it)
+            const int64_t s0 = lp.sb[s], s1 = std::min<int64_t>(lp.sb[s + 1], len);
+            const int64_t r0 = cum[(size_t)(tab[i].site_off + s0)], r1 = s1 < len ? (int64_t)cum[(size_t)(tab[i].site_off + s1)] : pairs[i];
+            const int64_t src = cbase[s * nC + i];
+            if ((int64_t)cum0[s * nC + i] != r0 || r1 < r0 || r1 > pairs[i] || src < 0) return WGBSSEG_E_STATE;
+            const DevBuf& buf = c->cost[s % (size_t)lp.nbuf];
+            if ((size_t)(src + (r1 - r0)) * 8 > buf.cap) return WGBSSEG_E_STATE;
+            if (r1 > r0 && hipMemcpy(out + at + r0, buf.as<double>() + src, (size_t)(r1 - r0) * 8, hipMemcpyDeviceToHost) != hipSuccess) return WGBSSEG_E_HIP;
+        }
+        at += pairs[i];
+    }
+    return at == c->last_pairs ? c->last_pairs * 8 : (int64_t)WGBSSEG_E_STATE;
+}
+
+}  // namespace
+
 extern "C" {
 
 int wgbsseg_get_timings(const wgbsseg_ctx* c, wgbsseg_timings* out)
@@ -2516,10 +2574,12 @@ int64_t wgbsseg_debug_fetch(wgbsseg_ctx* c, const char* what, void* out, int64_t
     if (strcmp(what, "cost")) return WGBSSEG_E_ARG;
     // the scored blocks of a one-stage job: the rows of chunk 0, then of chunk 1, ...; where a chunk's rows lie in the cost buffer is the stage
     // plan's business (k_stage_plan: row 0 of plan_cbase), how many blocks it has the windows pass's (chunk_pairs)
-    if (c->last_stages != 1 || tab.empty()) return WGBSSEG_E_STATE;
+    if (c->last_stages < 1 || tab.empty()) return WGBSSEG_E_STATE;
+    if (c->last_stages > c->last_plan.nbuf) return WGBSSEG_E_STATE;        // a later stage has scored into an earlier one's buffer
     const int64_t bytes = c->last_pairs * 8;
     if (bytes > cap_bytes) return WGBSSEG_E_CAPACITY;
     if (hipSetDevice(c->device) != hipSuccess) return WGBSSEG_E_HIP;
+    if (c->last_stages > 1) return fetch_staged_cost(c, static_cast<double*>(out));
     if (!c->last_cost_rows_known) {
         const size_t nC = tab.size();
         if (nC * 8 > c->plan_cbase.cap || nC * 8 > c->chunk_pairs.cap) return WGBSSEG_E_STATE;
@@ -2540,6 +2600,21 @@ int64_t wgbsseg_debug_fetch(wgbsseg_ctx* c, const char* what, void* out, int64_t
         i = j;
     }
     return at == c->last_pairs ? bytes : (int64_t)WGBSSEG_E_STATE;
+}
+
+int64_t wgbsseg_debug_last_plan(const wgbsseg_ctx* c, int64_t* out, int64_t cap)
+{
+    if (!c || !out || !c->last_valid) return WGBSSEG_E_STATE;
+    const wgbsseg_ctx::LastPlan& lp = c->last_plan;
+    const int64_t nS = lp.n_stages, need = 8 + (nS + 1) + nS + 3 * nS;
+    if (nS < 1 || (int64_t)lp.sb.size() != nS + 1 || (int64_t)lp.dp16.size() != nS || (int64_t)lp.stage_tiles.size() != 3 * nS) return WGBSSEG_E_STATE;
+    if (cap < need) return WGBSSEG_E_CAPACITY;
+    const int64_t head[8] = {nS, lp.gated, lp.nbuf, lp.last_pct, lp.dp_mode, lp.all_narrow, lp.live_ctx, lp.n_chunks};
+    int64_t* o = std::copy(head, head + 8, out);
+    o = std::copy(lp.sb.begin(), lp.sb.end(), o);
+    o = std::copy(lp.dp16.begin(), lp.dp16.end(), o);
+    std::copy(lp.stage_tiles.begin(), lp.stage_tiles.end(), o);
+    return need;
 }
 
 int wgbsseg_debug_sample_terms(wgbsseg_ctx* c, const float* nmeth, const float* ntotal, int64_t count, float pseudo_count, float* out)
