@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 351            /* 0.3.5.1: wgbsseg_debug_last_plan (test hook: the staging form of the last call); wgbsseg_debug_fetch("cost") serves staged calls with n_stages <= nbuf.  0.3.5:wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 360            /* 0.3.6: wgbsseg_bedbeta_* (`wgbstools bed2beta`: BED methylation calls joined to the CpG dictionary on the device).  0.3.5.1: wgbsseg_debug_last_plan (test hook: the staging form of the last call); wgbsseg_debug_fetch("cost") serves staged calls with n_stages <= nbuf.  0.3.5:wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -788,6 +788,44 @@ int wgbsseg_patview_set_labels(wgbsseg_patview* v, const char* const* labels, in
 int32_t wgbsseg_patview_label_rank(const wgbsseg_patview* v, int64_t label);
 int wgbsseg_patview_set_source(wgbsseg_patview* v, int32_t label_rank, uint32_t T, int32_t reps, uint64_t seed, uint32_t stream, char* err, size_t errlen);
 void wgbsseg_patview_sample_info(wgbsseg_patview* v, int64_t* out);
+
+/*
+ * BED methylation calls -> .beta (`wgbstools bed2beta`: bed2beta.py:11-51, a pandas drop_duplicates and a left merge with the CpG
+ * dictionary; utils_wgbs.py:277-290 trim_to_uint8).  create(): loci[n_sites] (uint32, the bp position of every CpG; n_sites < 2^31), and
+ * the genome's chromosomes: chromosome k is named chrom_names[k] and owns the sites [chrom_lo[k], chrom_hi[k]) (0-based).  WGBSSEG_E_ARG,
+ * naming the chromosome, unless 1 <= n_chroms <= 65,535, the names are non-empty, distinct and free of tabs and newlines, the ranges are
+ * disjoint and inside [0, n_sites), and the loci ascend strictly inside every chromosome.  flags: WGBSSEG_BED_ADD_ONE (1): a line's
+ * position is start + 1; WGBSSEG_BED_HEADER (2): the line at byte offset 0 of the file is a header and is dropped unread (the caller
+ * decides: the reference takes the first line for a header exactly when its second field is not made of decimal digits only).  The loci
+ * and the table go to the device once, for all files.  feed() / feed_bgzf(): as for wgbsseg_homog (asynchronous, the text is copied; text
+ * or BGZF bytes, not both; at most 2^47 bytes of text per file).  Per line `chr \t start \t end \t #meth \t #total [\t ...]` — the third
+ * field and everything behind the fifth are not looked at, empty lines are skipped —: with p = start (+ 1) the line matches site i when
+ * chr equals a chromosome's name byte for byte and loci[i] == p inside that chromosome's sites.  A line on an unknown chromosome or at a
+ * position that is no CpG is dropped and counted.  Of several lines that match one site the FIRST in the file wins, however the file is
+ * cut into calls, tiles or BGZF members.  finish(): out[n_sites * 2] (host), per site the winning line's (#meth, #total), where #total >
+ * 255 stored as (trunc(#meth / #total * 255), 255) (float64, the reference's order of operations), 0, 0 for a site without a line;
+ * stats[6] (may be NULL) = lines read, lines matched, lines dropped for an unknown chromosome, lines dropped for not being a CpG,
+ * duplicates dropped among the matched lines, sites set.  It first feeds a last line that has no newline, then returns WGBSSEG_E_ARG for
+ * a BGZF member refused on the device, else "failed in bed2beta: the line at byte offset N of the input ..." for the lowest line that has
+ * fewer than five fields; whose start, #meth or #total is not 1 to 18 decimal digits and nothing else (no sign, no '.', no exponent, no
+ * '\r'); whose #total exceeds 2^31 - 1; or whose #meth exceeds its #total (the reference would wrap it).  next_file(): after finish(),
+ * before the next file's first feed: clears the table, the counters and the refusal, makes the feed forget the file (text or BGZF may
+ * change, byte and member offsets count from 0 again) and sets the next file's flags; WGBSSEG_E_ARG when the last feed_bgzf() left bytes
+ * over (no whole member).  kernel_ms / inflate_ms: device time (HIP events) of the k_bedbeta_scan / inflate launches so far, over all
+ * files; wait for them.
+ */
+#define WGBSSEG_BED_ADD_ONE 1
+#define WGBSSEG_BED_HEADER 2
+typedef struct wgbsseg_bedbeta wgbsseg_bedbeta;
+int wgbsseg_bedbeta_create(int device, const uint32_t* loci, int64_t n_sites, const char* const* chrom_names, const int64_t* chrom_lo,
+                           const int64_t* chrom_hi, int32_t n_chroms, int32_t flags, wgbsseg_bedbeta** out, char* err, size_t errlen);
+int wgbsseg_bedbeta_feed(wgbsseg_bedbeta* b, const char* text, int64_t n_bytes, char* err, size_t errlen);
+int wgbsseg_bedbeta_feed_bgzf(wgbsseg_bedbeta* b, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen);
+int wgbsseg_bedbeta_finish(wgbsseg_bedbeta* b, uint8_t* out, int64_t* stats, char* err, size_t errlen);
+int wgbsseg_bedbeta_next_file(wgbsseg_bedbeta* b, int32_t flags, char* err, size_t errlen);
+void wgbsseg_bedbeta_destroy(wgbsseg_bedbeta* b);
+double wgbsseg_bedbeta_kernel_ms(wgbsseg_bedbeta* b);
+double wgbsseg_bedbeta_inflate_ms(wgbsseg_bedbeta* b);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

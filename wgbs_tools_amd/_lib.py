@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 351          # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 360        # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -53,7 +53,9 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_patview_destroy', 'wgbsseg_patview_kernel_ms', 'wgbsseg_patview_inflate_ms', 'wgbsseg_patview_phase_ms', 'wgbsseg_patview_info',
            'wgbsseg_patview_next_file', 'wgbsseg_merge_rows', 'wgbsseg_last_merge_rows_ms',
            'wgbsseg_patview_set_mask', 'wgbsseg_patview_mask_info', 'wgbsseg_patview_mask_ms',
-           'wgbsseg_patview_set_labels', 'wgbsseg_patview_label_rank', 'wgbsseg_patview_set_source', 'wgbsseg_patview_sample_info']
+           'wgbsseg_patview_set_labels', 'wgbsseg_patview_label_rank', 'wgbsseg_patview_set_source', 'wgbsseg_patview_sample_info',
+           'wgbsseg_bedbeta_create', 'wgbsseg_bedbeta_feed', 'wgbsseg_bedbeta_feed_bgzf', 'wgbsseg_bedbeta_finish', 'wgbsseg_bedbeta_next_file',
+           'wgbsseg_bedbeta_destroy', 'wgbsseg_bedbeta_kernel_ms', 'wgbsseg_bedbeta_inflate_ms']
 
 
 class NativeLibraryError(RuntimeError):
@@ -349,7 +351,19 @@ def load():
     L.wgbsseg_merge_rows.argtypes = [vp, vp, i32, i32, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_last_merge_rows_ms.restype = C.c_double
     L.wgbsseg_last_merge_rows_ms.argtypes = [vp]
-    for eng in ('patbeta', 'homog', 'bimodal', 'fraglen', 'patview'):
+    L.wgbsseg_bedbeta_create.restype = i32
+    L.wgbsseg_bedbeta_create.argtypes = [i32, vp, i64, C.POINTER(C.c_char_p), vp, vp, i32, i32, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.wgbsseg_bedbeta_feed.restype = i32
+    L.wgbsseg_bedbeta_feed.argtypes = [vp, C.c_char_p, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_bedbeta_finish.restype = i32
+    L.wgbsseg_bedbeta_finish.argtypes = [vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_bedbeta_next_file.restype = i32
+    L.wgbsseg_bedbeta_next_file.argtypes = [vp, i32, C.c_char_p, C.c_size_t]
+    L.wgbsseg_bedbeta_destroy.restype = None
+    L.wgbsseg_bedbeta_destroy.argtypes = [vp]
+    L.wgbsseg_bedbeta_kernel_ms.restype = C.c_double
+    L.wgbsseg_bedbeta_kernel_ms.argtypes = [vp]
+    for eng in ('patbeta', 'homog', 'bimodal', 'fraglen', 'patview', 'bedbeta'):
         f = getattr(L, 'wgbsseg_%s_feed_bgzf' % eng)
         f.restype = i32
         f.argtypes = [vp, C.c_char_p, i64, C.POINTER(i64), C.c_char_p, C.c_size_t]
@@ -883,6 +897,47 @@ class FragLen(_PatFeed):
         out = np.empty(self.max_frag, dtype=np.int64)
         self._call('finish', self._h, out.ctypes.data)
         return out
+
+
+class BedBeta(_PatFeed):
+    """wgbsseg_bedbeta: BED text `chr, start, end, #meth, #total` -> the uint8 (#meth, #total) rows of a .beta file on one GPU.  loci: the
+    uint32 bp position of every CpG; chrom_names / chrom_sizes: the genome's chromosomes in the order of the loci (CpG.chrome.size), or
+    chrom_ranges=(lo, hi): their 0-based site ranges given outright.  One engine serves many files: finish(), then next_file()."""
+    _abi = 'bedbeta'
+    ADD_ONE, HEADER = 1, 2
+
+    def __init__(self, loci, chrom_names, chrom_sizes=None, add_one=False, header=False, device=0, chrom_ranges=None):
+        super().__init__()
+        loci = np.ascontiguousarray(loci, dtype=np.uint32)
+        if chrom_ranges is None:
+            hi = np.cumsum(np.asarray(chrom_sizes, dtype=np.int64))
+            lo = hi - np.asarray(chrom_sizes, dtype=np.int64)
+        else:
+            lo, hi = chrom_ranges
+        lo = np.ascontiguousarray(lo, dtype=np.int64)
+        hi = np.ascontiguousarray(hi, dtype=np.int64)
+        raw = [c if isinstance(c, bytes) else str(c).encode() for c in chrom_names]
+        if lo.shape != hi.shape or lo.ndim != 1 or lo.size != len(raw):
+            raise ValueError('one name and one range per chromosome')
+        names = (C.c_char_p * max(len(raw), 1))(*raw)
+        self.n_sites = int(loci.size)
+        self._call('create', int(device), loci.ctypes.data if loci.size else None, self.n_sites, names, lo.ctypes.data if lo.size else None,
+                   hi.ctypes.data if hi.size else None, len(raw), self.flags_of(add_one, header), C.byref(self._h))
+
+    @classmethod
+    def flags_of(cls, add_one, header):
+        return (cls.ADD_ONE if add_one else 0) | (cls.HEADER if header else 0)
+
+    def finish(self):
+        """-> (uint8 rows [n_sites, 2], stats: lines, matched, unknown_chrom, not_cpg, duplicates, sites_set)"""
+        out = np.empty((self.n_sites, 2), dtype=np.uint8)
+        stats = np.zeros(6, dtype=np.int64)
+        self._call('finish', self._h, out.ctypes.data, stats.ctypes.data)
+        return out, dict(zip(('lines', 'matched', 'unknown_chrom', 'not_cpg', 'duplicates', 'sites_set'), stats.tolist()))
+
+    def next_file(self, add_one=False, header=False):
+        """between two files, after finish(): nothing of the file before stays"""
+        self._call('next_file', self._h, self.flags_of(add_one, header))
 
 
 class PatView(_PatFeed):

@@ -1,6 +1,7 @@
-// pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_fraglen, wgbsseg_bimodal, wgbsseg_patview), the feed they share
+// pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_fraglen, wgbsseg_bimodal, wgbsseg_patview) and the one that takes BED
+// text the same way (wgbsseg_bedbeta, at the end), the feed they share
 // (PatFeed, PrevRead), the stand-alone wgbsseg_bgzf_inflate and their extern "C" entry points.  Part of wgbsseg.hip, which includes it once set_err, HIP_TRY, check_device and the owners are
-// in scope; what an engine decides on the host is in homog_plan.h, frag_plan.h, bimodal_plan.h and view_plan.h, this file stages, launches and fetches.
+// in scope; what an engine decides on the host is in homog_plan.h, frag_plan.h, bimodal_plan.h, view_plan.h and bed2beta_plan.h, this file stages, launches and fetches.
 #pragma once
 
 // The pat-text feed of an engine (wgbsseg_patbeta / _homog / _fraglen / _bimodal / _patview): one device and stream; text chunks through two page-locked
@@ -1424,6 +1425,148 @@ void wgbsseg_patview_info(const wgbsseg_patview* v, int64_t* out)
 {
     if (!v || !out) return;
     out[0] = v->n_recs; out[1] = v->n_arena; out[2] = v->grown_recs; out[3] = v->grown_arena; out[4] = v->passes; out[5] = v->order;
+}
+
+}  // extern "C"
+
+// `wgbstools bed2beta` accumulator on one device: the loci and the chromosome table (bed2beta_plan.h) uploaded once, one 64-bit word per
+// site that k_bedbeta_scan lowers to the first matching line of the file (timed), the report words; finish() unpacks the table into the
+// .beta bytes, next_file() clears it for the next file.
+struct wgbsseg_bedbeta {
+    static constexpr const char* name = "bedbeta";
+    PatFeed feed;
+    BedBetaPlan plan;
+    int32_t flags = 0;
+    DevBuf loci, chroms, table, outb, report;
+    int64_t bgzf_left = 0;                                        // bytes the last feed_bgzf did not take
+    unsigned long long* dev_report() const { return report.as<unsigned long long>(); }
+    ~wgbsseg_bedbeta() { feed.drain(); }
+};
+
+// the table all ones, the report: no refused line, the counters 0 (queued on the feed's stream)
+static hipError_t bedbeta_clear(wgbsseg_bedbeta* b)
+{
+    hipError_t e = hipMemsetAsync(b->table.p, 0xff, (size_t)b->plan.n_words * 8, b->feed.st);
+    if (e == hipSuccess) e = hipMemsetAsync(b->report.p, 0xff, 8, b->feed.st);
+    if (e == hipSuccess) e = hipMemsetAsync(b->dev_report() + 1, 0, (WG_BB_REP_WORDS - 1) * 8, b->feed.st);
+    return e;
+}
+
+// a staged chunk of n_bytes / gx tiles: k_bedbeta_scan over it
+template <class Stage>
+static int pat_chunk(wgbsseg_bedbeta* b, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    std::string msg;
+    const int rc = plan_bedbeta_chunk(b->feed.fed, n_bytes, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    return PatFeed::one_launch(b, n_bytes, gx, stage, err, errlen, [] { return hipSuccess; }, [&](unsigned gx, const char* dtext) {
+        hipLaunchKernelGGL(k_bedbeta_scan, dim3(gx), dim3(WG_BLOCK), 0, b->feed.st, dtext, n_bytes, b->plan.view_at(b->chroms.as<const char>()),
+                           b->loci.as<const uint32_t>(), (b->flags & WG_BB_ADD_ONE) ? 1 : 0, (b->flags & WG_BB_HEADER) ? 1 : 0,
+                           b->table.as<unsigned long long>(), b->dev_report(), b->feed.fed);
+    });
+}
+
+extern "C" {
+
+// plan (bed2beta_plan.h) -> the loci and the chromosome table on the device, the table and the report cleared
+int wgbsseg_bedbeta_create(int device, const uint32_t* loci, int64_t n_sites, const char* const* chrom_names, const int64_t* chrom_lo,
+                           const int64_t* chrom_hi, int32_t n_chroms, int32_t flags, wgbsseg_bedbeta** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    BedBetaPlan plan;
+    std::string msg;
+    int rc = plan_bedbeta(loci, n_sites, chrom_names, chrom_lo, chrom_hi, n_chroms, flags, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    std::unique_ptr<wgbsseg_bedbeta> b(new (std::nothrow) wgbsseg_bedbeta());      // (a failing call below frees what has been made)
+    if (!b) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    rc = b->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    b->plan = std::move(plan);
+    b->flags = flags;
+    const BedBetaPlan& p = b->plan;
+    std::vector<char> tab(p.upload_bytes());
+    p.upload_to(tab.data());
+    HIP_TRY(b->loci.ensure((size_t)n_sites * 4)); HIP_TRY(b->chroms.ensure(tab.size()));
+    HIP_TRY(b->table.ensure((size_t)p.n_words * 8)); HIP_TRY(b->outb.ensure((size_t)p.n_words * 2)); HIP_TRY(b->report.ensure(WG_BB_REP_WORDS * 8));
+    HIP_TRY(hipMemcpy(b->loci.p, loci, (size_t)n_sites * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b->chroms.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(bedbeta_clear(b.get()));
+    *out = b.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_bedbeta_destroy(wgbsseg_bedbeta* b) { delete b; }
+
+int wgbsseg_bedbeta_feed(wgbsseg_bedbeta* b, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    return PatFeed::feed_text(b, text, n_bytes, err, errlen);
+}
+
+int wgbsseg_bedbeta_feed_bgzf(wgbsseg_bedbeta* b, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+{
+    const int rc = PatFeed::feed_bgzf(b, bytes, n_bytes, consumed, err, errlen);
+    if (rc == WGBSSEG_OK) b->bgzf_left = n_bytes - *consumed;
+    return rc;
+}
+
+// the carry; a refused BGZF member before a refused line; then the table unpacked into the .beta bytes, and the counters
+int wgbsseg_bedbeta_finish(wgbsseg_bedbeta* b, uint8_t* out, int64_t* stats, char* err, size_t errlen)
+{
+    if (!b || !out) { set_err(err, errlen, "bad arguments to bedbeta_finish"); return WGBSSEG_E_ARG; }
+    const hipStream_t st = b->feed.st;
+    HIP_TRY(hipSetDevice(b->feed.device));
+    int rc = PatFeed::flush_carry(b, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    unsigned long long rep[WG_BB_REP_WORDS];
+    HIP_TRY(hipMemcpyAsync(rep, b->report.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    rc = b->feed.inflate_refused(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    std::string msg;
+    if (wg_bb_refusal(rep[WG_BB_REP_BAD], msg)) { set_err(err, errlen, "%s", msg.c_str()); return WGBSSEG_E_ARG; }
+    const int64_t n_threads = b->plan.n_words / WG_BB_UNPACK_SITES;
+    HIP_TRY(hipMemsetAsync(b->dev_report() + WG_BB_REP_SET, 0, 8, st));      // (finish() may be called again)
+    hipLaunchKernelGGL(k_bedbeta_unpack, dim3((unsigned)((n_threads + WG_BLOCK - 1) / WG_BLOCK)), dim3(WG_BLOCK), 0, st,
+                       b->table.as<const unsigned long long>(), n_threads, b->outb.as<uint8_t>(), b->dev_report());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, b->outb.p, (size_t)b->plan.n_sites * 2, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(rep, b->report.p, sizeof(rep), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (stats) {
+        stats[0] = (int64_t)rep[WG_BB_REP_LINES]; stats[1] = (int64_t)rep[WG_BB_REP_MATCHED];
+        stats[2] = (int64_t)rep[WG_BB_REP_NO_CHROM]; stats[3] = (int64_t)rep[WG_BB_REP_NO_CPG];
+        stats[4] = (int64_t)(rep[WG_BB_REP_MATCHED] - rep[WG_BB_REP_SET]); stats[5] = (int64_t)rep[WG_BB_REP_SET];
+    }
+    return WGBSSEG_OK;
+}
+
+// Between two files: BGZF bytes left over are refused; the feed forgets the file — text or BGZF, the member offset, the carry, the bytes
+// fed (offsets count from 0 again) —, the table, the report and the counters are cleared, and `flags` are the next file's.
+int wgbsseg_bedbeta_next_file(wgbsseg_bedbeta* b, int32_t flags, char* err, size_t errlen)
+{
+    if (!b) { set_err(err, errlen, "bad arguments to bedbeta_next_file"); return WGBSSEG_E_ARG; }
+    std::string msg;
+    const int rc = plan_bedbeta_flags(flags, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    if (b->bgzf_left) { set_err(err, errlen, "bedbeta_next_file: %lld bytes behind the file's last whole BGZF member", (long long)b->bgzf_left); return WGBSSEG_E_ARG; }
+    PatFeed& f = b->feed;
+    HIP_TRY(hipSetDevice(f.device));
+    HIP_TRY(bedbeta_clear(b));
+    f.mode = 0; f.file_off = 0; f.fed = 0; f.carry.clear();
+    b->bgzf_left = 0;
+    b->flags = flags;
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_bedbeta_kernel_ms(wgbsseg_bedbeta* b)
+{
+    return b ? b->feed.kernel_ms() : -1.0;
+}
+
+double wgbsseg_bedbeta_inflate_ms(wgbsseg_bedbeta* b)
+{
+    return b ? b->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
 }
 
 }  // extern "C"

@@ -51,6 +51,8 @@
 #include "pair_kernels.h"
 #include "bed_kernels.h"
 #include "array_kernels.h"
+#include "bed2beta_plan.h"
+#include "bed2beta_kernels.h"
 #include "plain_dp.h"
 #include "stitch.h"
 #include "add_loci.h"

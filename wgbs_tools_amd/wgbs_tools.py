@@ -11,18 +11,21 @@ and formatted on the device), `frag_len` (the histogram of a pat file's read len
 view.main) and `merge` (the pat files or the beta files of replicates pooled into one: the reads of all files through the one view engine,
 the beta rows summed and saturated by one kernel) and `mask_pat` (a pat file with the sites of a blocks table hidden from every read: the same
 view engine with a bitmap of hidden sites inside its cut) and `mix_pat` (in-silico mixtures of pat files: the same view engine thins every
-file's reads by a counter-based binomial draw, tags them with their source and orders tied lines as the reference's `sort -m` does); every other reference subcommand is out of scope and says so."""
+file's reads by a counter-based binomial draw, tags them with their source and orders tied lines as the reference's `sort -m` does) and
+`bed2beta` (BED methylation calls of any pipeline joined to the CpG dictionary on the device, the first of duplicated lines kept: the door
+into the `.beta` files everything above reads); every other reference subcommand is out of scope and says so."""
 import sys
 
 from .genome import IllegalArgumentError, eprint
 
 VERSION = '0.2.0-mi355x'
 COMMANDS = ['segment', 'convert', 'pat2beta', 'beta_to_blocks', 'beta_to_table', 'find_markers', 'homog', 'test_bimodal',
-            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k', 'frag_len', 'view', 'cview', 'merge', 'mask_pat', 'mix_pat']
+            'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k', 'frag_len', 'view', 'cview', 'merge', 'mask_pat', 'mix_pat',
+            'bed2beta']
 MODULES = {'cview': 'view'}            # commands that run another command's module
 # reference command list (wgbs_tools.py:11-48), for the "not in this build" message.  `view` is in both lists: COMMANDS is looked at first and
 # carries its pat side; of a .beta / .lbeta input view.py itself says that it is not part of this build (and names `beta2bed`).  `merge` likewise:
-# merge.py says what of it (--labels, -L, .bin) is not part of this build; `mix_pat`: mix_pat.py says it of -L
+# merge.py says what of it (--labels, -L, .bin) is not part of this build; `mix_pat`: mix_pat.py says it of -L; `bed2beta`: bed2beta.py says it of -d
 REFERENCE_ONLY = ['view', 'merge', 'index',
                   'beta2bw', 'bam2pat', 'mbias', 'init_genome', 'set_default_ref', 'vis', 'pat_fig',
                   'dmb', 'mix_pat', 'bed2beta',
