@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 360            /* 0.3.6: wgbsseg_bedbeta_* (`wgbstools bed2beta`: BED methylation calls joined to the CpG dictionary on the device).  0.3.5.1: wgbsseg_debug_last_plan (test hook: the staging form of the last call); wgbsseg_debug_fetch("cost") serves staged calls with n_stages <= nbuf.  0.3.5:wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 370            /* 0.3.7: wgbsseg_patview_set_sam, wgbsseg_patview_sam_info (`wgbstools bam2pat`: SAM reads called, paired and merged on the device).  0.3.6: wgbsseg_bedbeta_* (`wgbstools bed2beta`: BED methylation calls joined to the CpG dictionary on the device).  0.3.5.1: wgbsseg_debug_last_plan (test hook: the staging form of the last call); wgbsseg_debug_fetch("cost") serves staged calls with n_stages <= nbuf.  0.3.5:wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -788,6 +788,38 @@ int wgbsseg_patview_set_labels(wgbsseg_patview* v, const char* const* labels, in
 int32_t wgbsseg_patview_label_rank(const wgbsseg_patview* v, int64_t label);
 int wgbsseg_patview_set_source(wgbsseg_patview* v, int32_t label_rank, uint32_t T, int32_t reps, uint64_t seed, uint32_t stream, char* err, size_t errlen);
 void wgbsseg_patview_sample_info(wgbsseg_patview* v, int64_t* out);
+
+/*
+ * SAM text in place of pat text (`wgbstools bam2pat`: src/python/bam2pat.py:144-209, src/pipeline_wgbs/patter.cpp, patter_utils.cpp):
+ * set_sam() once, after create() and before the first feed (WGBSSEG_E_STATE otherwise, and on an engine that has a mask or labels;
+ * set_mask(), set_labels() and next_file() are refused after it), on an engine created with WGBSSEG_VIEW_SORT and no other flag
+ * (WGBSSEG_E_ARG otherwise).  loci, n_sites and the chromosome table are those of wgbsseg_bedbeta_create (below), with its checks and
+ * messages.  feed() / feed_bgzf() then take what `samtools view [-h]` prints, cut anywhere between two lines (feed_bgzf: anywhere):
+ *   lines     empty lines are skipped; a line that begins with '@' is a header.  Only the first ten fields are read.
+ *   filter    a line stays when (FLAG & exclude_flags) == 0, (FLAG & include_flags) == include_flags and MAPQ >= mapq; strand 1 (top)
+ *             keeps FLAG 99 / 147 (paired) or 0, strand 2 (bottom) FLAG 83 / 163 (paired) or 16.  A line of fewer than 11 fields, or
+ *             whose FLAG or MAPQ is not made of decimal digits, is invalid: it is not filtered and keeps its place among the mates.  A
+ *             line that passes the filter and names a chromosome the table does not have is dropped.
+ *   one line  CIGAR: M = X copy bases, D N insert 'N', I S skip bases, H nothing; any other operation, '*', a missing number, an
+ *             operation past SEQ, a POS that is not decimal digits, a QNAME above 254 bytes: invalid.  At every CpG of RNAME at locus
+ *             POS + i inside the adjusted sequence: a top read (paired: not (FLAG & 0x53) == 83 and not (FLAG & 0xA3) == 163; single:
+ *             FLAG & 0x10 clear) gives C for "CG", T for "TG" at i; a bottom read gives C for "CG", T for "CA" at i, looked at at
+ *             j = i + 1; anything else '.'; clip: '.' when j < clip or j >= length - clip.  The pat runs from the first called site
+ *             to the last; none: the read is empty.
+ *   mates     paired != 0: two consecutive lines that stay, with equal QNAME and equal RNAME, are a pair — greedily: of k such lines
+ *             (1, 2), (3, 4), ... pair and an odd last one is single.  (The reference streams every chromosome by itself, so only lines
+ *             of one chromosome meet there; mates are adjacent, as Bismark and bwa-meth write them.)
+ *   merge     an empty or invalid side: the other as it is.  Else from the earlier start, a site both call differently becomes '.',
+ *             trailing then leading dots go; a span above 300 sites drops the pair; a result shorter than min_cpg is dropped.
+ * Every result is a record with count 1; finish() sorts, collapses, writes and deflates them as it does the reads of pat text (the
+ * ascending-start check does not apply).  The bytes that come out do not depend on how the text is cut into calls or BGZF members.
+ * sam_info(): out[10] = lines, header lines, filtered, invalid, unknown chromosome, empty, short, pairs, lines of a paired file left
+ * single, pairs merged too long (waits for the stream).  kernel_ms(): the device time of the SAM kernels.
+ */
+int wgbsseg_patview_set_sam(wgbsseg_patview* v, const uint32_t* loci, int64_t n_sites, const char* const* chrom_names, const int64_t* chrom_lo, const int64_t* chrom_hi,
+                            int32_t n_chroms, int32_t paired, int64_t exclude_flags, int64_t include_flags, int32_t mapq, int32_t strand, int32_t clip, int32_t min_cpg,
+                            char* err, size_t errlen);
+void wgbsseg_patview_sam_info(wgbsseg_patview* v, int64_t* out);
 
 /*
  * BED methylation calls -> .beta (`wgbstools bed2beta`: bed2beta.py:11-51, a pandas drop_duplicates and a left merge with the CpG

@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 360        # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 370        # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -54,6 +54,7 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_patview_next_file', 'wgbsseg_merge_rows', 'wgbsseg_last_merge_rows_ms',
            'wgbsseg_patview_set_mask', 'wgbsseg_patview_mask_info', 'wgbsseg_patview_mask_ms',
            'wgbsseg_patview_set_labels', 'wgbsseg_patview_label_rank', 'wgbsseg_patview_set_source', 'wgbsseg_patview_sample_info',
+           'wgbsseg_patview_set_sam', 'wgbsseg_patview_sam_info',
            'wgbsseg_bedbeta_create', 'wgbsseg_bedbeta_feed', 'wgbsseg_bedbeta_feed_bgzf', 'wgbsseg_bedbeta_finish', 'wgbsseg_bedbeta_next_file',
            'wgbsseg_bedbeta_destroy', 'wgbsseg_bedbeta_kernel_ms', 'wgbsseg_bedbeta_inflate_ms']
 
@@ -347,6 +348,10 @@ def load():
     L.wgbsseg_patview_set_source.argtypes = [vp, i32, C.c_uint32, i32, C.c_uint64, C.c_uint32, C.c_char_p, C.c_size_t]
     L.wgbsseg_patview_sample_info.restype = None
     L.wgbsseg_patview_sample_info.argtypes = [vp, vp]
+    L.wgbsseg_patview_set_sam.restype = i32
+    L.wgbsseg_patview_set_sam.argtypes = [vp, vp, i64, C.POINTER(C.c_char_p), vp, vp, i32, i32, i64, i64, i32, i32, i32, i32, C.c_char_p, C.c_size_t]
+    L.wgbsseg_patview_sam_info.restype = None
+    L.wgbsseg_patview_sam_info.argtypes = [vp, vp]
     L.wgbsseg_merge_rows.restype = i32
     L.wgbsseg_merge_rows.argtypes = [vp, vp, i32, i32, vp, C.c_char_p, C.c_size_t]
     L.wgbsseg_last_merge_rows_ms.restype = C.c_double
@@ -1001,6 +1006,35 @@ class PatView(_PatFeed):
         out = np.zeros(3, dtype=np.int64)
         self._L.wgbsseg_patview_sample_info(self._h, out.ctypes.data)
         return dict(zip(('sampled_reads', 'sampled_dropped', 'sampled_kept'), out.tolist()))
+
+    SAM_COUNTERS = ('lines', 'header', 'filtered', 'invalid', 'unknown_chrom', 'empty', 'short', 'pairs', 'left_single', 'too_long')
+
+    def set_sam(self, loci, chrom_names, chrom_sizes=None, paired=False, exclude_flags=1796, include_flags=0, mapq=10, strand=0, clip=0, min_cpg=1,
+                chrom_ranges=None):
+        """the engine takes SAM text instead of pat text (`wgbstools bam2pat`): once, before the first feed, on an engine made with
+        sort=True and nothing else.  loci / chrom_names / chrom_sizes (or chrom_ranges): the dictionary, as BedBeta takes it; strand: 0
+        both, 1 top, 2 bottom."""
+        loci = np.ascontiguousarray(loci, dtype=np.uint32)
+        if chrom_ranges is None:
+            hi = np.cumsum(np.asarray(chrom_sizes, dtype=np.int64))
+            lo = hi - np.asarray(chrom_sizes, dtype=np.int64)
+        else:
+            lo, hi = chrom_ranges
+        lo = np.ascontiguousarray(lo, dtype=np.int64)
+        hi = np.ascontiguousarray(hi, dtype=np.int64)
+        raw = [c if isinstance(c, bytes) else str(c).encode() for c in chrom_names]
+        if lo.shape != hi.shape or lo.ndim != 1 or lo.size != len(raw):
+            raise ValueError('one name and one range per chromosome')
+        names = (C.c_char_p * max(len(raw), 1))(*raw)
+        self._call('set_sam', self._h, loci.ctypes.data if loci.size else None, int(loci.size), names, lo.ctypes.data if lo.size else None,
+                   hi.ctypes.data if hi.size else None, len(raw), 1 if paired else 0, int(exclude_flags), int(include_flags), int(mapq), int(strand),
+                   int(clip), int(min_cpg))
+
+    def sam_info(self):
+        """the counters of a SAM engine (waits for the stream)"""
+        out = np.zeros(len(self.SAM_COUNTERS), dtype=np.int64)
+        self._L.wgbsseg_patview_sam_info(self._h, out.ctypes.data)
+        return dict(zip(self.SAM_COUNTERS, out.tolist()))
 
     def finish(self, deflate=False):
         lines, nbytes = C.c_int64(0), C.c_int64(0)

@@ -917,6 +917,18 @@ struct wgbsseg_patview {
     bool finished = false;
     const void* out = nullptr;                                    // the result on the device (text or dense) and its bytes
     int64_t out_bytes = 0;
+    SamPlan sam_plan;                                             // set_sam(): the engine takes SAM text (sam_plan.h) ...
+    bool sam = false;
+    DevBuf sam_loci, sam_chroms;                                  // ... the loci and the chromosome table on the device
+    DevBuf sam_tiles, sam_lines, sam_reads, sam_part, sam_head, sam_rid, sam_runs, sam_res, sam_wg;      // a chunk's tables (sam_kernels.h)
+    DevBuf sam_carry, sam_state;                                  // two wg_sam_carry slots, swapped like PrevRead's | the counters, shift0
+    PinnedBuf sam_home;                                           // the two totals a chunk sends home
+    unsigned long long sam_chunks = 0;
+    int64_t sam_lines_seen = 0;
+    wg_sam_carry* sam_carry_in() const { return sam_carry.as<wg_sam_carry>() + ((sam_chunks & 1) ^ 1); }
+    wg_sam_carry* sam_carry_out() const { return sam_carry.as<wg_sam_carry>() + (sam_chunks & 1); }
+    unsigned long long* sam_counters() const { return sam_state.as<unsigned long long>(); }
+    uint32_t* sam_shift0() const { return reinterpret_cast<uint32_t*>(sam_counters() + WG_SAM_COUNTERS); }
     Event ph[3][2];
     bool timed[3] = {false, false, false};
     double phase_ms[3] = {0.0, 0.0, 0.0};
@@ -972,6 +984,83 @@ static int view_source_missing(const wgbsseg_patview* v, char* err, size_t errle
     return WGBSSEG_E_STATE;
 }
 
+// A staged chunk of SAM text (set_sam(); sam_kernels.h has the launch sequence): count the lines -> L comes home -> the per-line kernels
+// up to the measure -> the records and arena bytes the chunk adds come home -> reserve -> pack.  Two waits per chunk: a pat cannot be
+// bounded by the bytes of its line (D and N operations give sites without text), so the room is made from what was measured.
+template <class Stage>
+static int sam_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    PatFeed& f = v->feed;
+    const hipStream_t st = f.st;
+    std::string msg;
+    SamChunk c;
+    int rc = plan_sam_lines(n_bytes, 0, c, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    HIP_TRY(v->sam_tiles.ensure((size_t)(2 * gx + 2) * 8));
+    const char* dtext = nullptr;
+    rc = stage(&dtext);
+    if (rc != WGBSSEG_OK) return rc;
+    uint64_t *tile_lines = v->sam_tiles.as<uint64_t>(), *tile_base = tile_lines + gx, *ltot = tile_base + gx;
+    uint64_t* home = static_cast<uint64_t*>(v->sam_home.p);
+    HIP_TRY(hipMemcpyAsync(v->sam_carry_out(), v->sam_carry_in(), sizeof(wg_sam_carry), hipMemcpyDeviceToDevice, st));      // kept when the chunk holds no mate-able line
+    HIP_TRY(f.span_begin());
+    hipLaunchKernelGGL(k_sam_count, dim3((unsigned)gx), dim3(WG_BLOCK), 0, st, dtext, n_bytes, tile_lines);
+    hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, tile_lines, tile_lines, gx, tile_base, ltot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(f.span_end());
+    HIP_TRY(hipMemcpyAsync(home, ltot, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    f.collect();
+    rc = plan_sam_lines(n_bytes, (int64_t)home[0], c, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    if (c.lines) {
+        const size_t L = (size_t)c.lines;
+        const int64_t G = c.groups;
+        HIP_TRY(v->sam_lines.ensure(L * 4)); HIP_TRY(v->sam_reads.ensure(L * sizeof(wg_sam_read))); HIP_TRY(v->sam_part.ensure(L * 4));
+        HIP_TRY(v->sam_head.ensure(L)); HIP_TRY(v->sam_rid.ensure(L * 4)); HIP_TRY(v->sam_runs.ensure(L * 4)); HIP_TRY(v->sam_res.ensure(L * sizeof(wg_sam_res)));
+        HIP_TRY(v->sam_wg.ensure((size_t)c.wg_words() * 8));
+        uint64_t *wg_part = v->sam_wg.as<uint64_t>(), *part_base = wg_part + G, *wg_heads = part_base + G, *head_base = wg_heads + G;
+        uint64_t *wg_recs = head_base + G, *wg_bytes = wg_recs + G, *rec_base = wg_bytes + G, *byte_base = rec_base + G, *tot = byte_base + G;
+        const wg_sam_args a = {dtext, n_bytes, v->sam_plan.chroms.view_at(v->sam_chroms.as<const char>()), v->sam_loci.as<const uint32_t>(), v->sam_plan.par};
+        const dim3 grid((unsigned)G), block(WG_BLOCK), one(1);
+        uint32_t *lstart = v->sam_lines.as<uint32_t>(), *part = v->sam_part.as<uint32_t>(), *rid = v->sam_rid.as<uint32_t>(), *runs = v->sam_runs.as<uint32_t>();
+        wg_sam_read* reads = v->sam_reads.as<wg_sam_read>();
+        wg_sam_res* res = v->sam_res.as<wg_sam_res>();
+        HIP_TRY(f.span_begin());
+        hipLaunchKernelGGL(k_sam_starts, dim3((unsigned)gx), block, 0, st, dtext, n_bytes, tile_base, lstart);
+        hipLaunchKernelGGL(k_sam_eval, grid, block, 0, st, a, lstart, c.lines, reads, wg_part, v->sam_counters());
+        hipLaunchKernelGGL(k_bed_scan, one, dim3(WG_BED_BLOCK), 0, st, wg_part, wg_part, G, part_base, tot);
+        hipLaunchKernelGGL(k_sam_compact, grid, block, 0, st, reads, c.lines, part_base, part);
+        hipLaunchKernelGGL(k_sam_heads, grid, block, 0, st, a, reads, part, tot, v->sam_carry_in(), v->sam_head.as<uint8_t>(), wg_heads, v->sam_shift0());
+        hipLaunchKernelGGL(k_bed_scan, one, dim3(WG_BED_BLOCK), 0, st, wg_heads, wg_heads, G, head_base, tot + 2);
+        hipLaunchKernelGGL(k_sam_runs, grid, block, 0, st, v->sam_head.as<const uint8_t>(), head_base, tot, rid, runs);
+        hipLaunchKernelGGL(k_sam_measure, grid, block, 0, st, a, reads, part, tot, rid, runs, v->sam_shift0(), v->sam_carry_in(), v->recs.as<const wg_view_rec>(),
+                           v->arena.as<const char>(), res, wg_recs, wg_bytes, v->sam_counters());
+        hipLaunchKernelGGL(k_bed_scan, one, dim3(WG_BED_BLOCK), 0, st, wg_recs, wg_bytes, G, rec_base, tot + 4);      // tot[4], tot[5]: the records, the arena bytes
+        hipLaunchKernelGGL(k_bed_scan, one, dim3(WG_BED_BLOCK), 0, st, wg_bytes, wg_bytes, G, byte_base, tot + 6);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(f.span_end());
+        HIP_TRY(hipMemcpyAsync(home, tot + 4, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        f.collect();
+        const int64_t added = (int64_t)home[0], bytes = (int64_t)home[1];
+        rc = plan_sam_records(v->n_recs, added, msg);
+        if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+        rc = view_reserve(v, v->n_recs + added, v->n_arena + bytes, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        HIP_TRY(f.span_begin());
+        hipLaunchKernelGGL(k_sam_pack, grid, block, 0, st, a, reads, part, tot, rid, runs, v->sam_shift0(), v->sam_carry_in(), v->sam_carry_out(), res, rec_base, byte_base,
+                           (uint64_t)v->n_recs, (uint64_t)v->n_arena, v->recs.as<wg_view_rec>(), v->arena.as<char>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(f.span_end());
+        v->n_recs += added; v->n_arena += bytes;
+        v->sam_lines_seen += c.lines;
+    }
+    v->sam_chunks += 1;                                            // (the carry's slots swap for the next chunk)
+    HIP_TRY(f.chunk_queued(n_bytes));
+    return WGBSSEG_OK;
+}
+
 // a staged chunk of n_bytes / gx tiles: totals of the chunk before -> reserve -> measure, scan, scan, pack -> its totals on their way
 template <class Stage>
 static int pat_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
@@ -979,6 +1068,7 @@ static int pat_chunk(wgbsseg_patview* v, int64_t n_bytes, int64_t gx, Stage&& st
     PatFeed& f = v->feed;
     HIP_TRY(hipSetDevice(f.device));
     if (v->finished) { set_err(err, errlen, "patview_feed: finish() has been called"); return WGBSSEG_E_STATE; }
+    if (v->sam) return sam_chunk(v, n_bytes, gx, stage, err, errlen);
     int rc = view_source_missing(v, err, errlen);
     if (rc != WGBSSEG_OK) return rc;
     rc = view_take_totals(v, err, errlen);
@@ -1188,6 +1278,7 @@ int wgbsseg_patview_set_mask(wgbsseg_patview* v, const int64_t* start_cpg, const
     if (!v) { set_err(err, errlen, "bad arguments to patview_set_mask"); return WGBSSEG_E_ARG; }
     if (v->masked) { set_err(err, errlen, "patview_set_mask: called twice"); return WGBSSEG_E_STATE; }
     if (v->fed_any || v->finished) { set_err(err, errlen, "patview_set_mask: called after the first feed"); return WGBSSEG_E_STATE; }
+    if (v->sam) { set_err(err, errlen, "patview_set_mask: the engine takes SAM text: a mask does not go with it"); return WGBSSEG_E_STATE; }
     if (v->labelled) { set_err(err, errlen, "patview_set_mask: the engine has labels: a mask and sources do not go together"); return WGBSSEG_E_STATE; }
     MaskPlan plan;
     std::string msg;
@@ -1229,6 +1320,7 @@ int wgbsseg_patview_set_labels(wgbsseg_patview* v, const char* const* labels, in
     if (!v) { set_err(err, errlen, "bad arguments to patview_set_labels"); return WGBSSEG_E_ARG; }
     if (v->labelled) { set_err(err, errlen, "patview_set_labels: called twice"); return WGBSSEG_E_STATE; }
     if (v->fed_any || v->finished) { set_err(err, errlen, "patview_set_labels: called after the first feed"); return WGBSSEG_E_STATE; }
+    if (v->sam) { set_err(err, errlen, "patview_set_labels: the engine takes SAM text: labels do not go with it"); return WGBSSEG_E_STATE; }
     if (v->masked) { set_err(err, errlen, "patview_set_labels: the engine has a mask: a mask and sources do not go together"); return WGBSSEG_E_STATE; }
     ViewLabels plan;
     std::string msg;
@@ -1266,6 +1358,48 @@ int wgbsseg_patview_set_source(wgbsseg_patview* v, int32_t label_rank, uint32_t 
     v->source = wg_view_source{seed, 0u, T, stream, (uint32_t)reps, (uint32_t)label_rank, nullptr, nullptr};
     v->source_file = v->files.open_file();
     return WGBSSEG_OK;
+}
+
+// SAM text in place of pat text (`wgbstools bam2pat`): plan (sam_plan.h: the checks, bed2beta_plan.h's chromosome table) -> the loci and
+// the table to the device, the carry and the counters cleared.  Once, before anything has been fed.
+int wgbsseg_patview_set_sam(wgbsseg_patview* v, const uint32_t* loci, int64_t n_sites, const char* const* chrom_names, const int64_t* chrom_lo, const int64_t* chrom_hi,
+                            int32_t n_chroms, int32_t paired, int64_t exclude_flags, int64_t include_flags, int32_t mapq, int32_t strand, int32_t clip, int32_t min_cpg,
+                            char* err, size_t errlen)
+{
+    if (!v) { set_err(err, errlen, "bad arguments to patview_set_sam"); return WGBSSEG_E_ARG; }
+    std::string msg;
+    int rc = plan_sam_state(v->sam, v->fed_any, v->finished, v->masked, v->labelled, v->plan.flags, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    SamPlan plan;
+    rc = plan_sam(loci, n_sites, chrom_names, chrom_lo, chrom_hi, n_chroms, paired, exclude_flags, include_flags, mapq, strand, clip, min_cpg, plan, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    const hipStream_t st = v->feed.st;
+    HIP_TRY(hipSetDevice(v->feed.device));
+    std::vector<char> tab(plan.chroms.upload_bytes());
+    plan.chroms.upload_to(tab.data());
+    const size_t state_bytes = (WG_SAM_COUNTERS + 1) * 8;
+    HIP_TRY(v->sam_loci.ensure((size_t)n_sites * 4)); HIP_TRY(v->sam_chroms.ensure(tab.size()));
+    HIP_TRY(v->sam_carry.ensure(2 * sizeof(wg_sam_carry))); HIP_TRY(v->sam_state.ensure(state_bytes));
+    if (!v->sam_home.ensure(16)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    HIP_TRY(hipMemcpy(v->sam_loci.p, loci, (size_t)n_sites * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(v->sam_chroms.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(v->sam_carry.p, 0, 2 * sizeof(wg_sam_carry), st));
+    HIP_TRY(hipMemsetAsync(v->sam_state.p, 0, state_bytes, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    v->sam_plan = std::move(plan);
+    v->sam = true;
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_patview_sam_info(wgbsseg_patview* v, int64_t* out)
+{
+    if (!v || !out) return;
+    for (int k = 0; k < WG_SAM_COUNTERS; k++) out[k] = 0;
+    if (!v->sam || hipSetDevice(v->feed.device) != hipSuccess || hipStreamSynchronize(v->feed.st) != hipSuccess) return;
+    unsigned long long got[WG_SAM_COUNTERS];
+    if (hipMemcpy(got, v->sam_counters(), sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) return;
+    for (int k = 0; k < WG_SAM_COUNTERS; k++) out[k] = (int64_t)got[k];
+    out[WG_SAM_N_LINES] = v->sam_lines_seen;
 }
 
 void wgbsseg_patview_sample_info(wgbsseg_patview* v, int64_t* out)
@@ -1306,6 +1440,7 @@ int wgbsseg_patview_feed_bgzf(wgbsseg_patview* v, const void* bytes, int64_t n_b
 int wgbsseg_patview_next_file(wgbsseg_patview* v, char* err, size_t errlen)
 {
     if (!v) { set_err(err, errlen, "bad arguments to patview_next_file"); return WGBSSEG_E_ARG; }
+    if (v->sam) { set_err(err, errlen, "patview_next_file: an engine that takes SAM text takes one file"); return WGBSSEG_E_STATE; }
     std::string msg;
     int rc = plan_view_next_file(v->finished, v->bgzf_left, v->files.open_file(), msg);
     if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }

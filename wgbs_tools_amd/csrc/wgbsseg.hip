@@ -41,6 +41,7 @@
 #include "homog_kernels.h"
 #include "frag_kernels.h"
 #include "view_kernels.h"
+#include "sam_kernels.h"
 #include "bimodal_kernels.h"
 #include "inflate_plan.h"
 #include "inflate_kernels.h"
