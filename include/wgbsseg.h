@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define WGBSSEG_VERSION 370            /* 0.3.7: wgbsseg_patview_set_sam, wgbsseg_patview_sam_info (`wgbstools bam2pat`: SAM reads called, paired and merged on the device).  0.3.6: wgbsseg_bedbeta_* (`wgbstools bed2beta`: BED methylation calls joined to the CpG dictionary on the device).  0.3.5.1: wgbsseg_debug_last_plan (test hook: the staging form of the last call); wgbsseg_debug_fetch("cost") serves staged calls with n_stages <= nbuf.  0.3.5:wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
+#define WGBSSEG_VERSION 380            /* 0.3.8: wgbsseg_fasta_*, wgbsseg_debug_fasta_walk (`wgbstools init_genome`: the CpG dictionary from FASTA text on the device).  0.3.7: wgbsseg_patview_set_sam, wgbsseg_patview_sam_info (`wgbstools bam2pat`: SAM reads called, paired and merged on the device).  0.3.6: wgbsseg_bedbeta_* (`wgbstools bed2beta`: BED methylation calls joined to the CpG dictionary on the device).  0.3.5.1: wgbsseg_debug_last_plan (test hook: the staging form of the last call); wgbsseg_debug_fetch("cost") serves staged calls with n_stages <= nbuf.  0.3.5:wgbsseg_patview_set_labels, wgbsseg_patview_label_rank, wgbsseg_patview_set_source, wgbsseg_patview_sample_info (`wgbstools mix_pat`: pat reads thinned and labelled on the device).  0.3.4: wgbsseg_patview_set_mask, wgbsseg_patview_mask_info, wgbsseg_patview_mask_ms (`wgbstools mask_pat`: sites hidden from pat reads on the device).  0.3.3: wgbsseg_patview_next_file, wgbsseg_merge_rows, wgbsseg_last_merge_rows_ms (`wgbstools merge`: pat and beta files of replicates pooled on the device).  0.3.2: wgbsseg_patview_* (`wgbstools view` / `cview`: pat reads filtered, sorted and collapsed on the device).  0.3.1: wgbsseg_bgzf_deflate, wgbsseg_bgzf_deflate_bound, wgbsseg_beta2bed_bgzf, wgbsseg_bgzf_deflate_ms, wgbsseg_bgzf_deflate_pass_ms (BGZF members deflated on the device).  0.3.0: wgbsseg_fraglen_* (`wgbstools frag_len`: the read-length histogram of a pat file).  0.2.9: wgbsseg_{patbeta,homog,bimodal}_feed_bgzf and _inflate_ms, wgbsseg_bgzf_inflate (BGZF members inflated on the device).  0.2.8: wgbsseg_site_counts, wgbsseg_site_table, wgbsseg_site_table_pass_ms, wgbsseg_site_table_limits (`wgbstools beta_to_450k`).  0.2.7: wgbsseg_beta2bed, wgbsseg_beta2bed_pass_ms, wgbsseg_beta2bed_limits, WGBSSEG_E_IO (`wgbstools beta2bed`).  0.2.6: wgbsseg_pair_ranges, wgbsseg_pair_hist, wgbsseg_pair_hist_limits (`wgbstools compare_betas`).  0.2.5: wgbsseg_sample_stats (`wgbstools beta_cov` / `beta_stats`).  0.2.4.1: wgbsseg_debug_bimodal_terms.  0.2.4: wgbsseg_bimodal_* (`wgbstools test_bimodal`).  0.2.3: wgbsseg_homog_* and wgbsseg_debug_homog_bins (`wgbstools homog`).  0.2.1: round 4 changed wgbsseg_scan_only's argument list and added wgbsseg_add_loci_borders without a bump; a binding compares wgbsseg_version() with the header it was written against */
 #define WGBSSEG_MAX_CPG 65535          /* longest block, in sites (min(max_cpg, longest chunk)): see wgbsseg_segment_chunks */
 
 #define WGBSSEG_OK              0
@@ -858,6 +858,51 @@ int wgbsseg_bedbeta_next_file(wgbsseg_bedbeta* b, int32_t flags, char* err, size
 void wgbsseg_bedbeta_destroy(wgbsseg_bedbeta* b);
 double wgbsseg_bedbeta_kernel_ms(wgbsseg_bedbeta* b);
 double wgbsseg_bedbeta_inflate_ms(wgbsseg_bedbeta* b);
+
+/*
+ * FASTA text -> the CpG dictionary (`wgbstools init_genome`: init_genome.py:142-179, 246-260, where `samtools faidx`, a regular
+ * expression per chromosome, `bgzip` and `tabix` do it).  The rule (csrc/fasta_core.h, the same functions on the host and on the device):
+ *   header   a line that begins with '>' — as the first byte of the input or right after '\n' — up to the next '\n'; the sequence's name
+ *            is what follows the '>' up to the first space, tab, '\r' or '\n'
+ *   bases    every other byte that is not '\n' or '\r' is a base of the current sequence; bases count from 1
+ *   sites    a base C / c whose next base in the same sequence is G / g, whatever line breaks lie between them; its locus is the C's number
+ * That is the reference's ''.join(s.strip() ...).upper() + finditer('CG') for every FASTA whose lines carry no blanks; a '\r' is skipped
+ * wherever it stands.  feed() / feed_bgzf(): the text or the bytes of a BGZF file, not both; asynchronous, the bytes are copied; A CALL
+ * MAY END AT ANY BYTE (an unwrapped chromosome is one line of 250 MB): what a call leaves open — the state, the sequence and its bases so
+ * far, a C whose next base has not come yet — is carried on the device.  The results do not depend on how the input is cut into calls,
+ * tiles or BGZF members.  finish_scan(): once, after the last feed; counts[3] = sequences, sites, bytes of text.  WGBSSEG_E_ARG for a BGZF
+ * member refused on the device, else "Invalid FASTA: <what> at byte offset N of the text" for the lowest N among: a byte other than '\n' /
+ * '\r' before the first header (the byte); a header with an empty name (its '>'); a name of more than 255 bytes (its '>'); a byte of a
+ * sequence outside 0x21 .. 0x7E that is not '\n' or '\r' (the byte); a sequence of more than 2^32 - 2 bases (its '>'); else for two
+ * sequences with one name.  sequences(): per sequence, in FASTA order, the offset of its header, its bases, its sites, the length of its
+ * name and the name (256 bytes each, zero-padded); any pointer may be NULL.  select(): order[n_order], the sequences the dictionary keeps,
+ * in the dictionary's order, each at most once (which sequences are chromosomes and how they are sorted is the caller's rule:
+ * init_genome.py's is_valid_chrome and chromosome_order); none: WGBSSEG_E_ARG, "no chromosome is kept".  Their loci are gathered into one
+ * array, *n_sites long; loci(): that array (what `loci.u32` holds; n must be *n_sites).  dict(): `name \t locus \t site \n` per selected
+ * site, site counting from 1 over the dictionary, formatted on the device; deflate != 0: as BGZF members, the end-of-file member last
+ * (what wgbsseg_bgzf_deflate writes).  *n_lines, *n_bytes: of the result, which stays on the device; read(): its bytes [offset, offset +
+ * len).  kernel_ms: device time (HIP events) of the measure, scan and pack launches so far; inflate_ms: of the inflate launches; both wait
+ * for them.  phase_ms: the gather of select(), the emit and the deflate of dict().
+ * wgbsseg_debug_fasta_walk (test hook, no device): the same rule run serially over text[0, n) on the host, into tables with room for
+ * cap_seqs sequences and cap_loci loci (WGBSSEG_E_CAPACITY when they do not suffice); counts[2] = sequences, sites; *refused: (offset << 8
+ * | reason) of the first refusal (reasons 1 .. 5 in the order above), ~0: none.
+ */
+typedef struct wgbsseg_fasta wgbsseg_fasta;
+int wgbsseg_fasta_create(int device, wgbsseg_fasta** out, char* err, size_t errlen);
+int wgbsseg_fasta_feed(wgbsseg_fasta* f, const char* text, int64_t n_bytes, char* err, size_t errlen);
+int wgbsseg_fasta_feed_bgzf(wgbsseg_fasta* f, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen);
+int wgbsseg_fasta_finish_scan(wgbsseg_fasta* f, int64_t* counts, char* err, size_t errlen);
+int wgbsseg_fasta_sequences(wgbsseg_fasta* f, int64_t* hdr_off, int64_t* n_bases, int64_t* n_sites, int32_t* name_len, char* names, char* err, size_t errlen);
+int wgbsseg_fasta_select(wgbsseg_fasta* f, const int64_t* order, int64_t n_order, int64_t* n_sites, char* err, size_t errlen);
+int wgbsseg_fasta_loci(wgbsseg_fasta* f, uint32_t* out, int64_t n, char* err, size_t errlen);
+int wgbsseg_fasta_dict(wgbsseg_fasta* f, int32_t deflate, int64_t* n_lines, int64_t* n_bytes, char* err, size_t errlen);
+int wgbsseg_fasta_read(wgbsseg_fasta* f, int64_t offset, void* buf, int64_t len, char* err, size_t errlen);
+void wgbsseg_fasta_destroy(wgbsseg_fasta* f);
+double wgbsseg_fasta_kernel_ms(wgbsseg_fasta* f);
+double wgbsseg_fasta_inflate_ms(wgbsseg_fasta* f);
+void wgbsseg_fasta_phase_ms(const wgbsseg_fasta* f, double* gather_ms, double* emit_ms, double* deflate_ms);
+int wgbsseg_debug_fasta_walk(const char* text, int64_t n, int64_t cap_seqs, int64_t cap_loci, int64_t* hdr_off, int64_t* n_bases, int64_t* n_sites, int32_t* name_len,
+                             char* names, uint32_t* loci, int64_t* counts, uint64_t* refused);
 
 int wgbsseg_get_timings(const wgbsseg_ctx* ctx, wgbsseg_timings* out);
 

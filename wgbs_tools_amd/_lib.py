@@ -23,7 +23,7 @@ SYNTH_LIB_PATH = op.join(HERE, 'csrc', 'libwgbssynth.so')
 OK, E_ARG, E_METH_GT_COV, E_NOMEM, E_HIP, E_LOCI_ORDER, E_CAPACITY, E_STATE, E_IO = 0, -1, -2, -3, -4, -5, -6, -7, -8
 
 # every symbol include/wgbsseg.h declares (tests check the built library exports exactly these)
-ABI_VERSION = 370        # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
+ABI_VERSION = 380        # include/wgbsseg.h WGBSSEG_VERSION this binding's prototypes describe
 EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg_destroy',
            'wgbsseg_set_betas_host', 'wgbsseg_set_betas_device', 'wgbsseg_set_loci_host', 'wgbsseg_set_loci_device',
            'wgbsseg_segment_chunks', 'wgbsseg_segment_regions', 'wgbsseg_segment_chunks_host', 'wgbsseg_prefix_sums', 'wgbsseg_scan_only',
@@ -56,7 +56,10 @@ EXPORTS = ['wgbsseg_version', 'wgbsseg_device_count', 'wgbsseg_create', 'wgbsseg
            'wgbsseg_patview_set_labels', 'wgbsseg_patview_label_rank', 'wgbsseg_patview_set_source', 'wgbsseg_patview_sample_info',
            'wgbsseg_patview_set_sam', 'wgbsseg_patview_sam_info',
            'wgbsseg_bedbeta_create', 'wgbsseg_bedbeta_feed', 'wgbsseg_bedbeta_feed_bgzf', 'wgbsseg_bedbeta_finish', 'wgbsseg_bedbeta_next_file',
-           'wgbsseg_bedbeta_destroy', 'wgbsseg_bedbeta_kernel_ms', 'wgbsseg_bedbeta_inflate_ms']
+           'wgbsseg_bedbeta_destroy', 'wgbsseg_bedbeta_kernel_ms', 'wgbsseg_bedbeta_inflate_ms',
+           'wgbsseg_fasta_create', 'wgbsseg_fasta_feed', 'wgbsseg_fasta_feed_bgzf', 'wgbsseg_fasta_finish_scan', 'wgbsseg_fasta_sequences', 'wgbsseg_fasta_select',
+           'wgbsseg_fasta_loci', 'wgbsseg_fasta_dict', 'wgbsseg_fasta_read', 'wgbsseg_fasta_destroy', 'wgbsseg_fasta_kernel_ms', 'wgbsseg_fasta_inflate_ms',
+           'wgbsseg_fasta_phase_ms', 'wgbsseg_debug_fasta_walk']
 
 
 class NativeLibraryError(RuntimeError):
@@ -368,7 +371,31 @@ def load():
     L.wgbsseg_bedbeta_destroy.argtypes = [vp]
     L.wgbsseg_bedbeta_kernel_ms.restype = C.c_double
     L.wgbsseg_bedbeta_kernel_ms.argtypes = [vp]
-    for eng in ('patbeta', 'homog', 'bimodal', 'fraglen', 'patview', 'bedbeta'):
+    L.wgbsseg_fasta_create.restype = i32
+    L.wgbsseg_fasta_create.argtypes = [i32, C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_feed.restype = i32
+    L.wgbsseg_fasta_feed.argtypes = [vp, C.c_char_p, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_finish_scan.restype = i32
+    L.wgbsseg_fasta_finish_scan.argtypes = [vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_sequences.restype = i32
+    L.wgbsseg_fasta_sequences.argtypes = [vp, vp, vp, vp, vp, vp, C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_select.restype = i32
+    L.wgbsseg_fasta_select.argtypes = [vp, vp, i64, C.POINTER(i64), C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_loci.restype = i32
+    L.wgbsseg_fasta_loci.argtypes = [vp, vp, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_dict.restype = i32
+    L.wgbsseg_fasta_dict.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64), C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_read.restype = i32
+    L.wgbsseg_fasta_read.argtypes = [vp, i64, vp, i64, C.c_char_p, C.c_size_t]
+    L.wgbsseg_fasta_destroy.restype = None
+    L.wgbsseg_fasta_destroy.argtypes = [vp]
+    L.wgbsseg_fasta_kernel_ms.restype = C.c_double
+    L.wgbsseg_fasta_kernel_ms.argtypes = [vp]
+    L.wgbsseg_fasta_phase_ms.restype = None
+    L.wgbsseg_fasta_phase_ms.argtypes = [vp, vp, vp, vp]
+    L.wgbsseg_debug_fasta_walk.restype = i32
+    L.wgbsseg_debug_fasta_walk.argtypes = [C.c_char_p, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_uint64)]
+    for eng in ('patbeta', 'homog', 'bimodal', 'fraglen', 'patview', 'bedbeta', 'fasta'):
         f = getattr(L, 'wgbsseg_%s_feed_bgzf' % eng)
         f.restype = i32
         f.argtypes = [vp, C.c_char_p, i64, C.POINTER(i64), C.c_char_p, C.c_size_t]
@@ -1071,6 +1098,101 @@ class PatView(_PatFeed):
         out = np.zeros(6, dtype=np.int64)
         self._L.wgbsseg_patview_info(self._h, out.ctypes.data)
         return dict(zip(('records', 'arena_bytes', 'grown_records', 'grown_arena', 'merge_passes', 'order'), out.tolist()))
+
+
+FA_MAX_NAME = 255                                                 # csrc/fasta_core.h WG_FA_MAX_NAME
+FA_REASONS = (None, 'before_header', 'empty_name', 'long_name', 'bad_byte', 'long_sequence')      # ... WG_FA_BAD_*
+
+
+def _fasta_table(n, hdr, bases, sites, nlen, names):
+    raw = names.tobytes()
+    return [dict(name=raw[i * (FA_MAX_NAME + 1):i * (FA_MAX_NAME + 1) + max(0, min(int(nlen[i]), FA_MAX_NAME))], offset=int(hdr[i]), bases=int(bases[i]), sites=int(sites[i]))
+            for i in range(n)]
+
+
+class Fasta(_PatFeed):
+    """wgbsseg_fasta: FASTA text -> the sequence table and the CpG dictionary on one GPU (`wgbstools init_genome`).  feed() takes text
+    cut at ANY byte (feed_bgzf(): the bytes of a BGZF file).  finish_scan() -> the sequences in FASTA order, dicts of name (bytes),
+    offset, bases, sites; select(order) -> the sites of the kept sequences, whose loci loci() returns; dict() -> (lines, bytes) of
+    `name \\t locus \\t site` for them, which stays on the device (as BGZF with deflate=True); read() / chunks() fetch it."""
+    _abi = 'fasta'
+
+    def __init__(self, device=0):
+        super().__init__()
+        self.n_seqs = self.n_sites = self.n_text = self.n_sel = self.n_lines = self.n_bytes = None
+        self._call('create', int(device), C.byref(self._h))
+
+    def feed(self, text):
+        """text: bytes, cut anywhere"""
+        self._call('feed', self._h, text, len(text))
+
+    def finish_scan(self):
+        counts = np.zeros(3, dtype=np.int64)
+        self._call('finish_scan', self._h, counts.ctypes.data)
+        self.n_seqs, self.n_sites, self.n_text = counts.tolist()
+        n = max(self.n_seqs, 1)
+        hdr, bases, sites = (np.zeros(n, dtype=np.int64) for _ in range(3))
+        nlen = np.zeros(n, dtype=np.int32)
+        names = np.zeros(n * (FA_MAX_NAME + 1), dtype=np.uint8)
+        self._call('sequences', self._h, hdr.ctypes.data, bases.ctypes.data, sites.ctypes.data, nlen.ctypes.data, names.ctypes.data)
+        return _fasta_table(self.n_seqs, hdr, bases, sites, nlen, names)
+
+    def select(self, order):
+        """order: indices into finish_scan()'s table, the kept sequences in the dictionary's order -> the dictionary's sites"""
+        o = np.ascontiguousarray(order, dtype=np.int64)
+        n = C.c_int64(0)
+        self._call('select', self._h, o.ctypes.data if o.size else None, o.size, C.byref(n))
+        self.n_sel = int(n.value)
+        return self.n_sel
+
+    def loci(self):
+        out = np.empty(self.n_sel, dtype=np.uint32)
+        self._call('loci', self._h, out.ctypes.data if out.size else None, out.size)
+        return out
+
+    def dict(self, deflate=False):
+        lines, nbytes = C.c_int64(0), C.c_int64(0)
+        self._call('dict', self._h, 1 if deflate else 0, C.byref(lines), C.byref(nbytes))
+        self.n_lines, self.n_bytes = int(lines.value), int(nbytes.value)
+        return self.n_lines, self.n_bytes
+
+    def read(self, offset=0, length=None):
+        """bytes [offset, offset + length) of dict()'s result (default: to its end)"""
+        length = self.n_bytes - offset if length is None else int(length)
+        out = np.empty(max(length, 1), dtype=np.uint8)
+        self._call('read', self._h, int(offset), out.ctypes.data, length)
+        return out[:length].tobytes()
+
+    def chunks(self, piece=64 << 20):
+        for at in range(0, self.n_bytes, piece):
+            yield self.read(at, min(piece, self.n_bytes - at))
+
+    def phase_ms(self):
+        """(gather of select(), emit and deflate of dict()), HIP-event milliseconds"""
+        a, b, c = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._L.wgbsseg_fasta_phase_ms(self._h, C.addressof(a), C.addressof(b), C.addressof(c))
+        return a.value, b.value, c.value
+
+
+def debug_fasta_walk(text):
+    """wgbsseg_debug_fasta_walk: the engine's rule run serially on the host (no device) -> (the table as Fasta.finish_scan() returns it,
+    uint32 loci in FASTA order, refusal: None or (byte offset, one of FA_REASONS))"""
+    L = load()
+    text = bytes(text)
+    cap_s, cap_l = text.count(b'>') + 1, len(text) // 2 + 1
+    hdr, bases, sites = (np.zeros(cap_s, dtype=np.int64) for _ in range(3))
+    nlen = np.zeros(cap_s, dtype=np.int32)
+    names = np.zeros(cap_s * (FA_MAX_NAME + 1), dtype=np.uint8)
+    loci = np.zeros(cap_l, dtype=np.uint32)
+    counts = np.zeros(2, dtype=np.int64)
+    bad = C.c_uint64(0)
+    rc = L.wgbsseg_debug_fasta_walk(text, len(text), cap_s, cap_l, hdr.ctypes.data, bases.ctypes.data, sites.ctypes.data, nlen.ctypes.data, names.ctypes.data,
+                                    loci.ctypes.data, counts.ctypes.data, C.byref(bad))
+    if rc != OK:
+        raise SegmentorError(rc, 'debug_fasta_walk failed')
+    n, m = counts.tolist()
+    refusal = None if bad.value == 2 ** 64 - 1 else (bad.value >> 8, FA_REASONS[bad.value & 0xff])
+    return _fasta_table(n, hdr, bases, sites, nlen, names), loci[:m].copy(), refusal
 
 
 class Bimodal(_PatFeed):

@@ -19,7 +19,7 @@ ARCH = 'gfx950'
 HIPFLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-pthread']
 
 TARGETS = {
-    'libwgbsseg.so': (['wgbsseg.hip'], ['owners.h', 'env.h', 'seg_kernels.h', 'block_plan.h', 'block_kernels.h', 'plain_dp.h', 'wave_prims.h', 'exact_log2.h', 'stitch.h', 'add_loci.h', 'table_io.h', 'pat_kernels.h', 'pat_engines.h', 'row_engines.h', 'homog_plan.h', 'homog_kernels.h', 'frag_plan.h', 'frag_kernels.h', 'view_core.h', 'view_plan.h', 'view_kernels.h', 'mask_plan.h', 'bimodal_plan.h', 'bimodal_kernels.h', 'inflate_core.h', 'inflate_plan.h', 'inflate_kernels.h', 'deflate_core.h', 'deflate_plan.h', 'deflate_kernels.h', 'stats_plan.h', 'stats_kernels.h', 'merge_plan.h', 'merge_kernels.h', 'pair_plan.h', 'pair_kernels.h', 'bed_fmt.h', 'bed_plan.h', 'bed_kernels.h', 'array_plan.h', 'array_kernels.h', 'bed2beta_core.h', 'bed2beta_plan.h', 'bed2beta_kernels.h', 'sam_core.h', 'sam_plan.h', 'sam_kernels.h', 'share_plan.h', '../../include/wgbsseg.h']),
+    'libwgbsseg.so': (['wgbsseg.hip'], ['owners.h', 'env.h', 'seg_kernels.h', 'block_plan.h', 'block_kernels.h', 'plain_dp.h', 'wave_prims.h', 'exact_log2.h', 'stitch.h', 'add_loci.h', 'table_io.h', 'pat_kernels.h', 'pat_engines.h', 'row_engines.h', 'homog_plan.h', 'homog_kernels.h', 'frag_plan.h', 'frag_kernels.h', 'view_core.h', 'view_plan.h', 'view_kernels.h', 'mask_plan.h', 'bimodal_plan.h', 'bimodal_kernels.h', 'inflate_core.h', 'inflate_plan.h', 'inflate_kernels.h', 'deflate_core.h', 'deflate_plan.h', 'deflate_kernels.h', 'stats_plan.h', 'stats_kernels.h', 'merge_plan.h', 'merge_kernels.h', 'pair_plan.h', 'pair_kernels.h', 'bed_fmt.h', 'bed_plan.h', 'bed_kernels.h', 'array_plan.h', 'array_kernels.h', 'bed2beta_core.h', 'bed2beta_plan.h', 'bed2beta_kernels.h', 'sam_core.h', 'sam_plan.h', 'sam_kernels.h', 'fasta_core.h', 'fasta_plan.h', 'fasta_kernels.h', 'share_plan.h', '../../include/wgbsseg.h']),
     'libwgbssynth.so': (['synth.hip'], []),
 }
 

@@ -1,5 +1,5 @@
 // pat_engines.h — the engines that take pat text in chunks (wgbsseg_patbeta, wgbsseg_homog, wgbsseg_fraglen, wgbsseg_bimodal, wgbsseg_patview) and the one that takes BED
-// text the same way (wgbsseg_bedbeta, at the end), the feed they share
+// text the same way (wgbsseg_bedbeta) and the one that takes FASTA text cut at any byte (wgbsseg_fasta, at the end), the feed they share
 // (PatFeed, PrevRead), the stand-alone wgbsseg_bgzf_inflate and their extern "C" entry points.  Part of wgbsseg.hip, which includes it once set_err, HIP_TRY, check_device and the owners are
 // in scope; what an engine decides on the host is in homog_plan.h, frag_plan.h, bimodal_plan.h, view_plan.h and bed2beta_plan.h, this file stages, launches and fetches.
 #pragma once
@@ -193,6 +193,43 @@ struct PatFeed {
         const int64_t n = (int64_t)last.size(), gx = tiles_of(Engine::name, n, err, errlen);
         if (gx < 0) return WGBSSEG_E_ARG;
         return pat_chunk(e, n, gx, [&](const char** dev) { return e->feed.stage_chunk(last.data(), n, dev, err, errlen); }, err, errlen);      // (copied before this returns)
+    }
+    // The byte-cut path (wgbsseg_fasta): a chunk may end anywhere, so there is no line check, no line rule and no host carry; what a
+    // chunk leaves open is the engine's own business, on the device.  The same pat_chunk hook, staging and spans as above.
+    template <class Engine>
+    static int feed_bytes(Engine* e, const char* host, int64_t n_bytes, char* err, size_t errlen)
+    {
+        if (!e || (n_bytes && !host) || n_bytes < 0) { set_err(err, errlen, "bad arguments to %s_feed", Engine::name); return WGBSSEG_E_ARG; }
+        if (n_bytes == 0) return WGBSSEG_OK;
+        const int64_t gx = tiles_of(Engine::name, n_bytes, err, errlen);
+        if (gx < 0) return WGBSSEG_E_ARG;
+        PatFeed& f = e->feed;
+        const int rc = f.claim(TEXT, Engine::name, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        return pat_chunk(e, n_bytes, gx, [&](const char** dev) { return f.stage_chunk(host, n_bytes, dev, err, errlen); }, err, errlen);
+    }
+    template <class Engine>
+    static int feed_bgzf_bytes(Engine* e, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+    {
+        if (!e || !consumed || n_bytes < 0 || (n_bytes && !bytes)) { set_err(err, errlen, "bad arguments to %s_feed_bgzf", Engine::name); return WGBSSEG_E_ARG; }
+        *consumed = 0;
+        PatFeed& f = e->feed;
+        int rc = f.claim(BGZF, Engine::name, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        BgzfPlan p;
+        std::string msg;
+        rc = plan_bgzf_bytes(static_cast<const uint8_t*>(bytes), n_bytes, f.file_off, p, msg);
+        if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+        if (p.n_text > 0) {
+            const int64_t gx = tiles_of(Engine::name, p.n_text, err, errlen);
+            if (gx < 0) return WGBSSEG_E_ARG;
+            HIP_TRY(hipSetDevice(f.device));
+            rc = pat_chunk(e, p.n_text, gx, [&](const char** dev) { return f.stage_bgzf(bytes, p, dev, err, errlen); }, err, errlen);
+            if (rc != WGBSSEG_OK) return rc;
+        }
+        f.file_off += (unsigned long long)p.consumed;
+        *consumed = p.consumed;
+        return WGBSSEG_OK;
     }
     // finish(): a member k_bgzf_inflate refused comes before any refusal of the text.  Waits for the stream.
     int inflate_refused(char* err, size_t errlen)
@@ -1702,6 +1739,416 @@ double wgbsseg_bedbeta_kernel_ms(wgbsseg_bedbeta* b)
 double wgbsseg_bedbeta_inflate_ms(wgbsseg_bedbeta* b)
 {
     return b ? b->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
+}
+
+}  // extern "C"
+
+// `wgbstools init_genome` on one device: FASTA text through the feed's byte-cut path (a chunk may end anywhere) -> the sequence table and
+// the loci of every CpG in FASTA order (fasta_kernels.h has the launch sequence; the carry between chunks is a few words on the device);
+// then select() gathers the kept sequences' loci in dictionary order (that array is loci.u32) and dict() writes `name \t locus \t site`
+// for them and deflates the text into BGZF by the codec's launch sequence.  The chunk launches are the LAUNCHES span; gather, emit and
+// deflate have events of their own.
+struct wgbsseg_fasta {
+    enum { GATHER = 0, EMIT = 1, DEFLATE = 2 };
+    static constexpr const char* name = "fasta";
+    PatFeed feed;
+    DevBuf tiles, entries, carry, bad, totals, seqs, loci;
+    PinnedBuf home;
+    int64_t cap_seqs = 0, cap_loci = 0;                           // what seqs / loci have room for
+    int64_t n_seqs = 0, n_loci = 0;                               // what they hold (the chunks fed so far)
+    bool scanned = false, selected = false, written = false;
+    std::vector<wg_fa_seq> table;                                 // finish_scan(): the records at home ...
+    std::vector<int64_t> n_bases, n_sites;                        // ... and what follows from them
+    DevBuf sel, cum, names, name_len, wg, text, slots, meta, dense;
+    int64_t n_sel = 0, n_chroms = 0;
+    const void* out = nullptr;
+    int64_t out_bytes = 0;
+    PinnedBuf fetch;
+    Event ph[3][2];
+    bool timed[3] = {false, false, false};
+    double phase_ms[3] = {0.0, 0.0, 0.0};
+    ~wgbsseg_fasta() { feed.drain(); }
+};
+
+// room for `seqs` records and `loci` loci, by view_plan.h's growth rule; what the buffers hold is kept (the stream is idle)
+static int fasta_reserve(wgbsseg_fasta* f, int64_t seqs, int64_t loci, char* err, size_t errlen)
+{
+    const int64_t ns = wg_view_grow(f->cap_seqs, seqs), nl = wg_view_grow(f->cap_loci, loci);
+    if (ns != f->cap_seqs) {
+        DevBuf fresh;
+        HIP_TRY(fresh.ensure((size_t)ns * sizeof(wg_fa_seq)));
+        if (f->n_seqs) HIP_TRY(hipMemcpy(fresh.p, f->seqs.p, (size_t)f->n_seqs * sizeof(wg_fa_seq), hipMemcpyDeviceToDevice));
+        f->seqs = std::move(fresh);
+        f->cap_seqs = ns;
+    }
+    if (nl != f->cap_loci) {
+        DevBuf fresh;
+        HIP_TRY(fresh.ensure((size_t)nl * 4));
+        if (f->n_loci) HIP_TRY(hipMemcpy(fresh.p, f->loci.p, (size_t)f->n_loci * 4, hipMemcpyDeviceToDevice));
+        f->loci = std::move(fresh);
+        f->cap_loci = nl;
+    }
+    return WGBSSEG_OK;
+}
+
+static hipError_t fasta_phase(wgbsseg_fasta* f, int which, int end)
+{
+    if (!end) f->timed[which] = true;
+    return hipEventRecord(f->ph[which][end], f->feed.st);
+}
+
+static void fasta_read_phases(wgbsseg_fasta* f)
+{
+    for (int k = 0; k < 3; k++) {
+        float ms = 0.f;
+        if (f->timed[k] && hipEventElapsedTime(&ms, f->ph[k][0], f->ph[k][1]) == hipSuccess) f->phase_ms[k] = (double)ms;
+    }
+}
+
+// A staged chunk of n_bytes / gx tiles: settle the pending C -> measure -> scan -> the totals come home (the first wait) -> reserve ->
+// pack.  The second wait is the staging slot's, two chunks on.  The loci buffer always has room for one site more than it holds: the
+// next chunk's k_fa_settle may add the pending one.
+template <class Stage>
+static int pat_chunk(wgbsseg_fasta* f, int64_t n_bytes, int64_t gx, Stage&& stage, char* err, size_t errlen)
+{
+    PatFeed& fd = f->feed;
+    const hipStream_t st = fd.st;
+    HIP_TRY(hipSetDevice(fd.device));
+    if (f->scanned) { set_err(err, errlen, "fasta_feed: finish_scan() has been called"); return WGBSSEG_E_STATE; }
+    std::string msg;
+    int rc = plan_fasta_chunk(n_bytes, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    HIP_TRY(f->tiles.ensure((size_t)gx * sizeof(wg_fa_tile))); HIP_TRY(f->entries.ensure((size_t)gx * sizeof(wg_fa_entry)));
+    const char* dtext = nullptr;
+    rc = stage(&dtext);
+    if (rc != WGBSSEG_OK) return rc;
+    wg_fa_carry* carry = f->carry.as<wg_fa_carry>();
+    uint64_t* home = static_cast<uint64_t*>(f->home.p);
+    HIP_TRY(fd.span_begin());
+    hipLaunchKernelGGL(k_fa_settle, dim3(1), dim3(1), 0, st, dtext, n_bytes, carry, f->loci.as<uint32_t>());
+    hipLaunchKernelGGL(k_fa_measure, dim3((unsigned)gx), dim3(WG_FA_BLOCK), 0, st, dtext, n_bytes, f->tiles.as<wg_fa_tile>());
+    hipLaunchKernelGGL(k_fa_scan, dim3(1), dim3(WG_FA_SCAN_BLOCK), 0, st, f->tiles.as<const wg_fa_tile>(), gx, (uint64_t)fd.fed, carry, f->entries.as<wg_fa_entry>(),
+                       f->totals.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(fd.span_end());
+    HIP_TRY(hipMemcpyAsync(home, f->totals.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    fd.collect();
+    const int64_t seqs = (int64_t)home[0], loci = (int64_t)home[1];
+    if (seqs < f->n_seqs || loci < f->n_loci || seqs - f->n_seqs > n_bytes || loci - f->n_loci > n_bytes + 1) {
+        set_err(err, errlen, "fasta: the scan of a chunk of %lld bytes reports %lld sequences and %lld sites behind %lld and %lld", (long long)n_bytes, (long long)seqs,
+                (long long)loci, (long long)f->n_seqs, (long long)f->n_loci);
+        return WGBSSEG_E_HIP;
+    }
+    rc = fasta_reserve(f, seqs, loci + 1, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    f->n_seqs = seqs; f->n_loci = loci;
+    HIP_TRY(fd.span_begin());
+    hipLaunchKernelGGL(k_fa_pack, dim3((unsigned)gx), dim3(WG_FA_BLOCK), 0, st, dtext, n_bytes, (uint64_t)fd.fed, f->entries.as<const wg_fa_entry>(), f->seqs.as<wg_fa_seq>(),
+                       f->loci.as<uint32_t>(), f->bad.as<unsigned long long>(), carry);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(fd.span_end());
+    HIP_TRY(fd.chunk_queued(n_bytes));
+    return WGBSSEG_OK;
+}
+
+// text[0, n) deflated into f->dense, the end-of-file member behind it (the member rule and the kernels of wgbsseg_bgzf_deflate)
+static int fasta_deflate(wgbsseg_fasta* f, int64_t n, int64_t* bytes, char* err, size_t errlen)
+{
+    const hipStream_t st = f->feed.st;
+    const int64_t members = wg_deflate_members(n), bound = wg_deflate_bound(n);
+    if ((members + WG_DEF_WAVES - 1) / WG_DEF_WAVES > 0x7fffffff) { set_err(err, errlen, "fasta_dict: too much text to deflate in one call"); return WGBSSEG_E_ARG; }
+    HIP_TRY(f->dense.ensure((size_t)bound));
+    uint64_t total = 0;
+    if (members) {
+        HIP_TRY(f->slots.ensure((size_t)members * WG_DEF_PITCH)); HIP_TRY(f->meta.ensure((size_t)(2 * members + 2) * 8));
+        uint64_t *sizes = f->meta.as<uint64_t>(), *first = sizes + members, *dtot = first + members;
+        HIP_TRY(fasta_phase(f, wgbsseg_fasta::DEFLATE, 0));
+        hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)((members + WG_DEF_WAVES - 1) / WG_DEF_WAVES)), dim3(64 * WG_DEF_WAVES), 0, st,
+                           f->text.as<const uint8_t>(), n, members, f->slots.as<uint8_t>(), sizes);
+        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, sizes, sizes, members, first, dtot);
+        hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)members), dim3(WG_PACK_BLOCK), 0, st, f->slots.as<const uint8_t>(), sizes, first, f->dense.as<uint8_t>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(fasta_phase(f, wgbsseg_fasta::DEFLATE, 1));
+        HIP_TRY(hipMemcpyAsync(&total, dtot, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((int64_t)total > bound - (int64_t)sizeof(WG_BGZF_EOF)) { set_err(err, errlen, "fasta_dict: %llu bytes came out of the deflate, more than the bound", (unsigned long long)total); return WGBSSEG_E_HIP; }
+    }
+    HIP_TRY(hipMemcpyAsync(f->dense.as<uint8_t>() + total, WG_BGZF_EOF, sizeof(WG_BGZF_EOF), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *bytes = (int64_t)total + (int64_t)sizeof(WG_BGZF_EOF);
+    return WGBSSEG_OK;
+}
+
+// what wgbsseg_debug_fasta_walk's walk leaves: the tables of the caller
+struct FastaHostSink {
+    int64_t cap_seqs, cap_loci;
+    int64_t *hdr_off, *prev_bases, *first_locus;
+    int32_t* name_len;
+    char* names;
+    uint32_t* loci;
+    uint64_t bad = ~0ULL;
+    bool full = false;
+    void header(const wg_fa_cur& c, uint64_t at)
+    {
+        if ((int64_t)c.seqs >= cap_seqs) { full = true; return; }
+        hdr_off[c.seqs] = (int64_t)at; first_locus[c.seqs] = (int64_t)c.hits; prev_bases[c.seqs] = (int64_t)c.bases; name_len[c.seqs] = -1;
+    }
+    void name_byte(uint64_t seq, uint32_t idx, char b) { if ((int64_t)seq < cap_seqs) names[seq * (WG_FA_MAX_NAME + 1) + idx] = b; }
+    void name_end(uint64_t seq, uint64_t len) { if ((int64_t)seq < cap_seqs) name_len[seq] = (int32_t)std::min<uint64_t>(len, WG_FA_MAX_NAME + 1); }
+    void hit(uint64_t index, uint64_t locus) { if ((int64_t)index < cap_loci) loci[index] = (uint32_t)locus; else full = true; }
+    void pending(uint64_t) {}                                      // (the text ends: no next base)
+    void refuse(uint64_t at, int why) { bad = std::min<uint64_t>(bad, (at << 8) | (uint64_t)why); }
+};
+
+extern "C" {
+
+int wgbsseg_fasta_create(int device, wgbsseg_fasta** out, char* err, size_t errlen)
+{
+    if (!out) { set_err(err, errlen, "out is NULL"); return WGBSSEG_E_ARG; }
+    *out = nullptr;
+    std::unique_ptr<wgbsseg_fasta> f(new (std::nothrow) wgbsseg_fasta());      // (a failing call below frees what has been made)
+    if (!f) { set_err(err, errlen, "out of host memory"); return WGBSSEG_E_NOMEM; }
+    int rc = f->feed.open(device, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    for (auto& p : f->ph) for (auto& e : p) HIP_TRY(e.create());
+    HIP_TRY(f->carry.ensure(sizeof(wg_fa_carry))); HIP_TRY(f->bad.ensure(8)); HIP_TRY(f->totals.ensure(16));
+    if (!f->home.ensure(16)) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    rc = fasta_reserve(f.get(), WG_FA_INITIAL_SEQS, WG_FA_INITIAL_LOCI, err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    HIP_TRY(hipMemsetAsync(f->carry.p, 0, sizeof(wg_fa_carry), f->feed.st));      // at the start of a line, nothing seen, nothing pending
+    HIP_TRY(hipMemsetAsync(f->bad.p, 0xff, 8, f->feed.st));
+    *out = f.release();
+    return WGBSSEG_OK;
+}
+
+void wgbsseg_fasta_destroy(wgbsseg_fasta* f) { delete f; }
+
+int wgbsseg_fasta_feed(wgbsseg_fasta* f, const char* text, int64_t n_bytes, char* err, size_t errlen)
+{
+    return PatFeed::feed_bytes(f, text, n_bytes, err, errlen);
+}
+
+int wgbsseg_fasta_feed_bgzf(wgbsseg_fasta* f, const void* bytes, int64_t n_bytes, int64_t* consumed, char* err, size_t errlen)
+{
+    return PatFeed::feed_bgzf_bytes(f, bytes, n_bytes, consumed, err, errlen);
+}
+
+// The end of the input: a refused BGZF member before a refusal of the text; the record table comes home, the last sequence is closed
+// (a C left pending has no next base), two sequences of one name are refused.  counts: sequences, sites, bytes of text.
+int wgbsseg_fasta_finish_scan(wgbsseg_fasta* f, int64_t* counts, char* err, size_t errlen)
+{
+    if (!f || !counts) { set_err(err, errlen, "bad arguments to fasta_finish_scan"); return WGBSSEG_E_ARG; }
+    if (f->scanned) { set_err(err, errlen, "fasta_finish_scan: called twice"); return WGBSSEG_E_STATE; }
+    const hipStream_t st = f->feed.st;
+    HIP_TRY(hipSetDevice(f->feed.device));
+    f->scanned = true;
+    wg_fa_carry carry;
+    unsigned long long bad = ~0ULL;
+    HIP_TRY(hipMemcpyAsync(&carry, f->carry.p, sizeof(carry), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&bad, f->bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    f->feed.collect();
+    int rc = f->feed.inflate_refused(err, errlen);
+    if (rc != WGBSSEG_OK) return rc;
+    std::string msg;
+    if (bad != ~0ULL) { rc = wg_fa_refuse(msg, bad); set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    if ((int64_t)carry.seqs != f->n_seqs || (int64_t)carry.hits != f->n_loci) { set_err(err, errlen, "fasta_finish_scan: the carry and the totals disagree"); return WGBSSEG_E_HIP; }
+    const size_t n = (size_t)f->n_seqs;
+    f->table.resize(n);
+    if (n) HIP_TRY(hipMemcpy(f->table.data(), f->seqs.p, n * sizeof(wg_fa_seq), hipMemcpyDeviceToHost));
+    if (n && carry.state == WG_FA_NM) {                            // the text ends inside the last name
+        const uint64_t len = (uint64_t)f->feed.fed - carry.hdr_off - 1;
+        if (len == 0) { rc = wg_fa_refuse(msg, (carry.hdr_off << 8) | WG_FA_BAD_EMPTY_NAME); set_err(err, errlen, "%s", msg.c_str()); return rc; }
+        f->table[n - 1].name_len = (uint32_t)len;
+    }
+    f->n_bases.assign(n, 0); f->n_sites.assign(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        f->n_bases[i] = i + 1 < n ? (int64_t)f->table[i + 1].prev_bases : (int64_t)carry.bases;
+        f->n_sites[i] = (int64_t)((i + 1 < n ? f->table[i + 1].first_locus : (uint64_t)f->n_loci) - f->table[i].first_locus);
+    }
+    rc = plan_fasta_names(f->table, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    counts[0] = f->n_seqs; counts[1] = f->n_loci; counts[2] = (int64_t)f->feed.fed;
+    return WGBSSEG_OK;
+}
+
+// the table of finish_scan(): per sequence the offset of its header, its bases, its sites, the length of its name and the name
+// (WG_FA_MAX_NAME + 1 bytes each, zero-padded)
+int wgbsseg_fasta_sequences(wgbsseg_fasta* f, int64_t* hdr_off, int64_t* n_bases, int64_t* n_sites, int32_t* name_len, char* names, char* err, size_t errlen)
+{
+    if (!f || !f->scanned) { set_err(err, errlen, "fasta_sequences: nothing to read before finish_scan()"); return WGBSSEG_E_STATE; }
+    for (size_t i = 0; i < f->table.size(); i++) {
+        const wg_fa_seq& s = f->table[i];
+        if (hdr_off) hdr_off[i] = (int64_t)s.hdr_off;
+        if (n_bases) n_bases[i] = f->n_bases[i];
+        if (n_sites) n_sites[i] = f->n_sites[i];
+        if (name_len) name_len[i] = (int32_t)s.name_len;
+        if (names) {
+            char* dst = names + i * (WG_FA_MAX_NAME + 1);
+            memset(dst, 0, WG_FA_MAX_NAME + 1);
+            memcpy(dst, s.name, std::min<size_t>(s.name_len, WG_FA_MAX_NAME));
+        }
+    }
+    return WGBSSEG_OK;
+}
+
+// The kept sequences in dictionary order: their loci gathered into one array (a device-to-device copy per sequence), the cumulative
+// table and the names to the device.  *n_sites: the sites of the dictionary.
+int wgbsseg_fasta_select(wgbsseg_fasta* f, const int64_t* order, int64_t n_order, int64_t* n_sites, char* err, size_t errlen)
+{
+    if (!f || !n_sites) { set_err(err, errlen, "bad arguments to fasta_select"); return WGBSSEG_E_ARG; }
+    if (!f->scanned || f->table.size() != (size_t)f->n_seqs) { set_err(err, errlen, "fasta_select: finish_scan() comes first"); return WGBSSEG_E_STATE; }
+    std::string msg;
+    int64_t total = 0;
+    const int rc = plan_fasta_select(order, n_order, f->n_seqs, f->n_sites, &total, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    const hipStream_t st = f->feed.st;
+    HIP_TRY(hipSetDevice(f->feed.device));
+    std::vector<int64_t> cum((size_t)n_order);
+    std::vector<uint32_t> lens((size_t)n_order);
+    std::vector<char> names((size_t)n_order * (WG_FA_MAX_NAME + 1), 0);
+    HIP_TRY(f->sel.ensure((size_t)std::max<int64_t>(total, 1) * 4)); HIP_TRY(f->cum.ensure(cum.size() * 8)); HIP_TRY(f->name_len.ensure(lens.size() * 4));
+    HIP_TRY(f->names.ensure(names.size()));
+    HIP_TRY(fasta_phase(f, wgbsseg_fasta::GATHER, 0));
+    int64_t at = 0;
+    for (int64_t k = 0; k < n_order; k++) {
+        const wg_fa_seq& s = f->table[(size_t)order[k]];
+        const int64_t m = f->n_sites[(size_t)order[k]];
+        if (m) HIP_TRY(hipMemcpyAsync(f->sel.as<uint32_t>() + at, f->loci.as<uint32_t>() + s.first_locus, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
+        at += m;
+        cum[(size_t)k] = at; lens[(size_t)k] = s.name_len;
+        memcpy(names.data() + (size_t)k * (WG_FA_MAX_NAME + 1), s.name, s.name_len);
+    }
+    HIP_TRY(fasta_phase(f, wgbsseg_fasta::GATHER, 1));
+    HIP_TRY(hipMemcpyAsync(f->cum.p, cum.data(), cum.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(f->name_len.p, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(f->names.p, names.data(), names.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));                             // (the vectors go)
+    fasta_read_phases(f);
+    f->n_sel = total; f->n_chroms = n_order;
+    f->selected = true; f->written = false;
+    *n_sites = total;
+    return WGBSSEG_OK;
+}
+
+// the gathered loci: what loci.u32 holds
+int wgbsseg_fasta_loci(wgbsseg_fasta* f, uint32_t* out, int64_t n, char* err, size_t errlen)
+{
+    if (!f || !f->selected) { set_err(err, errlen, "fasta_loci: select() comes first"); return WGBSSEG_E_STATE; }
+    if (n != f->n_sel || (n && !out)) { set_err(err, errlen, "fasta_loci: room for %lld loci, the dictionary has %lld", (long long)n, (long long)f->n_sel); return WGBSSEG_E_ARG; }
+    HIP_TRY(hipSetDevice(f->feed.device));
+    if (n) HIP_TRY(hipMemcpyAsync(out, f->sel.p, (size_t)n * 4, hipMemcpyDeviceToHost, f->feed.st));
+    HIP_TRY(hipStreamSynchronize(f->feed.st));
+    return WGBSSEG_OK;
+}
+
+// the dictionary's text (CpG.bed) for the selected sites, as BGZF with deflate; it stays on the device for read()
+int wgbsseg_fasta_dict(wgbsseg_fasta* f, int32_t deflate, int64_t* n_lines, int64_t* n_bytes, char* err, size_t errlen)
+{
+    if (!f || !n_lines || !n_bytes) { set_err(err, errlen, "bad arguments to fasta_dict"); return WGBSSEG_E_ARG; }
+    *n_lines = *n_bytes = 0;
+    if (!f->selected) { set_err(err, errlen, "fasta_dict: select() comes first"); return WGBSSEG_E_STATE; }
+    const hipStream_t st = f->feed.st;
+    HIP_TRY(hipSetDevice(f->feed.device));
+    const int64_t n = f->n_sel, nb = (n + WG_FA_DICT_BLOCK - 1) / WG_FA_DICT_BLOCK;
+    uint64_t got[2] = {0, 0};
+    if (n) {
+        HIP_TRY(f->wg.ensure((size_t)(3 * nb + 2) * 8));
+        uint64_t *wg_bytes = f->wg.as<uint64_t>(), *wg_lines = wg_bytes + nb, *wg_base = wg_lines + nb, *tot = wg_base + nb;
+        const wg_dict_args a = {f->sel.as<const uint32_t>(), f->cum.as<const int64_t>(), f->names.as<const char>(), f->name_len.as<const uint32_t>(), n, (int32_t)f->n_chroms};
+        HIP_TRY(fasta_phase(f, wgbsseg_fasta::EMIT, 0));
+        hipLaunchKernelGGL(k_dict_len, dim3((unsigned)nb), dim3(WG_FA_DICT_BLOCK), 0, st, a, wg_bytes, wg_lines);
+        hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(WG_BED_BLOCK), 0, st, wg_bytes, wg_lines, nb, wg_base, tot);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(got, tot, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if ((int64_t)got[1] != n || got[0] > (uint64_t)n * WG_FA_DICT_MAX_LINE) { set_err(err, errlen, "fasta_dict: %llu bytes in %llu lines for %lld sites", (unsigned long long)got[0], (unsigned long long)got[1], (long long)n); return WGBSSEG_E_HIP; }
+        HIP_TRY(f->text.ensure((size_t)got[0] + 16));
+        hipLaunchKernelGGL(k_dict_emit, dim3((unsigned)nb), dim3(WG_FA_DICT_BLOCK), 0, st, a, wg_base, f->text.as<char>());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(fasta_phase(f, wgbsseg_fasta::EMIT, 1));
+    } else
+        HIP_TRY(f->text.ensure(16));
+    f->out = f->text.p; f->out_bytes = (int64_t)got[0];
+    if (deflate) {
+        const int rc = fasta_deflate(f, (int64_t)got[0], &f->out_bytes, err, errlen);
+        if (rc != WGBSSEG_OK) return rc;
+        f->out = f->dense.p;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    fasta_read_phases(f);
+    f->written = true;
+    *n_lines = n; *n_bytes = f->out_bytes;
+    return WGBSSEG_OK;
+}
+
+// bytes [offset, offset + len) of dict()'s result, in slabs through page-locked staging
+int wgbsseg_fasta_read(wgbsseg_fasta* f, int64_t offset, void* buf, int64_t len, char* err, size_t errlen)
+{
+    if (!f || !f->written) { set_err(err, errlen, "fasta_read: nothing to read before dict()"); return WGBSSEG_E_STATE; }
+    std::string msg;
+    const int rc = plan_view_read(offset, len, f->out_bytes, buf, msg);
+    if (rc != WGBSSEG_OK) { set_err(err, errlen, "%s", msg.c_str()); return rc; }
+    if (len == 0) return WGBSSEG_OK;
+    HIP_TRY(hipSetDevice(f->feed.device));
+    if (!f->fetch.ensure_exact((size_t)std::min<int64_t>(len, WG_VIEW_SLAB))) { set_err(err, errlen, "out of page-locked host memory"); return WGBSSEG_E_NOMEM; }
+    const char* src = static_cast<const char*>(f->out) + offset;
+    for (int64_t k = 0; k < wg_view_slabs(len); k++) {
+        const int64_t nb = wg_view_slab_len(len, k);
+        HIP_TRY(hipMemcpyAsync(f->fetch.p, src + k * WG_VIEW_SLAB, (size_t)nb, hipMemcpyDeviceToHost, f->feed.st));
+        HIP_TRY(hipStreamSynchronize(f->feed.st));
+        memcpy(static_cast<char*>(buf) + k * WG_VIEW_SLAB, f->fetch.p, (size_t)nb);
+    }
+    return WGBSSEG_OK;
+}
+
+double wgbsseg_fasta_kernel_ms(wgbsseg_fasta* f)
+{
+    return f ? f->feed.kernel_ms() : -1.0;
+}
+
+double wgbsseg_fasta_inflate_ms(wgbsseg_fasta* f)
+{
+    return f ? f->feed.kernel_ms(PatFeed::INFLATE) : -1.0;
+}
+
+void wgbsseg_fasta_phase_ms(const wgbsseg_fasta* f, double* gather_ms, double* emit_ms, double* deflate_ms)
+{
+    if (gather_ms) *gather_ms = f ? f->phase_ms[wgbsseg_fasta::GATHER] : 0.0;
+    if (emit_ms) *emit_ms = f ? f->phase_ms[wgbsseg_fasta::EMIT] : 0.0;
+    if (deflate_ms) *deflate_ms = f ? f->phase_ms[wgbsseg_fasta::DEFLATE] : 0.0;
+}
+
+// The rule on the host, serially: fasta_core.h's walk over text[0, n) — what the engine's kernels run 16 bytes at a time — into the
+// caller's tables (room for cap_seqs sequences and cap_loci loci; names: WG_FA_MAX_NAME + 1 bytes per sequence).  counts: sequences,
+// sites.  *refused: (offset << 8 | reason) of the first refusal, ~0: none.  No device is touched.
+int wgbsseg_debug_fasta_walk(const char* text, int64_t n, int64_t cap_seqs, int64_t cap_loci, int64_t* hdr_off, int64_t* n_bases, int64_t* n_sites, int32_t* name_len,
+                             char* names, uint32_t* loci, int64_t* counts, uint64_t* refused)
+{
+    if (n < 0 || (n && !text) || cap_seqs < 0 || cap_loci < 0 || !counts || !refused) return WGBSSEG_E_ARG;
+    if (cap_seqs && (!hdr_off || !n_bases || !n_sites || !name_len || !names)) return WGBSSEG_E_ARG;
+    if (cap_loci && !loci) return WGBSSEG_E_ARG;
+    std::vector<int64_t> prev((size_t)cap_seqs), first((size_t)cap_seqs);
+    if (cap_seqs) memset(names, 0, (size_t)cap_seqs * (WG_FA_MAX_NAME + 1));
+    FastaHostSink k = {cap_seqs, cap_loci, hdr_off, prev.data(), first.data(), name_len, names, loci};
+    wg_fa_cur c = {0, 0, 0, 0, WG_FA_LS};
+    const wg_fa_plain_text T = {text};
+    wg_fa_walk(T, n, 0, n, 0, c, k);
+    counts[0] = (int64_t)c.seqs; counts[1] = (int64_t)c.hits;
+    *refused = k.bad;
+    if (k.full) return WGBSSEG_E_CAPACITY;
+    const int64_t m = (int64_t)c.seqs;
+    if (m && c.state == WG_FA_NM) {                                // the text ends inside the last name
+        const uint64_t len = (uint64_t)n - c.hdr_off - 1;
+        if (len == 0) *refused = std::min<uint64_t>(*refused, (c.hdr_off << 8) | WG_FA_BAD_EMPTY_NAME);
+        name_len[m - 1] = (int32_t)std::min<uint64_t>(len, WG_FA_MAX_NAME + 1);
+    }
+    for (int64_t i = 0; i < m; i++) {
+        n_bases[i] = i + 1 < m ? prev[(size_t)i + 1] : (int64_t)c.bases;
+        n_sites[i] = (i + 1 < m ? first[(size_t)i + 1] : (int64_t)c.hits) - first[(size_t)i];
+    }
+    return WGBSSEG_OK;
 }
 
 }  // extern "C"

@@ -42,6 +42,7 @@
 #include "frag_kernels.h"
 #include "view_kernels.h"
 #include "sam_kernels.h"
+#include "fasta_kernels.h"
 #include "bimodal_kernels.h"
 #include "inflate_plan.h"
 #include "inflate_kernels.h"

@@ -14,7 +14,9 @@ view engine with a bitmap of hidden sites inside its cut) and `mix_pat` (in-sili
 file's reads by a counter-based binomial draw, tags them with their source and orders tied lines as the reference's `sort -m` does) and
 `bed2beta` (BED methylation calls of any pipeline joined to the CpG dictionary on the device, the first of duplicated lines kept: the door
 into the `.beta` files everything above reads) and `bam2pat` (SAM text — what `samtools view` prints — called against the CpG dictionary, mates
-merged and equal reads counted on the device, the same view engine behind it: the head of the pipeline, `.pat.gz` and `.beta` from alignments); every
+merged and equal reads counted on the device, the same view engine behind it: the head of the pipeline, `.pat.gz` and `.beta` from alignments) and
+`init_genome` / `set_default_ref` (the genome directory all of them start from: every CpG of a FASTA file found on the device, the dictionary's text
+formatted and deflated there; which directory is the default); every
 other reference subcommand is out of scope and says so."""
 import sys
 
@@ -23,12 +25,13 @@ from .genome import IllegalArgumentError, eprint
 VERSION = '0.2.0-mi355x'
 COMMANDS = ['segment', 'convert', 'pat2beta', 'beta_to_blocks', 'beta_to_table', 'find_markers', 'homog', 'test_bimodal',
             'beta_cov', 'beta_stats', 'compare_betas', 'beta2bed', 'beta_to_450k', 'frag_len', 'view', 'cview', 'merge', 'mask_pat', 'mix_pat',
-            'bed2beta', 'bam2pat']
+            'bed2beta', 'bam2pat', 'init_genome', 'set_default_ref']
 MODULES = {'cview': 'view'}            # commands that run another command's module
 # reference command list (wgbs_tools.py:11-48), for the "not in this build" message.  `view` is in both lists: COMMANDS is looked at first and
 # carries its pat side; of a .beta / .lbeta input view.py itself says that it is not part of this build (and names `beta2bed`).  `merge` likewise:
 # merge.py says what of it (--labels, -L, .bin) is not part of this build; `mix_pat`: mix_pat.py says it of -L; `bed2beta`: bed2beta.py says it of -d;
-# `bam2pat`: bam2pat.py says it of .bam / .cram inputs, of coordinate-sorted paired-end input and of -r / -s / -L, --blacklist, --mbias, --blueprint, --nanopore, --long, -rg, -d
+# `bam2pat`: bam2pat.py says it of .bam / .cram inputs, of coordinate-sorted paired-end input and of -r / -s / -L, --blacklist, --mbias, --blueprint, --nanopore, --long, -rg, -d;
+# `init_genome`: init_genome.py says it of a missing --fasta_path (no download) and of -d
 REFERENCE_ONLY = ['view', 'merge', 'index',
                   'beta2bw', 'bam2pat', 'mbias', 'init_genome', 'set_default_ref', 'vis', 'pat_fig',
                   'dmb', 'mix_pat', 'bed2beta',
